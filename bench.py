@@ -32,17 +32,10 @@ sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
 # A stream handle owns three HIP streams (main + two for the ordinary workers beside the tree replay);
-# the HIP runtime maps all streams of a process onto GPU_MAX_HW_QUEUES hardware queues (default 4)
-# and kernels of different streams that share a queue run one after the other.  With S streams per
-# process the runtime therefore needs 3 S queues (measured, 4 threads: 286 -> 348 frames/s with 16
-# queues; one stream: no difference).  Read once, at the first HIP call of the process.
-if "--streams" in sys.argv and "GPU_MAX_HW_QUEUES" not in os.environ:
-    try:
-        _s = int(sys.argv[sys.argv.index("--streams") + 1])
-        if _s > 1:
-            os.environ["GPU_MAX_HW_QUEUES"] = str(min(3 * _s + 1, 24))
-    except (IndexError, ValueError):
-        pass
+# the HIP runtime maps all streams of a process onto its default hardware queues, and kernels of
+# different streams that share a queue run one after the other, so --streams S > 1 (S threads of one
+# process) measures the streams sharing those queues.  The queue count is left at the runtime's
+# default.
 
 import numpy as np  # noqa: E402
 import torch  # noqa: E402  (first: a single HIP runtime per process, see video_segment_amd/_lib.py)
@@ -93,7 +86,15 @@ def parse():
     ap.add_argument("--no-extras", action="store_true",
                     help="skip the information-only legs after the timed region (other configs, other "
                          "inputs, several streams per GPU)")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned (rank 0, "
+                         "stream 0) as DIR/<name>.npy, see dump_outputs()")
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
+    if args.dump_outputs is not None and args.mode != "streams":
+        ap.error("--dump-outputs needs --mode streams")
+    return args
 
 
 def cpu_baseline(W, H, chunk, n_frames, device):
@@ -182,11 +183,57 @@ def make_frames(kind, W, H, n, dev, seed_shift=0, host=False):
     return frames
 
 
-def time_streams(vsg, frames, flow, W, H, chunk, S, warm, steps, device_index, barrier=None):
+DUMP_SEED = 20240607
+# what --dump-outputs may write: region ids with their pixel indices (float64 each), descriptor bytes
+# (float32) with their positions (float64), and one length per message -- under 60 MB in all
+DUMP_ID_BYTES = 36 << 20
+DUMP_DESC_BYTES = 20 << 20
+
+
+def dump_outputs(stream, n, W, H, directory):
+    """Writes what the last timed step handed its caller -- the n SegmentationDesc of the chunk
+    boundary -- as .npy files: `descriptor_lengths` (bytes per serialized message, float64 [n]),
+    `descriptor_bytes` (the n messages concatenated, one float32 per byte, at the positions listed in
+    `descriptor_byte_positions`: all of them, or above DUMP_DESC_BYTES a sorted sample drawn with
+    DUMP_SEED) and `region_ids` (float64 [n, P]: the region id of each frame's id image at the P
+    pixels listed as flat indices y * W + x in `region_id_pixels`: all of them, or above DUMP_ID_BYTES
+    the same sorted sample drawn with DUMP_SEED for every frame).  The pixel sample depends only on
+    W, H and n, so two builds run with the same arguments are compared value for value."""
+    os.makedirs(directory, exist_ok=True)
+    msgs = [stream.result_bytes(i) for i in range(n)]
+    lengths = np.array([len(m) for m in msgs], np.float64)
+    raw = np.frombuffer(b"".join(msgs), np.uint8)
+    n_bytes = DUMP_DESC_BYTES // (4 + 8)
+    if raw.size <= n_bytes:
+        byte_pos = np.arange(raw.size, dtype=np.int64)
+    else:
+        byte_pos = np.sort(np.random.default_rng([DUMP_SEED, 0]).choice(raw.size, n_bytes, replace=False))
+    n_px = max(1, min(W * H, DUMP_ID_BYTES // (8 * (n + 1))))
+    if n_px == W * H:
+        px = np.arange(W * H, dtype=np.int64)
+    else:
+        px = np.sort(np.random.default_rng([DUMP_SEED, 1]).choice(W * H, n_px, replace=False))
+    ids = np.stack([stream.result_id_image(i).reshape(-1)[px] for i in range(n)])
+    arrays = {"descriptor_lengths": lengths,
+              "descriptor_bytes": raw[byte_pos].astype(np.float32),
+              "descriptor_byte_positions": byte_pos.astype(np.float64),
+              "region_ids": ids.astype(np.float64),
+              "region_id_pixels": px.astype(np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(directory, name + ".npy"), a)
+    return {"dir": directory, "frames": n,
+            "arrays": dict((name, list(a.shape)) for name, a in arrays.items()),
+            "bytes": int(sum(a.nbytes for a in arrays.values()))}
+
+
+def time_streams(vsg, frames, flow, W, H, chunk, S, warm, steps, device_index, barrier=None,
+                 after_timed=None):
     """S independent streams (one host thread each) over the same resident frames (flow: one resident
     field for every frame, or a list with the field of frame k): `warm` untimed
     chunk boundaries per stream, then exactly `steps` timed ones between two synchronisations.
-    Every SegmentationDesc of a boundary is fetched inside the timed region."""
+    Every SegmentationDesc of a boundary is fetched inside the timed region.  after_timed(stream, n),
+    if given, is called after the timed region with stream 0 and the number of results of its last
+    timed boundary, before the streams are closed."""
     import threading
     torch.cuda.synchronize()
     in_use_before = vsg.memory_stats(device_index)["bytes_in_use"]
@@ -254,6 +301,9 @@ def time_streams(vsg, frames, flow, W, H, chunk, S, warm, steps, device_index, b
     run_all(steps, True)          # exactly `steps` timed boundaries per stream
     sync()
     dt = time.perf_counter() - t0
+    # (a stream's last process_frame call is the one that ended its last timed boundary: `_n` holds
+    # that boundary's number of results)
+    after = after_timed(streams[0], streams[0]._n) if after_timed is not None else None
     # what the streams hold on the device after warm-up and the timed chunks (their scratch only
     # grows): the library's own account of the blocks its live handles hold (vsg_device_memory_stats;
     # the drop in free device memory would miss blocks adopted from the cache of closed handles)
@@ -265,7 +315,7 @@ def time_streams(vsg, frames, flow, W, H, chunk, S, warm, steps, device_index, b
     spread = ({"min": all_steps[0], "median": all_steps[len(all_steps) // 2], "max": all_steps[-1]}
               if all_steps else None)
     return {"dt": dt, "frames": sum(outs), "acc": acc, "device_bytes_per_stream": int(device_bytes),
-            "step_ms": spread}
+            "step_ms": spread, "after_timed": after}
 
 
 def measured_copy_bandwidth(dev, nbytes=1 << 30, reps=5):
@@ -319,6 +369,11 @@ def stage_ms(acc, steps):
             "merge": acc["merge_ms"] / steps, "merge_wave_kernel": acc["wave_ms"] / steps,
             "merge_spine_kernel": acc["spine_ms"] / steps, "merge_filter_kernel": acc["filter_ms"] / steps,
             "readout": acc["readout_ms"] / steps, "host_post": acc["host_ms"] / steps}
+
+
+# the streams sweep of extra_measurements() keeps at most this many processes with the device open
+# (this one and the ranks of a sub-run)
+MAX_DEVICE_PROCESSES = 6
 
 
 def extra_measurements(vsg, args, dev, device_index, headline_fps, out):
@@ -619,7 +674,11 @@ def extra_measurements(vsg, args, dev, device_index, headline_fps, out):
     sweep = []
     for S in (1, 2, 4, 8):
         entry = {"streams": S}
-        if S == 1:
+        if 1 + S > MAX_DEVICE_PROCESSES:
+            d = None
+            entry["processes"] = {"skipped": "this process and %d ranks would be more than %d processes on "
+                                             "the device" % (S, MAX_DEVICE_PROCESSES)}
+        elif S == 1:
             d = sub_bench(lambda port: [os.path.abspath(__file__)])
         else:
             d = sub_bench(lambda port: ["-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(S),
@@ -649,12 +708,14 @@ def main():
     if not gpus_given:
         args.gpus = world      # `torchrun --nproc-per-node N bench.py` without --gpus
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
-        # `python bench.py --gpus N` without a launcher: start one rank per GPU ourselves.
-        os.execvp(sys.executable, [
+        # `python bench.py --gpus N` without a launcher: start one rank per GPU ourselves, in a
+        # child process (this one never touches the GPU).
+        import subprocess
+        sys.exit(subprocess.call([
             sys.executable, "-m", "torch.distributed.run", "--nnodes=1",
             "--nproc-per-node", str(args.gpus), "--master-addr", "127.0.0.1",
             "--master-port", os.environ.get("MASTER_PORT", "29533"), os.path.abspath(__file__)]
-            + sys.argv[1:])
+            + sys.argv[1:]))
     if gpus_given:
         assert world == args.gpus, "--gpus %d but WORLD_SIZE=%d" % (args.gpus, world)
     if world > 1:
@@ -694,7 +755,11 @@ def main():
             if world > 1:
                 dist.barrier()
 
-        r = time_streams(vsg, frames, flow, W, H, chunk, S, Wm, K, local_rank, barrier)
+        dump = None
+        if args.dump_outputs is not None and rank == 0:
+            def dump(stream, n):
+                return dump_outputs(stream, n, W, H, args.dump_outputs)
+        r = time_streams(vsg, frames, flow, W, H, chunk, S, Wm, K, local_rank, barrier, dump)
         tt = torch.tensor([r["dt"]], dtype=torch.float64, device=dev)
         fo = torch.tensor([r["frames"]], dtype=torch.float64, device=dev)
         ranks_info = None
@@ -723,7 +788,8 @@ def main():
         result = {"dt": float(tt.item()), "frames": float(fo.item()), "acc": r["acc"],
                   "step_ms": r["step_ms"],
                   "device_bytes_per_stream": r["device_bytes_per_stream"], "ranks": ranks_info,
-                  "parallelism": "%d independent 1080p stream(s) per GPU x %d GPU(s)" % (S, world)}
+                  "parallelism": "%d independent 1080p stream(s) per GPU x %d GPU(s)" % (S, world),
+                  "dump_outputs": r["after_timed"]}
         # PCIe-inclusive leg (rank 0, one stream, not `value`): the same steady-state chunks with
         # frames and flow handed over as host buffers, so that the H2D copies are timed as well.
         result["pcie"] = None
@@ -909,6 +975,8 @@ def main():
             out["pcie_inclusive"] = result["pcie"]
         if result.get("handoff"):
             out["config"]["handoff"] = result["handoff"]
+        if result.get("dump_outputs"):
+            out["dump_outputs"] = result["dump_outputs"]
         if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: the other ranks would wait)
             out["cpu_baseline"], threaded, out["parity_checked"] = cpu_baseline(
                 W, H, chunk, args.cpu_frames, local_rank)

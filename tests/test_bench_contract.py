@@ -46,6 +46,45 @@ def test_single_gpu_line_and_cpu_baseline():
 
 
 @pytest.mark.gpu
+def test_dump_outputs_hold_the_last_timed_step(tmp_path):
+    """--dump-outputs writes what the last timed step returned, within 64 MB: the same arrays as the
+    oracle's last chunk boundary over the same frames (two timed steps after one warm-up step)."""
+    import numpy as np
+    W, H, chunk, boundaries = 320, 240, 20, 3
+    d = tmp_path / "dump"
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
+                        "--width", str(W), "--height", str(H), "--no-cpu-baseline", "--no-pcie-leg",
+                        "--dump-outputs", str(d)],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = last_json_line(p.stdout)
+    check(out, 1, 2, 1)
+    assert out["dump_outputs"]["frames"] == chunk - 1
+    names = sorted(os.listdir(d))
+    assert names == sorted(n + ".npy" for n in out["dump_outputs"]["arrays"])
+    assert sum(os.path.getsize(d / n) for n in names) <= 64e6
+
+    import bench
+    import oracle_lib as ol
+    import synth
+    o = ol.OracleStream(W, H, ol.default_options(chunk_size=chunk), has_flow=True)
+    fl = synth.const_flow(W, H)
+    seen = 0
+    for k in range(chunk + (chunk - 1) * (boundaries - 1)):
+        n = o.process_frame(synth.bench_frame(W, H, k), fl if k > 0 else None)
+        if n:
+            seen += 1
+            last = n
+    assert seen == boundaries
+    bench.dump_outputs(o, last, W, H, str(tmp_path / "oracle"))
+    o.close()
+    for n in names:
+        got, want = np.load(d / n), np.load(tmp_path / "oracle" / n)
+        assert got.dtype in (np.float32, np.float64) and got.dtype == want.dtype, n
+        assert got.shape == want.shape and np.array_equal(got, want), n
+
+
+@pytest.mark.gpu
 @pytest.mark.parametrize("mode,port", [("streams", "29611"), ("chain", "29612")])
 def test_two_ranks_control_flow(mode, port):
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
