@@ -117,6 +117,24 @@ typedef struct vsg_diagnostics {
   int mail_mode;                 /* 0 spin, 1 yield, 2 sleep (VSG_MAIL_YIELD)                    */
 } vsg_diagnostics;
 
+/* Which paths of the ordered merge the last SegmentFullGraph call of a handle took (host counts; they
+ * cost no device sync or launch).  A separate struct so that vsg_diagnostics keeps its size.
+ * DESIGN 4.18-4.19. */
+typedef struct vsg_merge_paths {
+  int64_t hub_stages;                 /* stages that used hub regions                                  */
+  int64_t hub_absorbed;               /* regions absorbed through them                                 */
+  int64_t hub_cuts;                   /* stages cut at an edge that broke a rule                       */
+  int64_t hub_cuts_in_groups;         /* ... of a stage over a group of buckets                        */
+  int64_t hub_parts_in_later_bucket;  /* parts of a cut group stage that start in a later bucket       */
+  int64_t spine_side_cuts;            /* cuts at a kept edge of a tree replay's side cluster (b 0/1)   */
+  int64_t hub_retries;                /* stages whose hubs or assumptions broke a rule                 */
+  int64_t hub_reasons[6];             /* ... by reason: broken, inherit, shape, marked, pair, split    */
+  int64_t hub_exclusion_reruns;       /* reruns with the broken regions on the exclusion list          */
+  int64_t hub_off_reruns;             /* reruns without hubs                                           */
+  int64_t group_halvings;             /* failed group stages run again as two halves                   */
+  int64_t conservative_replays;       /* failed stages replayed edge by edge (inert_mode 0)            */
+} vsg_merge_paths;
+
 /* Device memory of the library, per device.  A closed handle leaves its blocks in a process-wide
  * cache and the next handle adopts them (no hipMalloc / hipFree after the first window of a caller
  * that creates a graph per window, dense_seg_graph_interface.h:58-98); the cached, unused bytes are
@@ -175,6 +193,7 @@ int vsg_stream_result_id_image(vsg_stream* s, int i, int32_t* out);
 int vsg_stream_last_merge_stats(const vsg_stream* s, int64_t* forced_regular_small);
 int vsg_stream_last_timings(const vsg_stream* s, vsg_timings* t);
 int vsg_stream_last_diagnostics(const vsg_stream* s, vsg_diagnostics* d);
+int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out);
 /* Parity hook: smoothed feature planes of the most recently added frame, W*H*3 f32 BGR
  * interleaved, host memory (PreprocessFeatures output, cpp:164-198). */
 int vsg_stream_last_smoothed(vsg_stream* s, float* out);
@@ -340,6 +359,7 @@ int vsg_graph_node_roots(vsg_graph* g, int32_t* out);
 int vsg_graph_merge_stats(const vsg_graph* g, int64_t* forced_regular_small);
 int vsg_graph_timings(const vsg_graph* g, vsg_timings* t);
 int vsg_graph_diagnostics(const vsg_graph* g, vsg_diagnostics* d);
+int vsg_graph_merge_paths(const vsg_graph* g, vsg_merge_paths* out);
 
 /* Test hook: the merge path's stable radix sort of (key, value) pairs by the low `end_bit` bits of
  * the keys (csrc/radix_sort.hip), on host arrays of n elements, run on `device`.  The reference sorts

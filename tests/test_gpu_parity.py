@@ -200,7 +200,11 @@ def test_seam3_region_list_constrained_chunk(vsg):
     assert len(gg.get_intervals(0)) == 0   # the virtual slice is never rasterized
 
 
-def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, **options):
+def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, on_chunk=None, **options):
+    """Streams N frames through the HIP library and the CPU oracle side by side; every call must give
+    the same number of results, the same SegmentationDesc bytes and the same merge statistics.
+    on_chunk(stream), if given, is called after every call that segmented a chunk (what that
+    chunk's merge did: stream.last_merge_paths())."""
     rng = np.random.default_rng(seed)
     go = vsg.default_options(chunk_size=chunk, **options)
     oo = ol.default_options(chunk_size=chunk, **options)
@@ -231,6 +235,8 @@ def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, **options)
                     (i, k, int((gi != oi).sum()), len(gb), len(ob)))
         if no:
             assert np.array_equal(gs.last_merge_stats(), os_.last_merge_stats())
+            if on_chunk is not None:
+                on_chunk(gs)
         total += no
     assert total == N
     gs.close()

@@ -75,6 +75,20 @@ class VsgDiagnostics(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class VsgMergePaths(C.Structure):
+    _fields_ = [
+        ("hub_stages", C.c_int64), ("hub_absorbed", C.c_int64),
+        ("hub_cuts", C.c_int64), ("hub_cuts_in_groups", C.c_int64), ("hub_parts_in_later_bucket", C.c_int64),
+        ("spine_side_cuts", C.c_int64),
+        ("hub_retries", C.c_int64), ("hub_reasons", C.c_int64 * 6),
+        ("hub_exclusion_reruns", C.c_int64), ("hub_off_reruns", C.c_int64),
+        ("group_halvings", C.c_int64), ("conservative_replays", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if k == "hub_reasons" else getattr(self, k)) for k, _ in self._fields_}
+
+
 class VsgMemoryStats(C.Structure):
     _fields_ = [
         ("bytes_in_use", C.c_int64), ("bytes_in_use_peak", C.c_int64), ("bytes_cached", C.c_int64),
@@ -106,7 +120,7 @@ EXPORTED_SYMBOLS = [
     "vsg_vectorize_id_image",
     "vsg_stream_create", "vsg_stream_destroy", "vsg_stream_process_frame", "vsg_stream_chunk_size",
     "vsg_stream_result_bytes", "vsg_stream_result_id_image", "vsg_stream_last_merge_stats",
-    "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_smoothed", "vsg_stream_export_halo",
+    "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_merge_paths", "vsg_stream_last_smoothed", "vsg_stream_export_halo",
     "vsg_stream_import_halo", "vsg_stream_expect_halo", "vsg_stream_restart",
     "vsg_chain_create", "vsg_chain_destroy", "vsg_chain_info", "vsg_chain_send_halo",
     "vsg_chain_recv_halo", "vsg_chain_exchange_halo",
@@ -119,7 +133,7 @@ EXPORTED_SYMBOLS = [
     "vsg_graph_region_sizes", "vsg_graph_index_image", "vsg_graph_get_regions",
     "vsg_graph_get_intervals", "vsg_graph_smoothed",
     "vsg_graph_spatial_buckets", "vsg_graph_temporal_buckets", "vsg_graph_node_roots",
-    "vsg_graph_merge_stats", "vsg_graph_timings", "vsg_graph_diagnostics",
+    "vsg_graph_merge_stats", "vsg_graph_timings", "vsg_graph_diagnostics", "vsg_graph_merge_paths",
     "vsg_debug_sort_pairs", "vsg_debug_sort_pairs_timed",
 ]
 
@@ -172,6 +186,7 @@ def lib():
     L.vsg_stream_last_merge_stats.argtypes = [vp, vp]
     L.vsg_stream_last_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_stream_last_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
+    L.vsg_stream_last_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
     L.vsg_stream_last_smoothed.argtypes = [vp, vp]
     L.vsg_stream_export_halo.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp]
     L.vsg_stream_import_halo.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -218,6 +233,7 @@ def lib():
     L.vsg_graph_merge_stats.argtypes = [vp, vp]
     L.vsg_graph_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_graph_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
+    L.vsg_graph_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
     _lib = L
     return L
 

@@ -116,6 +116,22 @@ struct vsg_graph {
   }
 };
 
+static void FillMergePaths(const vsg::MergePaths& mp, vsg_merge_paths* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->hub_stages = mp.hub_stages;
+  o->hub_absorbed = mp.hub_absorbed;
+  o->hub_cuts = mp.hub_cuts;
+  o->hub_cuts_in_groups = mp.hub_cuts_in_groups;
+  o->hub_parts_in_later_bucket = mp.hub_parts_in_later_bucket;
+  o->spine_side_cuts = mp.spine_side_cuts;
+  o->hub_retries = mp.hub_retries;
+  for (int q = 0; q < 6; ++q) o->hub_reasons[q] = mp.hub_reasons[q];
+  o->hub_exclusion_reruns = mp.hub_exclusion_reruns;
+  o->hub_off_reruns = mp.hub_off_reruns;
+  o->group_halvings = mp.group_halvings;
+  o->conservative_replays = mp.conservative_replays;
+}
+
 static void FillDiagnostics(const vsg::GraphTimings& gt, vsg_diagnostics* d) {
   std::memset(d, 0, sizeof(*d));
   d->segment_wall_ms = gt.segment_wall_ms;
@@ -319,6 +335,13 @@ int vsg_stream_last_diagnostics(const vsg_stream* s, vsg_diagnostics* d) {
   return Guard([&] {
     VSG_REQUIRE(s && d, VSG_ERR_INVALID, "null argument");
     FillDiagnostics(s->impl->last_graph_timings(), d);
+  });
+}
+
+int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out) {
+  return Guard([&] {
+    VSG_REQUIRE(s && out, VSG_ERR_INVALID, "null argument");
+    FillMergePaths(s->impl->last_graph_timings().paths, out);
   });
 }
 
@@ -1028,6 +1051,13 @@ int vsg_graph_diagnostics(const vsg_graph* g, vsg_diagnostics* d) {
   return Guard([&] {
     VSG_REQUIRE(g && d, VSG_ERR_INVALID, "null argument");
     FillDiagnostics(g->g->timings(), d);
+  });
+}
+
+int vsg_graph_merge_paths(const vsg_graph* g, vsg_merge_paths* out) {
+  return Guard([&] {
+    VSG_REQUIRE(g && out, VSG_ERR_INVALID, "null argument");
+    FillMergePaths(g->g->timings().paths, out);
   });
 }
 

@@ -531,6 +531,11 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
   S.hub_excl = hub_excl_.get();
   S.hub_max_splits = getenv("VSG_HUB_SPLITS") ? std::max(0, atoi(getenv("VSG_HUB_SPLITS"))) : kHubMaxSplits;
   S.hub_cut_min_work = getenv("VSG_CUT_MIN_WORK") ? atoi(getenv("VSG_CUT_MIN_WORK")) : 0;
+  // Test hooks of the cut paths: VSG_CUT_RATIO lowers the edges per violation from which a
+  // stage is cut (1 or 0: the stages of a small frame are cut too), VSG_HUB_CHECK=1 checks the list head
+  // and every cut position on the host.
+  S.hub_cut_ratio = getenv("VSG_CUT_RATIO") ? std::max(0, atoi(getenv("VSG_CUT_RATIO"))) : 1500;
+  S.hub_check = (getenv("VSG_HUB_CHECK") && atoi(getenv("VSG_HUB_CHECK")) != 0) ? 1 : 0;
   // (a stage takes its marks off again; an exception in the middle of one must not leave any behind)
   VSG_HIP(hipMemsetAsync(hub8_.get(), 0, N, stream_));
   // Sizes that follow the graph rather than the 1080p bench: the tree replay's scratch pool holds
@@ -1001,6 +1006,20 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
     const ThreadAllocCounters a1 = ThreadAllocSnapshot();
     const MailWaitCounters m1 = MailWaitSnapshot();
     timings_.stages = diag_stages;
+    MergePaths& mp = timings_.paths;
+    mp = MergePaths();
+    mp.hub_stages = diag_hub_stages;
+    mp.hub_absorbed = diag_hub_absorbed;
+    mp.hub_cuts = S.hub_splits;
+    mp.hub_cuts_in_groups = S.hub_cuts_in_groups;
+    mp.hub_parts_in_later_bucket = S.hub_parts_in_later_bucket;
+    mp.spine_side_cuts = S.spine_side_cuts;
+    mp.hub_retries = S.hub_retries;
+    for (int q = 0; q < 6; ++q) mp.hub_reasons[q] = S.hub_reasons[q];
+    mp.hub_exclusion_reruns = S.hub_exclusion_reruns;
+    mp.hub_off_reruns = S.hub_off_reruns;
+    mp.group_halvings = S.group_halvings;
+    mp.conservative_replays = S.conservative_replays;
     timings_.slab_growths = diag_slab_growths;
     timings_.slab_growth_ms = diag_slab_ms;
     timings_.spine_growths = diag_spine_growths;

@@ -13,6 +13,14 @@
 
 namespace vsg {
 
+// Which paths of the ordered merge ran in the last Segment call (vsg_merge_paths, include/vsg.h).
+struct MergePaths {
+  int64_t hub_stages = 0, hub_absorbed = 0;
+  int64_t hub_cuts = 0, hub_cuts_in_groups = 0, hub_parts_in_later_bucket = 0, spine_side_cuts = 0;
+  int64_t hub_retries = 0, hub_reasons[6] = {0, 0, 0, 0, 0, 0};
+  int64_t hub_exclusion_reruns = 0, hub_off_reruns = 0, group_halvings = 0, conservative_replays = 0;
+};
+
 struct GraphTimings {
   float edges_ms = 0, sort_ms = 0, merge_ms = 0, readout_ms = 0, host_post_ms = 0;
   int64_t edges_total = 0, edges_active = 0;
@@ -31,6 +39,7 @@ struct GraphTimings {
   double mail_wait_ms = 0, mail_wait_longest_ms = 0;
   int mail_mode = 0;
   double segment_wall_ms = 0, prepare_ms = 0, constrained_merge_ms = 0;
+  MergePaths paths;
 };
 
 class DenseGraphHip {

@@ -302,6 +302,17 @@ struct MergeScratch {
   int32_t* hub_excl;     // exclusion list of the stage and the edges that broke hub rules (kHubListInts)
   long long hub_retries; // such replays in this Segment call
   long long hub_reasons[6];   // ... by reason (kHubVioBroken .. kHubVioSplit)
+  // Which paths of RunBucketStage ran in this Segment call (vsg_merge_paths, include/vsg.h): host
+  // counts, kept without a sync or a launch of their own.
+  long long hub_cuts_in_groups;          // cuts of a stage over a group of buckets
+  long long hub_parts_in_later_bucket;   // parts of a cut group stage that start in a later bucket
+  long long spine_side_cuts;             // cuts at a kept edge of a tree replay's side cluster
+  long long hub_exclusion_reruns;        // reruns with the exclusion list (hub_attempt)
+  long long hub_off_reruns;              // reruns without hubs (hubs_off)
+  long long group_halvings;              // failed group stages run again as two halves
+  long long conservative_replays;        // failed stages replayed with inert_mode 0
+  long long hub_cut_ratio;               // a stage is cut only above this many edges per violation (VSG_CUT_RATIO)
+  int hub_check;                         // VSG_HUB_CHECK: host check of the list head and of every cut position
   int wave_debug;        // use the instrumented build of the wave worker (counters, self checks)
   int wave_dbg;          // debug hook (bit mask): 1 no chain, 4 no hot region, 8 one generic lane per round,
                          // 16 chain self check, 32 no jumping over pending lanes, 64 one chain lane per round

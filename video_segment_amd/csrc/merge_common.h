@@ -294,6 +294,16 @@ __device__ __forceinline__ void HubViolationAt(int32_t* list, int kind, int posi
   const int q = atomicAdd(&list[1 + kind], 1);
   if (q < kHubCutCap) list[4 + kHubExclCap + kind * kHubCutCap + q] = position;
 }
+// ... as a worker records it: the number of work edge p, or in a side cluster of a tree replay (T.side,
+// whose arrays are its own and come without s_seq) the kept position of the edge, kind 2.
+__device__ __forceinline__ void WorkerViolationAt(int32_t* list, const StageThr& T, const uint32_t* s_seq,
+                                                  const uint32_t* s_gpos, int p) {
+  if (T.side) {
+    HubViolationAt(list, 2, (int)s_gpos[p]);
+  } else if (s_seq) {
+    HubViolationAt(list, 1, (int)s_seq[p]);
+  }
+}
 __device__ __forceinline__ void HubExclude(int32_t* excl, uint8_t* flags, int r) {
   if (AtomicOrFlags(flags, r, kFlagHubBroken) & kFlagHubBroken) return;
   const int q = atomicAdd(&excl[0], 1);

@@ -1691,6 +1691,8 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
     w2.s_rb = o_rb;
     w2.s_gpos = o_gpos;
     w2.T.side = 1;
+    w2.s_seq = nullptr;   // (the side arrays are numbered their own way: a worker records the kept position)
+    VSG_REQUIRE(w2.T.hubs == 0, -4, "tree replay: a side cluster in a stage with hub regions");
     w2.work_cap = n_side / (w2.small_seg + 1) + 1;
     w2.work_list = (size_t)kWaveClasses * w2.work_cap <= ns ? seg_key : nullptr;
     w2.work_ctl = w2.work_list ? TakeZeroed(S, 2 * kWaveClasses) : nullptr;

@@ -787,7 +787,7 @@ __global__ __launch_bounds__(256) void k_merge_small(const int32_t* __restrict__
                                          : HubEdge(x, h.cons, h.flags, h.sz, T);
           if (act >= kHubViolation) {
             atomicOr(violation, act);
-            HubViolationAt(hub_excl, 1, (int)s_seq[p]);
+            WorkerViolationAt(hub_excl, T, s_seq, s_gpos, p);
             if (hub1) HubExclude(hub_excl, nodes.flags, r1);
             if (hub2) HubExclude(hub_excl, nodes.flags, r2);
           } else if (act == kHubKeep) {
@@ -796,7 +796,7 @@ __global__ __launch_bounds__(256) void k_merge_small(const int32_t* __restrict__
             const int xr = hub1 ? r2 : r1, hr = hub1 ? r1 : r2;
             nodes.parent[xr] = hr;
             if (x.flags & kFlagTentative) AtomicOrFlags(nodes.flags, hr, kFlagTentative);
-            hub_mark[s_seq[p]] = xr | (act == kHubAbsorbTest ? kHubTestBit : 0);
+            hub_mark[s_seq[p]] = xr | (act == kHubAbsorbTest ? kHubTestBit : 0);   // (T.hubs: s_seq is set, host-checked)
             if (act == kHubAbsorbTest) ++n_forced; else ++n_small;
           }
           continue;
@@ -810,12 +810,12 @@ __global__ __launch_bounds__(256) void k_merge_small(const int32_t* __restrict__
                                                : TentativeViolated(o1, o2, s2, s2);
           if (v) {
             atomicOr(violation, kVioCut);
-            HubViolationAt(hub_excl, 1, (int)s_seq[p]);
+            WorkerViolationAt(hub_excl, T, s_seq, s_gpos, p);
           }
         }
         if (stat == 4 && T.rle) {
           atomicOr(violation, kVioCut);
-          HubViolationAt(hub_excl, 1, (int)s_seq[p]);
+          WorkerViolationAt(hub_excl, T, s_seq, s_gpos, p);
         }
         n_forced += (stat == 1);
         n_regular += (stat == 2);
@@ -1267,7 +1267,20 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
       VSG_HIP(hipMemsetAsync(S.hub_excl, 0, 4 * sizeof(int32_t), s));
       S.hub_list_dirty = 0;
     } else {
-      VSG_HIP(hipMemsetAsync(S.hub_excl + 1, 0, 2 * sizeof(int32_t), s));   // (the exclusion list stays)
+      // (the exclusion list stays; the three counts of edges that broke a rule go, the kept positions too)
+      VSG_HIP(hipMemsetAsync(S.hub_excl + 1, 0, 3 * sizeof(int32_t), s));
+    }
+  }
+  if (S.hub_excl && S.hub_check) {   // (VSG_HUB_CHECK: what this run of the stage finds on the list is its own)
+    int head[4] = {0, 0, 0, 0};
+    VSG_HIP(hipMemcpyAsync(head, S.hub_excl, sizeof(head), hipMemcpyDeviceToHost, s));
+    VSG_HIP(hipStreamSynchronize(s));
+    for (int k = 1; k < 4; ++k) {
+      if (head[k] != 0) {
+        Throw(-4 /* VSG_ERR_INTERNAL */, "hub check: stage b=" + std::to_string(bucket) + " j0=" + std::to_string(j0) +
+                                             " n=" + std::to_string(n_b) + " starts with " + std::to_string(head[k]) +
+                                             " stale entries of kind " + std::to_string(k - 1) + " on the hub list");
+      }
     }
   }
   if (S.hub_attempt == 0 && S.hub_split_depth == 0) S.hub_splits_left = S.hub_max_splits;
@@ -1371,7 +1384,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   // them made its merge 1.5 s per chunk instead of 0.4.  (VSG_CUT_MIN_WORK: a floor on the replayed edges
   // as well -- measured at 2 K / 8 K / 32 K on the long 1080p noise stream: all worse than 0.)
   auto can_cut = [&](int work, long long violations) {
-    return work >= S.hub_cut_min_work && (long long)n_b > 1500ll * (violations + 1) && S.hub_splits_left > 0 &&
+    return work >= S.hub_cut_min_work && (long long)n_b > S.hub_cut_ratio * (violations + 1) && S.hub_splits_left > 0 &&
            S.bucket_base_host && S.bucket_prefix_host && S.list_off_host && S.list_slot_base_host;
   };
   auto retry_without_broken_hubs = [&](int violated, int work, bool list_complete, const uint32_t* work_gpos) -> bool {
@@ -1388,15 +1401,62 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     }
     if (can_cut(work, (long long)head[1] + (work_gpos ? head[2] + head[3] : 0))) {
       int at[3 * kHubCutCap];
+      int raw1[kHubCutCap];   // (VSG_HUB_CHECK: the work edges of kind 1, before k_hub_cut_gpos reads work_gpos at them)
+      if (S.hub_check && work_gpos) {
+        VSG_HIP(hipMemcpyAsync(raw1, S.hub_excl + 4 + kHubExclCap + kHubCutCap, sizeof(raw1), hipMemcpyDeviceToHost, s));
+        VSG_HIP(hipStreamSynchronize(s));
+        for (int i = 0; i < std::min(head[2], kHubCutCap); ++i) {
+          if (raw1[i] < 0 || raw1[i] >= work) {
+            Throw(-4 /* VSG_ERR_INTERNAL */, "hub check: stage b=" + std::to_string(bucket) + " j0=" + std::to_string(j0) +
+                                                 " n=" + std::to_string(n_b) + ": cut entry " + std::to_string(i) +
+                                                 " of kind 1 is work edge " + std::to_string(raw1[i]) + " of " +
+                                                 std::to_string(work));
+          }
+        }
+      }
       if (work_gpos) hipLaunchKernelGGL(k_hub_cut_gpos, dim3(1), dim3(64), 0, s, S.hub_excl, work_gpos);
       VSG_HIP(hipMemcpyAsync(at, S.hub_excl + 4 + kHubExclCap, sizeof(at), hipMemcpyDeviceToHost, s));
       VSG_HIP(hipStreamSynchronize(s));
-      for (int i = 0; i < std::min(head[1], kHubCutCap); ++i) cuts.push_back(at[i]);
+      // (VSG_HUB_CHECK: every position this run recorded lies in the stage -- a kept position of kind 1
+      // or 2 is checked against the stage's kept positions before it is located)
+      auto check_at = [&](int kind, int i, long long v, long long lo, long long hi) {
+        if (S.hub_check && (v < lo || v >= hi)) {
+          Throw(-4 /* VSG_ERR_INTERNAL */, "hub check: stage b=" + std::to_string(bucket) + " j0=" + std::to_string(j0) +
+                                               " n=" + std::to_string(n_b) + ": cut entry " + std::to_string(i) +
+                                               " of kind " + std::to_string(kind) + " is " + std::to_string(v) +
+                                               ", outside [" + std::to_string(lo) + ", " + std::to_string(hi) + ")");
+        }
+      };
+      auto in_stage = [&](int kind, int i, uint32_t gpos) {
+        if (!S.hub_check) return;
+        const long long g = SequencePosition(S, P, bucket, bucket_hi, gpos) - g_stage;
+        // (the position of a kept slot outside the stage's buckets can still land in [0, n_b): its list and
+        // bucket must be the stage's as well)
+        check_at(kind, i, g, 0, n_b);
+        const long long gg = g_stage + g;
+        const int b = BucketOfPosition(S, bucket, bucket_hi, gg);
+        const int32_t* row = S.bucket_base_host + (size_t)b * (P.num_lists + 1);
+        const int jb = (int)(gg - S.bucket_prefix_host[b]);
+        int l = 0;
+        while (l + 1 < P.num_lists && row[l + 1] <= jb) ++l;
+        if ((uint32_t)(S.list_slot_base_host[l] + S.list_off_host[(size_t)l * (kNumBuckets + 2) + b] + (jb - row[l])) != gpos) {
+          Throw(-4 /* VSG_ERR_INTERNAL */, "hub check: stage b=" + std::to_string(bucket) + " j0=" + std::to_string(j0) +
+                                               " n=" + std::to_string(n_b) + ": cut entry " + std::to_string(i) +
+                                               " of kind " + std::to_string(kind) + " is kept position " +
+                                               std::to_string(gpos) + ", not an edge of the stage");
+        }
+      };
+      for (int i = 0; i < std::min(head[1], kHubCutCap); ++i) {
+        check_at(0, i, at[i], 0, n_b);
+        cuts.push_back(at[i]);
+      }
       if (work_gpos) {
         for (int i = 0; i < std::min(head[2], kHubCutCap); ++i) {
+          in_stage(1, i, (uint32_t)at[kHubCutCap + i]);
           cuts.push_back((int)(SequencePosition(S, P, bucket, bucket_hi, (uint32_t)at[kHubCutCap + i]) - g_stage));
         }
         for (int i = 0; i < std::min(head[3], kHubCutCap); ++i) {   // (kept positions as they are)
+          in_stage(2, i, (uint32_t)at[2 * kHubCutCap + i]);
           cuts.push_back((int)(SequencePosition(S, P, bucket, bucket_hi, (uint32_t)at[2 * kHubCutCap + i]) - g_stage));
         }
       }
@@ -1423,6 +1483,9 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
       // run -- every part checks itself and is cut again if need be)
       S.hub_splits_left -= (int)cuts.size();
       S.hub_splits += (long long)cuts.size();
+      if (bucket_hi > bucket + 1) S.hub_cuts_in_groups += (long long)cuts.size();
+      // (the tree replay's side clusters: violated == 2 comes only from its branch for buckets 0 and 1 below)
+      if (violated == 2 && bucket < 2) S.spine_side_cuts += (long long)cuts.size();
       int replayed = 0;
       auto part = [&](int off, int n, bool plain) {
         if (n <= 0) return;
@@ -1431,6 +1494,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
         ++S.hub_split_depth;
         if (plain) ++S.hubs_off;
         const int b_at = BucketOfPosition(S, bucket, bucket_hi, g_stage + off);   // (a group: the part starts in a later bucket)
+        if (b_at > bucket) ++S.hub_parts_in_later_bucket;
         RunBucketStage(b_at, (int)(g_stage + off - S.bucket_prefix_host[b_at]), n, lists, bucket_base, list_slot_base,
                        kept_all, nodes, P, inert_mode, S, s, info ? &sub : nullptr);
         if (plain) --S.hubs_off;
@@ -1468,6 +1532,9 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     int& depth = (list_complete && S.hub_attempt + 1 < kHubMaxAttempts) ? S.hub_attempt : S.hubs_off;
     if (&depth == &S.hub_attempt) {
       hipLaunchKernelGGL(k_hub_exclude, dim3(16), dim3(256), 0, s, S.hub_excl, nodes);
+      ++S.hub_exclusion_reruns;
+    } else {
+      ++S.hub_off_reruns;
     }
     ++depth;
     RunBucketStage(bucket, j0, n_b, lists, bucket_base, list_slot_base, kept_all, nodes, P, inert_mode, S, s, info);
@@ -1532,6 +1599,9 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     }
   }
   const bool spine = !spine_in.segs.empty();
+  // (hubs and the tree replay exclude each other -- try_hubs needs !spine_possible --, so the side clusters
+  // of a tree replay never meet a hub: their workers have no work-edge numbers to record an absorption by)
+  VSG_REQUIRE(!(spine && hubs_used), -4, "merge stage: hub regions in a stage with a tree replay");
   // A stage that settles edges tentatively, replays run leaders only or relies on the spine
   // structure has to stay undoable.
   const bool optimistic = ((inert_mode == 2) && (n_ti > 0 || rle)) || spine || hubs_used;
@@ -1593,6 +1663,8 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     VSG_HIP(hipMemsetAsync(wa.hub_mark, 0xFF, (size_t)n_work * sizeof(int32_t), s));
   }
   auto general_workers = [&](const WorkerArgs& w, int small_threads, int grid, hipStream_t s) {
+    // (an edge on a hub records its absorption at hub_mark[s_seq[p]])
+    VSG_REQUIRE(!w.T.hubs || (w.s_seq && w.hub_mark), -4, "merge stage: hub workers without work-edge numbers");
     if (w.wave_min == w.small_seg) {
       hipLaunchKernelGGL(k_merge_small, dim3(Blocks(small_threads)), dim3(256), 0, s, w.num_segs,
                          w.seg_off, w.seg_cnt, w.s_ra, w.s_rb, w.s_gpos, w.nodes, w.kept_all, w.T,
@@ -1723,6 +1795,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
         // A group of buckets: its two halves (each optimistic again, split further if it fails
         // again) -- the conservative replay of everything the group holds would chain it into one
         // huge component, and bucket by bucket would cost a stage per bucket.
+        ++S.group_halvings;
         const int group_hi = S.group_hi;
         const int64_t g0 = (int64_t)S.bucket_prefix_host[bucket] + j0, g1 = g0 + n_b;
         const int mid = bucket + (bucket_hi - bucket) / 2;
@@ -1742,6 +1815,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
         if (info) info->replayed = replayed;
         return;
       }
+      ++S.conservative_replays;
       RunBucketStage(bucket, j0, n_b, lists, bucket_base, list_slot_base, kept_all, nodes, P, 0, S,
                      s, info);
       return;

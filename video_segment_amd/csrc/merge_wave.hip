@@ -136,7 +136,12 @@ __device__ __forceinline__ bool ReplayRounds(WaveTable& tab, float4* chain_buf, 
                                              const StageThr& T, int optimistic, int32_t* violation,
                                              unsigned long long* stats, int dbg_flags, int lane,
                                              bool valid, int sa, int sb, WaveCounters& C, uint32_t seq,
-                                             int32_t* hub_mark, int32_t* hub_excl) {
+                                             uint32_t gpos, int32_t* hub_mark, int32_t* hub_excl) {
+  // Where an edge broke a rule: its number among the stage's work edges (seq, kind 1), or in a side
+  // cluster of a tree replay -- whose edges are numbered their own way and come without s_seq -- its
+  // kept position (kind 2).  seq itself only ever indexes hub_mark, which is sized by the work edges.
+  const int vio_kind = T.side ? 2 : 1;
+  const int vio_at = T.side ? (int)gpos : (int)seq;
   auto Clock = []() -> unsigned long long { return kDbg ? __builtin_readcyclecounter() : 0ull; };
   bool pending = valid;
   int hot = -1;   // wave-uniform slot of the round's hot region
@@ -430,7 +435,7 @@ __device__ __forceinline__ bool ReplayRounds(WaveTable& tab, float4* chain_buf, 
                                        : HubEdge(x, h.cons, h.flags, h.sz, T);
       if (act >= kHubViolation) {
         atomicOr(violation, act);
-        HubViolationAt(hub_excl, 1, (int)seq);
+        HubViolationAt(hub_excl, vio_kind, vio_at);
         if (a_hub) HubExclude(hub_excl, nodes.flags, tab.key[sa]);
         if (b_hub) HubExclude(hub_excl, nodes.flags, tab.key[sb]);
       } else if (act == kHubKeep) {
@@ -494,12 +499,12 @@ __device__ __forceinline__ bool ReplayRounds(WaveTable& tab, float4* chain_buf, 
                                              : TentativeViolated(o1, o2, s2, s2);
         if (v) {
           atomicOr(violation, kVioCut);
-          HubViolationAt(hub_excl, 1, (int)seq);
+          HubViolationAt(hub_excl, vio_kind, vio_at);
         }
       }
       if (stat == 4 && T.rle) {
         atomicOr(violation, kVioCut);
-        HubViolationAt(hub_excl, 1, (int)seq);
+        HubViolationAt(hub_excl, vio_kind, vio_at);
       }
       C.n_forced += (stat == 1);
       C.n_regular += (stat == 2);
@@ -968,7 +973,7 @@ __global__ __launch_bounds__(128) void k_merge_wave(const int32_t* __restrict__ 
       cyc_load += bt1 - bt0b;
 
       const bool my_kept = ReplayRounds<kDbg>(tab, chain_buf, nodes, T, optimistic, violation, stats,
-                                              dbg_flags, lane, valid, sa, sb, C, seq, hub_mark, hub_excl);
+                                              dbg_flags, lane, valid, sa, sb, C, seq, gpos, hub_mark, hub_excl);
       WaveSync();
 
       if (valid && my_kept) kept_all[gpos] = 1;

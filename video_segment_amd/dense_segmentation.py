@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import VsgDiagnostics, VsgOptions, VsgTimings, check, lib
+from ._lib import VsgDiagnostics, VsgMergePaths, VsgOptions, VsgTimings, check, lib
 
 
 def default_options(**kw):
@@ -141,6 +141,13 @@ class DenseSegmentation:
         d = VsgDiagnostics()
         check(lib().vsg_stream_last_diagnostics(self.h, C.byref(d)))
         return d.as_dict()
+
+    def last_merge_paths(self):
+        """vsg_stream_last_merge_paths of the last segmented chunk (which paths of the ordered merge
+        ran), as a dict."""
+        m = VsgMergePaths()
+        check(lib().vsg_stream_last_merge_paths(self.h, C.byref(m)))
+        return m.as_dict()
 
     def last_smoothed(self):
         out = np.empty((self.H, self.W, 3), np.float32)
@@ -358,3 +365,9 @@ class DenseSegGraph:
         d = VsgDiagnostics()
         check(lib().vsg_graph_diagnostics(self.h, C.byref(d)))
         return d.as_dict()
+
+    def last_merge_paths(self):
+        """vsg_graph_merge_paths of the last segment() call, as a dict."""
+        m = VsgMergePaths()
+        check(lib().vsg_graph_merge_paths(self.h, C.byref(m)))
+        return m.as_dict()
