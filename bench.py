@@ -19,6 +19,12 @@ No data-path collective is needed; ranks only meet for the timing barrier and th
 two label planes + counters to the next rank with RCCL send/recv (the reference-exact multi-GPU
 mode; it cannot scale because of the chain).
 
+A plain run does only what the headline needs: it sets up, warms up, times the steps, writes
+--dump-outputs if asked and prints the line (roofline and stage figures from the timed steps
+themselves).  Everything else -- the CPU oracle baselines and their parity check, the
+PCIe-inclusive leg, the measured copy bandwidth of the roofline, the N > 1 chunk-chain leg and the
+information-only legs (other configs, other inputs, the streams sweep) -- runs only with --full.
+
 Prints ONE JSON line on rank 0.
 """
 import argparse
@@ -66,12 +72,17 @@ def parse():
     ap.add_argument("--streams", type=int, default=1,
                     help="concurrent independent 1080p streams per GPU (default 1 = the BASELINE "
                          "workload; >1 only quantifies how idle one stream leaves the GPU)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything beside it: CPU oracle "
+                         "baselines with their parity check, the PCIe-inclusive leg, the measured copy "
+                         "bandwidth, the N > 1 chunk-chain leg and the information-only legs")
+    ap.add_argument("--no-cpu-baseline", action="store_true",
+                    help="with --full: skip the CPU oracle baselines")
     ap.add_argument("--host-inputs", action="store_true",
                     help="frames and flow are handed over as host buffers (the H2D copies are "
                          "inside the timed region); reported as config.inputs, never the default")
     ap.add_argument("--no-pcie-leg", action="store_true",
-                    help="skip the short extra leg that measures the PCIe-inclusive rate")
+                    help="with --full: skip the short extra leg that measures the PCIe-inclusive rate")
     ap.add_argument("--dist-backend", default="nccl",
                     help="torch.distributed backend (nccl = RCCL; gloo only to exercise the N>1 "
                          "control flow on a box with fewer GPUs than ranks, with --share-gpu)")
@@ -79,13 +90,15 @@ def parse():
                     help="testing only: all ranks use device 0")
     ap.add_argument("--cpu-frames", type=int, default=20)
     ap.add_argument("--pipelined-leg", action="store_true",
-                    help="also measure two chunk engines on one video (video_segment_amd/pipelined.py)")
+                    help="with --full: also measure two chunk engines on one video "
+                         "(video_segment_amd/pipelined.py)")
     ap.add_argument("--no-chain-leg", action="store_true",
-                    help="N > 1, --mode streams: skip the short chunk-chain leg after the replicas leg")
+                    help="with --full, N > 1, --mode streams: skip the short chunk-chain leg after the "
+                         "replicas leg")
     ap.add_argument("--chain-leg-timeout", type=int, default=240)
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the information-only legs after the timed region (other configs, other "
-                         "inputs, several streams per GPU)")
+                    help="with --full: skip the information-only legs after the timed region (other "
+                         "configs, other inputs, several streams per GPU)")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="after the timed steps, write what the last timed step returned (rank 0, "
                          "stream 0) as DIR/<name>.npy, see dump_outputs()")
@@ -94,6 +107,8 @@ def parse():
         ap.error("--steps must be at least 1 and --warmup at least 0")
     if args.dump_outputs is not None and args.mode != "streams":
         ap.error("--dump-outputs needs --mode streams")
+    if args.pipelined_leg and not args.full:
+        ap.error("--pipelined-leg is one of the information-only legs: it needs --full")
     return args
 
 
@@ -660,8 +675,8 @@ def extra_measurements(vsg, args, dev, device_index, headline_fps, out):
         env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
         for k_ in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
             env.pop(k_, None)
-        cmd = [sys.executable] + extra(port) + ["--steps", "2", "--warmup", "1", "--no-extras",
-                                               "--no-cpu-baseline", "--no-pcie-leg", "--width", str(W),
+        # (a plain run: the headline only, without --full)
+        cmd = [sys.executable] + extra(port) + ["--steps", "2", "--warmup", "1", "--width", str(W),
                                                "--height", str(H), "--chunk", str(chunk)]
         p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=env, cwd=ROOT)
         if p.returncode != 0:
@@ -790,10 +805,10 @@ def main():
                   "device_bytes_per_stream": r["device_bytes_per_stream"], "ranks": ranks_info,
                   "parallelism": "%d independent 1080p stream(s) per GPU x %d GPU(s)" % (S, world),
                   "dump_outputs": r["after_timed"]}
-        # PCIe-inclusive leg (rank 0, one stream, not `value`): the same steady-state chunks with
-        # frames and flow handed over as host buffers, so that the H2D copies are timed as well.
+        # PCIe-inclusive leg (--full, rank 0, one stream, not `value`): the same steady-state chunks
+        # with frames and flow handed over as host buffers, so that the H2D copies are timed as well.
         result["pcie"] = None
-        if rank == 0 and not args.host_inputs and not args.no_pcie_leg and S == 1:
+        if args.full and rank == 0 and not args.host_inputs and not args.no_pcie_leg and S == 1:
             st_ = vsg.DenseSegmentation(W, H, vsg.default_options(chunk_size=chunk, device=local_rank),
                                         has_flow=True)
             need = min(chunk + (chunk - 1) * 2, n_frames)
@@ -817,14 +832,14 @@ def main():
                                           "pageable host memory inside the timed region"}
             st_.close()
         del frames
-        # The other partition of SURVEY 8(e), on every N > 1 run: ONE video sharded chunk-wise over
-        # the ranks, the label-plane halo handed from rank to rank through the library's own
-        # ncclSend / ncclRecv (dense_segmentation.cpp:281-331 is the hand-off it replaces).  Two
-        # chunks per rank after one warm-up chunk per rank; information beside `value`, which stays
-        # the replicas number.
+        # The other partition of SURVEY 8(e), on every N > 1 run with --full: ONE video sharded
+        # chunk-wise over the ranks, the label-plane halo handed from rank to rank through the
+        # library's own ncclSend / ncclRecv (dense_segmentation.cpp:281-331 is the hand-off it
+        # replaces).  Two chunks per rank after one warm-up chunk per rank; information beside
+        # `value`, which stays the replicas number.
         result["chain"] = None
         chain_timed_out = False
-        if world > 1 and not args.no_chain_leg:
+        if args.full and world > 1 and not args.no_chain_leg:
             import copy
             from video_segment_amd.multi_gpu import run_chain_bench
             a2 = copy.copy(args)
@@ -911,7 +926,7 @@ def main():
         alg_by_kernel = {
             "wave": WAVE_BYTES_PER_EDGE * acc["wave_edges"] / max(acc["wave_launches"], 1),
             "spine": SPINE_BYTES_PER_EDGE * acc["spine_edges"] / max(acc["spine_launches"], 1)}
-        copy_gbps = measured_copy_bandwidth(dev) if args.mode == "streams" else None
+        copy_gbps = measured_copy_bandwidth(dev) if args.full and args.mode == "streams" else None
         out = {
             "metric": "over-segmented frames/sec at 1080p",
             "value": fps,
@@ -951,7 +966,7 @@ def main():
                 else None,
                 "peak_measured": copy_gbps,
                 "peak_measured_note": "device-to-device copy of 1 GiB on this box, bytes read + written per "
-                                      "second (SURVEY 8(d))",
+                                      "second (SURVEY 8(d)); measured with --full",
                 "frac_of_measured": (achieved / copy_gbps) if copy_gbps else None,
                 "kernels": kernel_table(W, H, chunk),
                 "launches": acc[dom[0] + "_launches"],
@@ -977,13 +992,15 @@ def main():
             out["config"]["handoff"] = result["handoff"]
         if result.get("dump_outputs"):
             out["dump_outputs"] = result["dump_outputs"]
-        if not args.no_cpu_baseline and world == 1:   # (rank 0 at N = 1 only: the other ranks would wait)
+        # --full only from here on: what the headline does not need (rank 0 at N = 1 only: the
+        # other ranks would wait)
+        if args.full and not args.no_cpu_baseline and world == 1:
             out["cpu_baseline"], threaded, out["parity_checked"] = cpu_baseline(
                 W, H, chunk, args.cpu_frames, local_rank)
             if threaded is not None:
                 out["cpu_baseline_threaded"] = threaded
             assert out["parity_checked"], "HIP output differs from the oracle on the bench workload"
-        if world == 1 and args.mode == "streams" and not args.no_extras and not args.host_inputs \
+        if args.full and world == 1 and args.mode == "streams" and not args.no_extras and not args.host_inputs \
                 and args.streams == 1 and (W, H) == (1920, 1080):
             torch.cuda.empty_cache()
             extras = {}

@@ -33,16 +33,52 @@ def check(out, n_gpus, steps, warmup):
     assert abs(r["frac"] - r["achieved"] / r["peak"]) < 1e-12
 
 
+# what only `bench.py --full` measures or checks; a plain run leaves these keys out
+FULL_ONLY = ["cpu_baseline", "cpu_baseline_threaded", "parity_checked", "pcie_inclusive", "configs",
+             "workloads", "streams_sweep", "pipelined"]
+
+
+def test_full_is_off_by_default(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "3", "--warmup", "1"])
+    assert bench.parse().full is False
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--pipelined-leg"])
+    assert bench.parse().full is True
+    # the pipelined leg is one of the information-only legs: without --full it would silently not run
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--pipelined-leg"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+@pytest.mark.gpu
+def test_plain_line_is_the_headline_only():
+    """A plain run sets up, warms up, times the steps and prints the line: the contract keys and
+    what the timed steps themselves give (roofline, stages), none of the --full legs."""
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2",
+                        "--warmup", "1", "--width", "320", "--height", "240"],
+                       capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    out = last_json_line(p.stdout)
+    check(out, 1, 2, 1)
+    assert out["value"] * out["ms_per_step"] * out["steps"] / 1e3 == pytest.approx(2 * 19)
+    assert out["stage_ms_per_step"]["merge"] > 0 and out["roofline"]["achieved"] >= 0
+    for k in FULL_ONLY:
+        assert k not in out, k
+    assert out["roofline"]["peak_measured"] is None and out["chain"] is None
+
+
 @pytest.mark.gpu
 def test_single_gpu_line_and_cpu_baseline():
-    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1",
-                        "--width", "320", "--height", "240", "--cpu-frames", "20"],
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2",
+                        "--warmup", "1", "--width", "320", "--height", "240", "--cpu-frames", "20"],
                        capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert p.returncode == 0, p.stderr[-2000:]
     out = last_json_line(p.stdout)
     check(out, 1, 2, 1)
     c = out["cpu_baseline"]
     assert c["kind"] == "port" and c["cores"] == 1 and c["value"] > 0 and "sample" in c
+    assert out["parity_checked"] is True and out["pcie_inclusive"]["value"] > 0
+    assert out["roofline"]["peak_measured"] > 0
 
 
 @pytest.mark.gpu
@@ -91,7 +127,7 @@ def test_two_ranks_control_flow(mode, port):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
            "--master-addr", "127.0.0.1", "--master-port", port, os.path.join(ROOT, "bench.py"),
            "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "256", "--height", "144",
-           "--mode", mode, "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline"]
+           "--mode", mode, "--dist-backend", "gloo", "--share-gpu", "--no-cpu-baseline", "--full"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=360, cwd=ROOT, env=env)
     assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
     out = last_json_line(p.stdout)
@@ -116,11 +152,31 @@ def test_two_ranks_control_flow(mode, port):
         assert "expected" in ch and ch["vs_one_stream"] > 0
 
 
+@pytest.mark.gpu
+def test_two_ranks_plain_line():
+    """A plain N > 1 run: the replicas leg and what every rank measured, no chunk-chain leg."""
+    env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
+           "--master-addr", "127.0.0.1", "--master-port", "29613", os.path.join(ROOT, "bench.py"),
+           "--gpus", "2", "--steps", "2", "--warmup", "1", "--width", "256", "--height", "144",
+           "--dist-backend", "gloo", "--share-gpu"]
+    p = subprocess.run(cmd, capture_output=True, text=True, timeout=360, cwd=ROOT, env=env)
+    assert p.returncode == 0, (p.stdout + p.stderr)[-3000:]
+    out = last_json_line(p.stdout)
+    check(out, 2, 2, 1)
+    assert abs(out["value"] * out["ms_per_step"] * out["steps"] / 1e3 - 76) < 1e-6
+    assert out["ranks"]["world_size"] == 2 and out["ranks"]["allreduce_sum_of_ones"] == 2.0
+    assert out["chain"] is None
+    for k in FULL_ONLY:
+        assert k not in out, k
+
+
 def test_committed_round_line_carries_every_key():
-    """The default `python bench.py` line of the round (profiles/, produced on an MI355X by
-    tools/measure_round.sh): the contract keys plus what the headline depends on -- the other
-    single-GPU configs, the other inputs (each with its own oracle check), the streams sweep, the
-    memory a stream holds -- and counters that belong to the kernel sources of the same commit."""
+    """The full bench line of the round (what `bench.py --full` prints, a plain run before that option
+    existed; profiles/, produced on an MI355X by tools/measure_round.sh): the contract keys plus what
+    the headline depends on -- the other single-GPU configs, the other inputs (each with its own
+    oracle check), the streams sweep, the memory a stream holds -- and counters that belong to the
+    kernel sources of the same commit."""
     import glob
     paths = sorted(glob.glob(os.path.join(ROOT, "profiles", "r6_*_bench_1080p.json")))
     assert paths, "no round-6 bench line under profiles/"
