@@ -1,0 +1,115 @@
+/*
+ * vsg_render.h -- C ABI of the segmentation renderer (libvsg_render.so).
+ *
+ * Mirrors the reference's SegmentationRenderUnit (segmentation/segmentation_unit.cpp:478-655,
+ * segment_util/segmentation_render.{h,cpp}) and SegmentationDescToIdImage
+ * (segment_util/segmentation_util.cpp:741-770) on an MI355X: a serialized SegmentationDesc goes in,
+ * a BGR24 picture of its regions at a hierarchy level (or an int32 image of their ids at a level)
+ * comes out, in host or in device memory.  The library is independent of libvsg_hip.so; it reads the
+ * few proto fields it needs (region.id, region.raster.scan_inter, hierarchy[l].region{id,parent_id},
+ * frame_width, frame_height) with a reader of its own.
+ *
+ * Conventions are those of vsg.h: every function returns VSG_OK (0) or a negative status,
+ * vsg_render_last_error() is a thread-local message of the last failure, a handle is
+ * thread-compatible and owns one HIP stream, and there is NO CPU fallback: without a usable HIP
+ * device vsg_render_create fails with VSG_ERR_DEVICE.  Every call returns after its work on the
+ * handle's stream has finished, so an output in device memory is complete on return; inputs in
+ * device memory have to be complete when the call is made.
+ *
+ * Not offered (the reference has them): draw_shape_descriptors, and the two cv::putText overlays
+ * ("Frame #...", "Change to chunk id ...") -- the Hershey glyphs are OpenCV's data.  A rendered
+ * frame therefore equals the reference's up to those text pixels.
+ *
+ * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
+ * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
+ * region order).  Intervals outside the frame are refused with VSG_ERR_INVALID.
+ */
+#ifndef VSG_RENDER_H_
+#define VSG_RENDER_H_
+
+#include <stddef.h>
+#include <stdint.h>
+
+#ifdef __cplusplus
+extern "C" {
+#endif
+
+#ifndef VSG_OK
+#define VSG_OK 0
+#define VSG_ERR_INVALID -1
+#define VSG_ERR_DEVICE -2
+#define VSG_ERR_STATE -3
+#define VSG_ERR_INTERNAL -4
+#define VSG_MEM_HOST 0
+#define VSG_MEM_DEVICE 1
+#endif
+
+typedef struct vsg_render vsg_render;
+
+/* SegmentationRenderUnitOptions (segmentation_unit.h) without the stream names. */
+typedef struct vsg_render_options {
+  float blend_alpha;       /* 0.5f; weight of the render over the source frame                    */
+  float hierarchy_level;   /* 0; a value with a fractional part is a fraction of the hierarchy's
+                            * height, resolved on the first frame (segmentation_unit.cpp:567-580)  */
+  int highlight_edges;     /* 1; region boundaries in black                                       */
+  int concat_with_source;  /* 0; 1 = output of 2*H rows, render on top, source frame below        */
+  int has_video;           /* 1; 0 = no source frame: blend_alpha is forced to 1                  */
+  int device;              /* -1 = the caller's current HIP device                                */
+} vsg_render_options;
+
+/* What the last vsg_render_frame / vsg_render_id_image call of a handle did.  Device times are HIP
+ * events on the handle's stream around the kernels; host times are wall clock. */
+typedef struct vsg_render_stats {
+  double decode_ms;            /* proto decode, hierarchy lookup, colour table, interval list (host) */
+  double upload_ms;            /* interval list to the device, frame to the device when it is host
+                                * memory (host wall clock until the copies are enqueued)              */
+  float clear_us, fill_us, compose_us;   /* plane clear, k_render_fill, k_render_compose            */
+  int launches;                /* kernels + memsets + copies enqueued by the call                   */
+  int64_t intervals;           /* scan intervals painted                                            */
+  int64_t distinct_ids;        /* distinct mapped ids of the frame                                  */
+  int64_t device_allocations;  /* hipMalloc / hipHostMalloc calls of the handle since creation      */
+} vsg_render_stats;
+
+const char* vsg_render_last_error(void);
+void vsg_render_default_options(vsg_render_options* o);
+
+/* concat_with_source without has_video is VSG_ERR_INVALID (the reference CHECK-fails,
+ * segmentation_unit.cpp:613). */
+int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_render** h);
+void vsg_render_destroy(vsg_render* h);
+
+/* Renders one frame.  seg: serialized SegmentationDesc (host).  bgr: the BGR24 source frame of
+ * `stride` bytes per row in mem_in memory (ignored without has_video, required with it).  out: H
+ * (or 2*H) rows of out_stride bytes in mem_out memory; out_stride 0 = vsg_render_default_stride.
+ * Only the first 3*W bytes of each output row are written.
+ * The first frame's desc is kept as the hierarchy and resolves the level; every later desc that
+ * carries a hierarchy replaces the kept one (segmentation_unit.cpp:567-591). */
+int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const uint8_t* bgr,
+                     size_t stride, int mem_in, uint8_t* out, size_t out_stride, int mem_out);
+
+/* SegmentationDescToIdImage(level, ...): W*H int32, the id at `level` of the region covering each
+ * pixel, -1 where none does.  The hierarchy is the desc's own when it carries one (it then also
+ * replaces the handle's kept one), else the kept one.  level < 0, or level > 0 and not below the
+ * hierarchy's height, is VSG_ERR_INVALID (the reference's clamp at segmentation_util.cpp:748
+ * would index past the last level there). */
+int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
+                        int32_t* out_int32, int mem_out);
+
+/* The level the handle resolved on its first rendered frame (-1 for an over-segmentation without
+ * hierarchy, which renders as level 0); VSG_ERR_STATE before the first frame. */
+int vsg_render_level(vsg_render* h, int* level);
+
+/* 3*W rounded up to a multiple of 4 (segmentation_unit.cpp:526-529). */
+size_t vsg_render_default_stride(int width);
+
+int vsg_render_last_stats(vsg_render* h, vsg_render_stats* s);
+
+/* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
+ * restated, so that process-global state stays untouched.  Host only; needs no device. */
+void vsg_render_color(int region_id, uint8_t c[3]);
+
+#ifdef __cplusplus
+}
+#endif
+
+#endif /* VSG_RENDER_H_ */

@@ -1,0 +1,112 @@
+"""Device time of the renderer's two kernels next to a plain device-to-device copy.
+
+    python tools/render_probe.py [--reps 60] [--warmup 10] [--out profiles/render_kernels.json]
+
+For 1920x1080 and 3840x2160, on a checker-like (synth.bench_frame) and a many-region
+(synth.noise_frame) chunk result of the dense over-segmentation: k_render_fill and k_render_compose
+are timed with HIP events on the handle's stream (vsg_render_last_stats), frame and output in device
+memory, default options (edges, blend 0.5).  In the same run a device-to-device copy of 7 bytes per
+pixel is timed with torch events: it reads and writes as many bytes as the two kernels have to move
+(plane write 4 + plane read 4 + frame read 3 + frame write 3 = 14 per pixel).  Medians over the
+repetitions after a warm-up, with the 10th and 90th percentile as the spread.
+"""
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+
+def pct(values):
+    a = np.asarray(values, np.float64)
+    return {"median": float(np.median(a)), "p10": float(np.percentile(a, 10)), "p90": float(np.percentile(a, 90))}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=60)
+    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_kernels.json"))
+    ap.add_argument("--sizes", default="1920x1080,3840x2160")
+    args = ap.parse_args()
+
+    import torch
+    import synth
+    import video_segment_amd as vsg
+    from video_segment_amd import _lib
+    if _lib.lib().vsg_device_count() <= 0:
+        sys.exit("render_probe needs a HIP device: a time from anywhere else says nothing")
+    dev = torch.device("cuda", 0)
+    result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        px = W * H
+        # the copy moving the same bytes: 7 * px read + 7 * px written
+        src = torch.empty(7 * px, dtype=torch.uint8, device=dev)
+        dst = torch.empty_like(src)
+        for kind, frame_fn in (("checker", synth.bench_frame), ("noise", synth.noise_frame)):
+            N = 3
+            fl = torch.from_numpy(synth.const_flow(W, H)).to(dev)
+            d = vsg.DenseSegmentation(W, H, vsg.default_options(chunk_size=20), has_flow=True)
+            frames, segs = [], []
+            for k in range(N):
+                frames.append(torch.from_numpy(frame_fn(W, H, k)).to(dev))
+                n = d.process_frame(frames[k], fl if k > 0 else None, flush=(k == N - 1))
+                segs += [d.result_bytes(i) for i in range(n)]
+            d.close()
+            seg, frame = segs[1], frames[1]
+            r = vsg.SegmentationRenderer(W, H)
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            rows = {k: [] for k in ("clear_us", "fill_us", "compose_us", "decode_ms", "upload_ms", "call_ms", "copy_us")}
+            for it in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                r.render(seg, frame, out=out)
+                call_ms = (time.perf_counter() - t0) * 1e3
+                st = r.last_stats()
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                dst.copy_(src)
+                e1.record()
+                e1.synchronize()
+                if it >= args.warmup:
+                    for k in ("clear_us", "fill_us", "compose_us", "decode_ms", "upload_ms"):
+                        rows[k].append(st[k])
+                    rows["call_ms"].append(call_ms)
+                    rows["copy_us"].append(e0.elapsed_time(e1) * 1e3)
+            st = r.last_stats()
+            r.close()
+            med = {k: pct(v) for k, v in rows.items()}
+            fill_bytes = 4 * px + 16 * st["intervals"]          # plane write + interval list read
+            compose_bytes = (4 + 3 + 3) * px                    # plane read + frame read + frame write
+            kernels_us = med["fill_us"]["median"] + med["compose_us"]["median"]
+            case = {
+                "size": size, "input": kind, "intervals": st["intervals"], "distinct_ids": st["distinct_ids"],
+                "launches_per_frame": st["launches"],
+                "fill": dict(med["fill_us"], unit="us", bytes_per_pixel=fill_bytes / px,
+                             GBps=fill_bytes / med["fill_us"]["median"] / 1e3),
+                "compose": dict(med["compose_us"], unit="us", bytes_per_pixel=compose_bytes / px,
+                                GBps=compose_bytes / med["compose_us"]["median"] / 1e3),
+                "clear": dict(med["clear_us"], unit="us"),
+                "copy_same_bytes": dict(med["copy_us"], unit="us", bytes_per_pixel=14.0,
+                                        GBps=14 * px / med["copy_us"]["median"] / 1e3),
+                "kernels_over_copy": kernels_us / med["copy_us"]["median"],
+                "host_decode_colour_table_ms": med["decode_ms"],
+                "host_upload_ms": med["upload_ms"],
+                "call_wall_ms": med["call_ms"],
+            }
+            result["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()

@@ -6,6 +6,10 @@
 //   seg_tree_synth --width 64 --height 48 --frames 45 --flow --input probe [--nouse_pipeline]
 // prints the number of over-segmented frames, Region2D counts and the FNV-1a-32 hash of all region
 // id images (the quantity pinned in SURVEY.md App. B), then __SEGMENTATION_FINISHED__.
+//
+//   --render_level <float> [--render_concat] [--render_blend_alpha <float>]
+// puts a SegmentationRenderUnit (seg_tree.cpp --render_and_save) behind the segmentation and prints a
+// second line, render_frames=N render_fnv1a32=<FNV-1a-32 of the rendered frames' pixel bytes>.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -16,6 +20,7 @@
 #include "flow_reader.h"
 #include "raw_video_reader.h"
 #include "segmentation_io.h"
+#include "segmentation_render_unit.h"
 #include "segmentation_unit.h"
 #include "video_pipeline.h"
 
@@ -153,6 +158,33 @@ class HashSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// Hashes the pixel bytes (3 * width per row, no padding) of every "RenderedRegionStream" frame.
+class RenderHashSinkUnit : public VideoUnit {
+ public:
+  bool OpenStreams(StreamSet* set) override {
+    idx_ = FindStreamIdx("RenderedRegionStream", set);
+    return idx_ >= 0;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const VideoFrame& f = input->at(idx_)->As<VideoFrame>();
+    for (int y = 0; y < f.height(); ++y) {
+      const uint8_t* row = f.data() + (size_t)y * f.width_step();
+      for (int x = 0; x < f.width() * 3; ++x) {
+        hash_ ^= row[x];
+        hash_ *= 16777619u;
+      }
+    }
+    ++frames_;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  int frames() const { return frames_; }
+
+ private:
+  int idx_ = -1, frames_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -214,6 +246,10 @@ struct Flags {
   std::string flow_output_file;    // DenseFlowOptions::flow_output_file: explicit path for --save_flow
   double pipeline_max_rate = 0;    // seg_tree.cpp:349 uses 20 frames/s for its root
   bool two_stage_oversegment = false;
+  // SegmentationRenderUnit behind the segmentation (seg_tree.cpp --render_and_save); < 0: no render
+  double render_level = -1;
+  bool render_concat = false;
+  double render_blend_alpha = 0.5;
 };
 
 bool ParseFlags(int argc, char** argv, Flags* f) {
@@ -234,7 +270,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
       has_v = true;
     }
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
-                                   "two_stage_oversegment", "region_segmentation"};
+                                   "two_stage_oversegment", "region_segmentation", "render_concat"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -260,6 +296,9 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "save_flow") f->save_flow = bv;
     else if (a == "two_stage_oversegment") f->two_stage_oversegment = bv;
     else if (a == "region_segmentation") f->region_segmentation = bv;
+    else if (a == "render_concat") f->render_concat = bv;
+    else if (a == "render_level") f->render_level = atof(v.c_str());
+    else if (a == "render_blend_alpha") f->render_blend_alpha = atof(v.c_str());
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -379,6 +418,20 @@ int main(int argc, char** argv) {
     if (FLAGS.use_pipeline) cut();
   }
 
+  std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
+  RenderHashSinkUnit render_sink;
+  if (FLAGS.render_level >= 0) {
+    SegmentationRenderUnitOptions render_options;
+    render_options.hierarchy_level = (float)FLAGS.render_level;
+    render_options.concat_with_source = FLAGS.render_concat;
+    render_options.blend_alpha = (float)FLAGS.render_blend_alpha;
+    render_options.device = FLAGS.device;
+    render_unit.reset(new SegmentationRenderUnit(render_options));
+    render_unit->AttachTo(input);
+    render_sink.AttachTo(render_unit.get());
+    input = &render_sink;
+  }
+
   HashSinkUnit sink;
   sink.AttachTo(input);
   input = &sink;
@@ -414,6 +467,10 @@ int main(int argc, char** argv) {
               "seconds=%.3f fps=%.2f pipeline=%d hierarchy_levels=%d\n",
               sink.frames(), sink.first_regions(), sink.total_regions(), sink.hash(), sink.bytes(),
               dt, sink.frames() / dt, FLAGS.use_pipeline ? 1 : 0, sink.first_levels());
+  if (render_unit) {
+    std::printf("render_frames=%d render_fnv1a32=%08x render_level=%d\n", render_sink.frames(), render_sink.hash(),
+                render_unit->hierarchy_level());
+  }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;
 }

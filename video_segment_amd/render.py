@@ -1,0 +1,230 @@
+"""Python host layer of the segmentation renderer (C ABI: include/vsg_render.h, libvsg_render.so).
+
+``SegmentationRenderer`` mirrors the reference's SegmentationRenderUnit (segmentation_unit.cpp:478-655)
+without its stream plumbing: serialized ``SegmentationDesc`` bytes and, optionally, the BGR24 source
+frame go in, the rendered frame (or the id image of a hierarchy level) comes out.  Frames and outputs
+may be numpy arrays (host memory) or torch CUDA tensors (device memory); the output lives where the
+frame does, or where ``out=`` says.  All per-pixel work happens in the HIP library; there is no
+Python or CPU fallback.
+"""
+import ctypes as C
+import os
+import subprocess
+
+import numpy as np
+
+from . import _lib
+from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError
+
+_HERE = os.path.dirname(os.path.abspath(__file__))
+RENDER_DIR = os.path.join(_HERE, "render")
+LIB_PATH = os.path.join(_HERE, "lib", "libvsg_render.so")
+
+
+class VsgRenderOptions(C.Structure):
+    _fields_ = [
+        ("blend_alpha", C.c_float),
+        ("hierarchy_level", C.c_float),
+        ("highlight_edges", C.c_int),
+        ("concat_with_source", C.c_int),
+        ("has_video", C.c_int),
+        ("device", C.c_int),
+    ]
+
+
+class VsgRenderStats(C.Structure):
+    _fields_ = [
+        ("decode_ms", C.c_double), ("upload_ms", C.c_double),
+        ("clear_us", C.c_float), ("fill_us", C.c_float), ("compose_us", C.c_float),
+        ("launches", C.c_int),
+        ("intervals", C.c_int64), ("distinct_ids", C.c_int64), ("device_allocations", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+# Every symbol include/vsg_render.h declares.
+EXPORTED_SYMBOLS = [
+    "vsg_render_last_error", "vsg_render_default_options", "vsg_render_create", "vsg_render_destroy",
+    "vsg_render_frame", "vsg_render_id_image", "vsg_render_level", "vsg_render_default_stride",
+    "vsg_render_last_stats", "vsg_render_color",
+]
+
+
+def build(force=False):
+    """Compiles libvsg_render.so in-tree (hipcc --offload-arch=gfx950); make decides what is stale."""
+    subprocess.check_call(["make", "-C", RENDER_DIR, "-j8", "-s"] + (["-B"] if force else []))
+    return LIB_PATH
+
+
+_handle = None
+
+
+def lib():
+    global _handle
+    if _handle is not None:
+        return _handle
+    if not os.path.exists(LIB_PATH):
+        raise RuntimeError("libvsg_render.so is missing (%s): build the HIP extension first; there is no "
+                           "fallback path" % LIB_PATH)
+    try:   # one HIP runtime per process: bind to the one torch loaded (see _lib.lib)
+        import torch  # noqa: F401
+    except ImportError:
+        pass
+    L = C.CDLL(LIB_PATH)
+    vp = C.c_void_p
+    L.vsg_render_last_error.restype = C.c_char_p
+    L.vsg_render_default_options.argtypes = [C.POINTER(VsgRenderOptions)]
+    L.vsg_render_default_options.restype = None
+    L.vsg_render_create.argtypes = [C.POINTER(VsgRenderOptions), C.c_int, C.c_int, C.POINTER(vp)]
+    L.vsg_render_destroy.argtypes = [vp]
+    L.vsg_render_destroy.restype = None
+    L.vsg_render_frame.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int]
+    L.vsg_render_id_image.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_int]
+    L.vsg_render_level.argtypes = [vp, C.POINTER(C.c_int)]
+    L.vsg_render_default_stride.argtypes = [C.c_int]
+    L.vsg_render_default_stride.restype = C.c_size_t
+    L.vsg_render_last_stats.argtypes = [vp, C.POINTER(VsgRenderStats)]
+    L.vsg_render_color.argtypes = [C.c_int, C.POINTER(C.c_uint8 * 3)]
+    L.vsg_render_color.restype = None
+    _handle = L
+    return L
+
+
+def check(rc):
+    if rc != VSG_OK:
+        raise VsgError("vsg_render error %d: %s" % (rc, lib().vsg_render_last_error().decode()), rc)
+
+
+def default_render_options(**kw):
+    o = VsgRenderOptions()
+    lib().vsg_render_default_options(C.byref(o))
+    for k, v in kw.items():
+        if not hasattr(o, k):
+            raise TypeError("unknown render option %r" % k)
+        setattr(o, k, v)
+    return o
+
+
+def render_color(region_id):
+    """(c0, c1, c2) = srand(region_id); rand() % 255 three times, the colour the reference paints a
+    region id with (bytes 0, 1, 2 of the pixel).  Host only."""
+    c = (C.c_uint8 * 3)()
+    # srand takes the id as unsigned; any Python int is reduced to the 32 bits the C int carries
+    rid = ((int(region_id) + (1 << 31)) % (1 << 32)) - (1 << 31)
+    lib().vsg_render_color(rid, C.byref(c))
+    return tuple(c)
+
+
+def default_stride(width):
+    return (3 * width + 3) // 4 * 4
+
+
+def _is_torch(x):
+    return type(x).__module__.startswith("torch")
+
+
+def _frame_ptr(x, rows, width, what):
+    """(pointer, row stride in bytes, mem kind) of a rows x width x 3 uint8 array or tensor whose
+    pixels are packed and whose rows may be further apart."""
+    if tuple(x.shape) != (rows, width, 3):
+        raise ValueError("%s has to be %d x %d x 3, got %s" % (what, rows, width, tuple(x.shape)))
+    if str(x.dtype).replace("torch.", "") != "uint8":
+        raise TypeError("%s has to be uint8" % what)
+    if _is_torch(x):
+        if x.stride(2) != 1 or x.stride(1) != 3 or (rows > 1 and x.stride(0) < 3 * width):
+            raise ValueError("%s: pixels have to be packed BGR24" % what)
+        if x.is_cuda:
+            import torch
+            torch.cuda.current_stream(x.device).synchronize()   # the library works on its own stream
+        return C.c_void_p(x.data_ptr()), x.stride(0), VSG_MEM_DEVICE if x.is_cuda else VSG_MEM_HOST
+    if x.strides[2] != 1 or x.strides[1] != 3 or (rows > 1 and x.strides[0] < 3 * width):
+        raise ValueError("%s: pixels have to be packed BGR24" % what)
+    return x.ctypes.data_as(C.c_void_p), x.strides[0], VSG_MEM_HOST
+
+
+class SegmentationRenderer:
+    """Renders SegmentationDesc messages at a hierarchy level on one MI355X.
+
+    options: blend_alpha (0.5), hierarchy_level (0; fractional = fraction of the hierarchy's height),
+    highlight_edges (True), concat_with_source (False), has_video (True), device (-1)."""
+
+    def __init__(self, width, height, **options):
+        self.W, self.H = width, height
+        self.opts = default_render_options(**{k: (int(v) if isinstance(v, bool) else v) for k, v in options.items()})
+        h = C.c_void_p()
+        check(lib().vsg_render_create(C.byref(self.opts), width, height, C.byref(h)))
+        self.h = h
+        self._destroy = lib().vsg_render_destroy
+
+    def close(self):
+        if getattr(self, "h", None):
+            self._destroy(self.h)
+            self.h = None
+
+    def __del__(self):
+        self.close()
+
+    @property
+    def out_rows(self):
+        return self.H * (2 if self.opts.concat_with_source else 1)
+
+    @property
+    def level(self):
+        """The level resolved on the first rendered frame (None before it)."""
+        v = C.c_int()
+        rc = lib().vsg_render_level(self.h, C.byref(v))
+        if rc == _lib.VSG_ERR_STATE:
+            return None
+        check(rc)
+        return v.value
+
+    def render(self, seg_bytes, bgr=None, out=None):
+        """Returns the rendered out_rows x W x 3 uint8 frame: a numpy array, or a torch CUDA tensor
+        when bgr is one.  out: a caller's buffer instead (rows x W x 3 view; its rows may be wider
+        than 3 * W bytes, the bytes between them are left alone)."""
+        p_bgr, stride, mem_in = None, 0, VSG_MEM_HOST
+        if self.opts.has_video:
+            if bgr is None:
+                raise ValueError("the renderer was created with has_video: pass the source frame")
+            p_bgr, stride, mem_in = _frame_ptr(bgr, self.H, self.W, "bgr")
+        if out is None:
+            if bgr is not None and self.opts.has_video and _is_torch(bgr) and bgr.is_cuda:
+                import torch
+                out = torch.empty((self.out_rows, self.W, 3), dtype=torch.uint8, device=bgr.device)
+            else:
+                out = np.empty((self.out_rows, self.W, 3), np.uint8)
+        p_out, out_stride, mem_out = _frame_ptr(out, self.out_rows, self.W, "out")
+        seg_bytes = bytes(seg_bytes)
+        check(lib().vsg_render_frame(self.h, seg_bytes, len(seg_bytes), p_bgr, stride, mem_in, p_out, out_stride,
+                                     mem_out))
+        return out
+
+    def id_image(self, seg_bytes, level=0, out=None):
+        """H x W int32 ids at `level` (-1 where no region covers a pixel).  out: a contiguous int32
+        numpy array or torch CUDA tensor to fill instead of a new numpy array."""
+        if out is None:
+            out = np.empty((self.H, self.W), np.int32)
+        if tuple(out.shape) != (self.H, self.W) or str(out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("out has to be %d x %d int32" % (self.H, self.W))
+        if _is_torch(out):
+            if not out.is_contiguous():
+                raise ValueError("out has to be contiguous")
+            p, mem = C.c_void_p(out.data_ptr()), VSG_MEM_DEVICE if out.is_cuda else VSG_MEM_HOST
+            if out.is_cuda:
+                import torch
+                torch.cuda.current_stream(out.device).synchronize()
+        else:
+            if not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out has to be C-contiguous")
+            p, mem = out.ctypes.data_as(C.c_void_p), VSG_MEM_HOST
+        seg_bytes = bytes(seg_bytes)
+        check(lib().vsg_render_id_image(self.h, seg_bytes, len(seg_bytes), int(level), p, mem))
+        return out
+
+    def last_stats(self):
+        """vsg_render_last_stats of the last render / id_image call, as a dict."""
+        s = VsgRenderStats()
+        check(lib().vsg_render_last_stats(self.h, C.byref(s)))
+        return s.as_dict()

@@ -1,0 +1,589 @@
+// render_capi.cpp -- extern "C" entry points declared in include/vsg_render.h: the proto reader, the
+// hierarchy state of the reference's SegmentationRenderUnit, the colour table and the device buffers
+// around the two kernels of render.hip.
+#include <algorithm>
+#include <chrono>
+#include <cmath>
+#include <cstring>
+#include <memory>
+#include <stdexcept>
+#include <string>
+#include <unordered_map>
+#include <utility>
+#include <vector>
+
+#include "../../include/vsg_render.h"
+#include "render.h"
+
+namespace {
+
+using vsg_render_impl::Interval;
+
+struct Error : std::runtime_error {
+  int code;
+  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
+};
+
+[[noreturn]] void Throw(int code, const std::string& msg) { throw Error(code, msg); }
+
+#define RENDER_HIP(call)                                                                        \
+  do {                                                                                          \
+    hipError_t e_ = (call);                                                                     \
+    if (e_ != hipSuccess) Throw(VSG_ERR_DEVICE, std::string(hipGetErrorString(e_)) + " in " #call); \
+  } while (0)
+
+thread_local std::string g_last_error;
+
+template <class F>
+int Guard(F&& f) {
+  try {
+    f();
+    return VSG_OK;
+  } catch (const Error& e) {
+    g_last_error = e.what();
+    return e.code;
+  } catch (const std::exception& e) {
+    g_last_error = e.what();
+    return VSG_ERR_INTERNAL;
+  }
+}
+
+// Binds the calling thread to the handle's device for the duration of a call (a handle may be
+// driven from any thread; the HIP current device is a per-thread setting).
+class DeviceGuard {
+ public:
+  explicit DeviceGuard(int device) {
+    if (hipGetDevice(&prev_) != hipSuccess) return;
+    if (prev_ != device) {
+      RENDER_HIP(hipSetDevice(device));
+      changed_ = true;
+    }
+  }
+  ~DeviceGuard() {
+    if (changed_) (void)hipSetDevice(prev_);
+  }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+
+ private:
+  int prev_ = -1;
+  bool changed_ = false;
+};
+
+double NowMs() {
+  return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
+      .count();
+}
+
+// ---- glibc rand() ---------------------------------------------------------------------------
+// srand(seed) + three rand() calls of glibc's default generator (stdlib/random_r.c: TYPE_3, an
+// additive feedback generator of degree 31 and separation 3, seeded by a Lehmer sequence, its first
+// 310 outputs discarded), on a private state.
+void GlibcColor(int region_id, uint8_t c[3]) {
+  uint32_t seed = (uint32_t)region_id;   // srand takes an unsigned int
+  if (seed == 0) seed = 1;
+  uint32_t state[31];
+  int32_t word = (int32_t)seed;
+  state[0] = (uint32_t)word;
+  for (int i = 1; i < 31; ++i) {
+    const int64_t hi = word / 127773, lo = word % 127773;
+    int64_t w = 16807 * lo - 2836 * hi;
+    if (w < 0) w += 2147483647;
+    word = (int32_t)w;
+    state[i] = (uint32_t)word;
+  }
+  int f = 3, r = 0;
+  auto next = [&]() {
+    const uint32_t val = (state[f] += state[r]);
+    if (++f >= 31) {
+      f = 0;
+      ++r;
+    } else if (++r >= 31) {
+      r = 0;
+    }
+    return (int32_t)(val >> 1);
+  };
+  for (int i = 0; i < 310; ++i) next();
+  for (int k = 0; k < 3; ++k) c[k] = (uint8_t)(next() % 255);
+}
+
+// ---- minimal proto2 reader --------------------------------------------------------------------
+struct Cursor {
+  const uint8_t* p;
+  const uint8_t* end;
+  bool ok = true;
+  uint64_t Varint() {
+    uint64_t v = 0;
+    int shift = 0;
+    while (p < end) {
+      const uint8_t b = *p++;
+      v |= (uint64_t)(b & 0x7f) << shift;
+      if (!(b & 0x80)) return v;
+      shift += 7;
+      if (shift > 63) break;
+    }
+    ok = false;
+    return 0;
+  }
+  // Next field: number and wire type; a varint's value, or a length-delimited payload in *sub.
+  bool Next(int* field, int* wt, Cursor* sub, uint64_t* value) {
+    if (p >= end || !ok) return false;
+    const uint64_t tag = Varint();
+    *field = (int)(tag >> 3);
+    *wt = (int)(tag & 7);
+    if (*wt == 0) {
+      *value = Varint();
+    } else if (*wt == 2) {
+      const uint64_t n = Varint();
+      if (!ok || n > (uint64_t)(end - p)) return ok = false;
+      sub->p = p;
+      sub->end = p + n;
+      sub->ok = true;
+      p += n;
+    } else if (*wt == 5) {
+      if (end - p < 4) return ok = false;
+      p += 4;
+    } else if (*wt == 1) {
+      if (end - p < 8) return ok = false;
+      p += 8;
+    } else {
+      return ok = false;
+    }
+    return ok;
+  }
+};
+
+struct CompoundRef {
+  int32_t id, parent_id;
+};
+typedef std::vector<std::vector<CompoundRef>> Hierarchy;   // [level], sorted by id
+
+// What a render needs of a SegmentationDesc: per Region2D its id and where its intervals start in
+// `intervals` (value still unset), and the hierarchy.
+struct ParsedDesc {
+  std::vector<int32_t> region_ids;
+  std::vector<size_t> region_begin;   // region_ids.size() + 1 entries
+  Hierarchy hierarchy;
+};
+
+void ParseDesc(const uint8_t* seg, size_t len, int W, int H, ParsedDesc* d, std::vector<Interval>* intervals) {
+  d->region_ids.clear();
+  d->region_begin.clear();
+  d->hierarchy.clear();
+  intervals->clear();
+  Cursor top{seg, seg + len};
+  int f, wt;
+  uint64_t v;
+  Cursor sub{nullptr, nullptr};
+  int frame_w = 0, frame_h = 0;
+  while (top.Next(&f, &wt, &sub, &v)) {
+    if (f == 4 && wt == 0) frame_w = (int)(int64_t)v;
+    if (f == 5 && wt == 0) frame_h = (int)(int64_t)v;
+    if (f == 2 && wt == 2) {   // SegmentationDesc.region
+      int id = -1;
+      Cursor region = sub, raster{nullptr, nullptr}, rsub{nullptr, nullptr};
+      bool has_raster = false;
+      while (region.Next(&f, &wt, &rsub, &v)) {
+        if (f == 1 && wt == 0) id = (int)(int64_t)v;                      // Region2D.id
+        if (f == 3 && wt == 2) { raster = rsub; has_raster = true; }      // Region2D.raster
+      }
+      if (!region.ok) Throw(VSG_ERR_INVALID, "malformed Region2D");
+      d->region_ids.push_back(id);
+      d->region_begin.push_back(intervals->size());
+      if (!has_raster) continue;
+      Cursor scan{nullptr, nullptr}, none{nullptr, nullptr};
+      while (raster.Next(&f, &wt, &scan, &v)) {
+        if (f != 1 || wt != 2) continue;   // Rasterization.scan_inter
+        int y = 0, lx = 0, rx = -1;
+        while (scan.Next(&f, &wt, &none, &v)) {
+          if (wt != 0) continue;
+          if (f == 1) y = (int)(int64_t)v;
+          if (f == 2) lx = (int)(int64_t)v;
+          if (f == 3) rx = (int)(int64_t)v;
+        }
+        if (!scan.ok) Throw(VSG_ERR_INVALID, "malformed ScanInterval");
+        if (rx < lx) continue;   // paints nothing in the reference's loop either
+        // the kernel trusts these bounds
+        if (y < 0 || y >= H || lx < 0 || rx >= W) Throw(VSG_ERR_INVALID, "scan interval outside the frame");
+        intervals->push_back(Interval{y, lx, rx, 0u});
+      }
+      if (!raster.ok) Throw(VSG_ERR_INVALID, "malformed Rasterization");
+    }
+    if (f == 3 && wt == 2) {   // SegmentationDesc.hierarchy
+      d->hierarchy.emplace_back();
+      std::vector<CompoundRef>& level = d->hierarchy.back();
+      Cursor hl = sub, cr{nullptr, nullptr}, none{nullptr, nullptr};
+      while (hl.Next(&f, &wt, &cr, &v)) {
+        if (f != 2 || wt != 2) continue;   // HierarchyLevel.region
+        CompoundRef c{-1, -1};             // parent_id defaults to -1
+        while (cr.Next(&f, &wt, &none, &v)) {
+          if (f == 1 && wt == 0) c.id = (int)(int64_t)v;
+          if (f == 4 && wt == 0) c.parent_id = (int)(int64_t)v;
+        }
+        if (!cr.ok) Throw(VSG_ERR_INVALID, "malformed CompoundRegion");
+        level.push_back(c);
+      }
+      if (!hl.ok) Throw(VSG_ERR_INVALID, "malformed HierarchyLevel");
+      // GetCompoundRegionFromId is a binary search (segmentation_util.cpp:123-136)
+      if (!std::is_sorted(level.begin(), level.end(),
+                          [](const CompoundRef& a, const CompoundRef& b) { return a.id < b.id; })) {
+        Throw(VSG_ERR_INVALID, "hierarchy level is not sorted by region id");
+      }
+    }
+  }
+  if (!top.ok) Throw(VSG_ERR_INVALID, "malformed SegmentationDesc");
+  d->region_begin.push_back(intervals->size());
+  if ((frame_w && frame_w != W) || (frame_h && frame_h != H)) {
+    Throw(VSG_ERR_INVALID, "SegmentationDesc is " + std::to_string(frame_w) + "x" + std::to_string(frame_h) +
+                               ", the handle " + std::to_string(W) + "x" + std::to_string(H));
+  }
+}
+
+// GetParentId(region_id, 0, level, hierarchy), segmentation_util.cpp:166-185.
+int ParentId(int region_id, int level, const Hierarchy& hier) {
+  int id = region_id;
+  for (int l = 0; l < level; ++l) {
+    const std::vector<CompoundRef>& regions = hier[l];
+    auto it = std::lower_bound(regions.begin(), regions.end(), id,
+                               [](const CompoundRef& c, int key) { return c.id < key; });
+    if (it == regions.end() || it->id != id) {
+      Throw(VSG_ERR_INVALID, "region " + std::to_string(id) + " is not in hierarchy level " + std::to_string(l));
+    }
+    id = it->parent_id;
+  }
+  return id;
+}
+
+// A device or pinned-host block that only grows; every runtime allocation is counted.
+struct Block {
+  void* p = nullptr;
+  size_t cap = 0;
+  bool pinned = false;
+  void Reserve(size_t bytes, int64_t* allocations) {
+    if (bytes <= cap) return;
+    Release();
+    const size_t want = std::max(bytes, cap + cap / 2);
+    if (pinned) RENDER_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
+    else RENDER_HIP(hipMalloc(&p, want));
+    cap = want;
+    ++*allocations;
+  }
+  void Release() {
+    if (!p) return;
+    if (pinned) (void)hipHostFree(p);
+    else (void)hipFree(p);
+    p = nullptr;
+    cap = 0;
+  }
+};
+
+}  // namespace
+
+struct vsg_render {
+  vsg_render_options opt;
+  int device = 0, W = 0, H = 0, pitch = 0;
+  hipStream_t stream = nullptr;
+  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  // SegmentationRenderUnit's state
+  bool level_resolved = false;
+  int level = 0;
+  Hierarchy kept;
+  // scratch of a call
+  ParsedDesc desc;
+  std::vector<Interval> intervals;
+  std::unordered_map<int32_t, uint32_t> colors;   // mapped id -> packed colour (a pure function)
+  Block d_intervals, h_intervals, d_plane, d_src, d_out, d_ids;
+  int64_t allocations = 0;
+  vsg_render_stats stats;
+
+  ~vsg_render() {
+    if (stream) (void)hipStreamSynchronize(stream);
+    for (Block* b : {&d_intervals, &h_intervals, &d_plane, &d_src, &d_out, &d_ids}) b->Release();
+    for (hipEvent_t e : ev) {
+      if (e) (void)hipEventDestroy(e);
+    }
+    if (stream) (void)hipStreamDestroy(stream);
+  }
+
+  // Interval list to the device through the pinned block (rewritten only after the stream drained:
+  // every call ends with a synchronisation).
+  void UploadIntervals() {
+    const size_t bytes = intervals.size() * sizeof(Interval);
+    if (!bytes) return;
+    h_intervals.Reserve(bytes, &allocations);
+    d_intervals.Reserve(bytes, &allocations);
+    std::memcpy(h_intervals.p, intervals.data(), bytes);
+    RENDER_HIP(hipMemcpyAsync(d_intervals.p, h_intervals.p, bytes, hipMemcpyHostToDevice, stream));
+    ++stats.launches;
+  }
+
+  void FinishStats() {
+    RENDER_HIP(hipStreamSynchronize(stream));
+    float ms = 0;
+    RENDER_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
+    stats.clear_us = ms * 1000.0f;
+    RENDER_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
+    stats.fill_us = ms * 1000.0f;
+    RENDER_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
+    stats.compose_us = ms * 1000.0f;
+    stats.device_allocations = allocations;
+  }
+};
+
+namespace {
+
+void CheckMem(int mem, const char* what) {
+  if (mem != VSG_MEM_HOST && mem != VSG_MEM_DEVICE) Throw(VSG_ERR_INVALID, std::string(what) + ": unknown memory kind");
+}
+
+// Parses the desc, applies the hierarchy bookkeeping both entry points share (a desc that carries a
+// hierarchy replaces the kept one) and returns the hierarchy to map ids with.
+const Hierarchy& Ingest(vsg_render* h, const uint8_t* seg, size_t seg_len) {
+  if (!seg && seg_len) Throw(VSG_ERR_INVALID, "seg is null");
+  ParseDesc(seg, seg_len, h->W, h->H, &h->desc, &h->intervals);
+  if (!h->desc.hierarchy.empty()) h->kept = h->desc.hierarchy;
+  return h->kept;
+}
+
+// Sets every interval's value to value_of(mapped id of its region); returns the distinct mapped ids.
+template <class ValueOf>
+int64_t AssignValues(vsg_render* h, int level, const Hierarchy& hier, ValueOf value_of) {
+  std::unordered_map<int32_t, uint32_t> seen;   // one lookup and one colour per distinct id and frame
+  const ParsedDesc& d = h->desc;
+  for (size_t r = 0; r < d.region_ids.size(); ++r) {
+    if (d.region_begin[r] == d.region_begin[r + 1]) continue;
+    const int mapped = level > 0 ? ParentId(d.region_ids[r], level, hier) : d.region_ids[r];
+    auto it = seen.find(mapped);
+    if (it == seen.end()) it = seen.emplace(mapped, value_of(mapped)).first;
+    for (size_t k = d.region_begin[r]; k < d.region_begin[r + 1]; ++k) h->intervals[k].value = it->second;
+  }
+  return (int64_t)seen.size();
+}
+
+}  // namespace
+
+extern "C" {
+
+const char* vsg_render_last_error(void) { return g_last_error.c_str(); }
+
+void vsg_render_default_options(vsg_render_options* o) {
+  if (!o) return;
+  o->blend_alpha = 0.5f;
+  o->hierarchy_level = 0.0f;
+  o->highlight_edges = 1;
+  o->concat_with_source = 0;
+  o->has_video = 1;
+  o->device = -1;
+}
+
+size_t vsg_render_default_stride(int width) {
+  size_t step = (size_t)width * 3;
+  if (step % 4) step += 4 - step % 4;
+  return step;
+}
+
+void vsg_render_color(int region_id, uint8_t c[3]) { GlibcColor(region_id, c); }
+
+int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_render** out) {
+  return Guard([&] {
+    if (!out) Throw(VSG_ERR_INVALID, "handle pointer is null");
+    *out = nullptr;
+    vsg_render_options opt;
+    vsg_render_default_options(&opt);
+    if (o) opt = *o;
+    if (width <= 0 || height <= 0 || width > (1 << 15) || height > (1 << 15)) Throw(VSG_ERR_INVALID, "bad frame size");
+    if (!(opt.hierarchy_level >= 0.0f && opt.hierarchy_level <= 1e6f)) Throw(VSG_ERR_INVALID, "bad hierarchy_level");
+    if (!std::isfinite(opt.blend_alpha)) Throw(VSG_ERR_INVALID, "bad blend_alpha");
+    if (opt.concat_with_source && !opt.has_video) {
+      Throw(VSG_ERR_INVALID, "Request concatenation with source but no video stream present.");
+    }
+    if (!opt.has_video) opt.blend_alpha = 1.0f;   // segmentation_unit.cpp:486-490
+    int n = 0;
+    const hipError_t e = hipGetDeviceCount(&n);
+    if (e != hipSuccess || n <= 0) {
+      Throw(VSG_ERR_DEVICE, "no usable HIP device (libvsg_render has no CPU fallback): " +
+                                std::string(e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
+    }
+    if (opt.device >= n) Throw(VSG_ERR_DEVICE, "device ordinal out of range");
+    std::unique_ptr<vsg_render> h(new vsg_render);
+    h->opt = opt;
+    h->W = width;
+    h->H = height;
+    h->pitch = vsg_render_impl::PlanePitch(width);
+    std::memset(&h->stats, 0, sizeof(h->stats));
+    h->h_intervals.pinned = true;
+    if (opt.device >= 0) h->device = opt.device;
+    else RENDER_HIP(hipGetDevice(&h->device));
+    DeviceGuard guard(h->device);
+    RENDER_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    for (hipEvent_t& ev : h->ev) RENDER_HIP(hipEventCreate(&ev));
+    h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
+    *out = h.release();
+  });
+}
+
+void vsg_render_destroy(vsg_render* h) {
+  if (!h) return;
+  int prev = -1;
+  const bool have = hipGetDevice(&prev) == hipSuccess;
+  (void)hipSetDevice(h->device);
+  delete h;
+  if (have) (void)hipSetDevice(prev);
+}
+
+int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const uint8_t* bgr, size_t stride,
+                     int mem_in, uint8_t* out, size_t out_stride, int mem_out) {
+  return Guard([&] {
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    CheckMem(mem_in, "bgr");
+    CheckMem(mem_out, "out");
+    const int W = h->W, H = h->H;
+    const size_t row_bytes = (size_t)W * 3;
+    const bool video = h->opt.has_video != 0;
+    if (video && !bgr) Throw(VSG_ERR_INVALID, "the handle was created with has_video: bgr is null");
+    if (video && stride < row_bytes) Throw(VSG_ERR_INVALID, "stride is smaller than 3 * width");
+    if (out_stride == 0) out_stride = vsg_render_default_stride(W);
+    if (out_stride < row_bytes) Throw(VSG_ERR_INVALID, "out_stride is smaller than 3 * width");
+    const int out_rows = h->opt.concat_with_source ? 2 * H : H;
+    DeviceGuard guard(h->device);
+    std::memset(&h->stats, 0, sizeof(h->stats));
+
+    // ---- host: decode, hierarchy state (segmentation_unit.cpp:567-591), colour table ----
+    const double t0 = NowMs();
+    const Hierarchy& hier = Ingest(h, seg, seg_len);
+    if (!h->level_resolved) {
+      const int size = (int)h->desc.hierarchy.size();   // the first frame's own hierarchy
+      float lvl = h->opt.hierarchy_level;
+      if (lvl != std::floor(lvl)) lvl = (float)(int)(lvl * size);
+      h->level = std::min<int>((int)lvl, size - 1);
+      h->level_resolved = true;
+    }
+    // HierarchyColorGenerator's own clamps (segmentation_render.cpp:40-50)
+    int level = h->level;
+    if (level > 0 && hier.empty()) level = 0;
+    if (!hier.empty() && level >= (int)hier.size()) level = (int)hier.size() - 1;
+    if (h->colors.size() > (1u << 20)) h->colors.clear();
+    h->stats.distinct_ids = AssignValues(h, level, hier, [&](int mapped) {
+      auto it = h->colors.find(mapped);
+      if (it == h->colors.end()) {
+        uint8_t c[3];
+        GlibcColor(mapped, c);
+        it = h->colors.emplace(mapped, (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16).first;
+      }
+      return it->second;
+    });
+    h->stats.intervals = (int64_t)h->intervals.size();
+    const double t1 = NowMs();
+    h->stats.decode_ms = t1 - t0;
+
+    // ---- uploads ----
+    h->UploadIntervals();
+    const uint8_t* src = nullptr;
+    size_t src_stride = 0;
+    if (video) {
+      if (mem_in == VSG_MEM_DEVICE) {
+        src = bgr;
+        src_stride = stride;
+      } else {
+        src_stride = vsg_render_default_stride(W);
+        h->d_src.Reserve(src_stride * H, &h->allocations);
+        RENDER_HIP(hipMemcpy2DAsync(h->d_src.p, src_stride, bgr, stride, row_bytes, H, hipMemcpyHostToDevice,
+                                    h->stream));
+        ++h->stats.launches;
+        src = static_cast<const uint8_t*>(h->d_src.p);
+      }
+    }
+    uint8_t* dst = out;
+    size_t dst_stride = out_stride;
+    if (mem_out == VSG_MEM_HOST) {
+      dst_stride = vsg_render_default_stride(W);
+      h->d_out.Reserve(dst_stride * out_rows, &h->allocations);
+      dst = static_cast<uint8_t*>(h->d_out.p);
+    }
+    h->stats.upload_ms = NowMs() - t1;
+
+    // ---- device: clear, fill, compose ----
+    uint32_t* plane = static_cast<uint32_t*>(h->d_plane.p);
+    RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
+    RENDER_HIP(hipMemsetAsync(plane, 0, (size_t)h->pitch * H * sizeof(uint32_t), h->stream));
+    RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
+    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), (int64_t)h->intervals.size(), plane,
+                                h->pitch, h->stream);
+    RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
+    const int mode = h->opt.concat_with_source ? vsg_render_impl::COMPOSE_CONCAT
+                     : video                   ? vsg_render_impl::COMPOSE_BLEND
+                                               : vsg_render_impl::COMPOSE_RENDER;
+    vsg_render_impl::LaunchCompose(plane, h->pitch, W, H, src, src_stride, dst, dst_stride, h->opt.highlight_edges,
+                                   mode, h->opt.blend_alpha, h->stream);
+    RENDER_HIP(hipGetLastError());
+    RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
+    h->stats.launches += 2 + (h->intervals.empty() ? 0 : 1);
+    if (mem_out == VSG_MEM_HOST) {
+      RENDER_HIP(hipMemcpy2DAsync(out, out_stride, dst, dst_stride, row_bytes, out_rows, hipMemcpyDeviceToHost,
+                                  h->stream));
+      ++h->stats.launches;
+    }
+    h->FinishStats();
+  });
+}
+
+int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int32_t* out, int mem_out) {
+  return Guard([&] {
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    CheckMem(mem_out, "out");
+    const int W = h->W, H = h->H;
+    DeviceGuard guard(h->device);
+    std::memset(&h->stats, 0, sizeof(h->stats));
+    const double t0 = NowMs();
+    const Hierarchy& hier = Ingest(h, seg, seg_len);
+    if (level < 0 || (level > 0 && level >= (int)hier.size())) {
+      Throw(VSG_ERR_INVALID, "level " + std::to_string(level) + " is not in the hierarchy (" +
+                                 std::to_string(hier.size()) + " levels)");
+    }
+    h->stats.distinct_ids = AssignValues(h, level, hier, [](int mapped) { return (uint32_t)mapped; });
+    h->stats.intervals = (int64_t)h->intervals.size();
+    const double t1 = NowMs();
+    h->stats.decode_ms = t1 - t0;
+    h->UploadIntervals();
+    const size_t bytes = (size_t)W * H * sizeof(int32_t);
+    uint32_t* ids = reinterpret_cast<uint32_t*>(out);   // device output: painted in place
+    if (mem_out == VSG_MEM_HOST) {
+      h->d_ids.Reserve(bytes, &h->allocations);
+      ids = static_cast<uint32_t*>(h->d_ids.p);
+    }
+    h->stats.upload_ms = NowMs() - t1;
+    RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
+    RENDER_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
+    RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
+    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), (int64_t)h->intervals.size(), ids, W,
+                                h->stream);
+    RENDER_HIP(hipGetLastError());
+    RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
+    RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
+    h->stats.launches += 1 + (h->intervals.empty() ? 0 : 1);
+    if (mem_out == VSG_MEM_HOST) {
+      RENDER_HIP(hipMemcpyAsync(out, ids, bytes, hipMemcpyDeviceToHost, h->stream));
+      ++h->stats.launches;
+    }
+    h->FinishStats();
+  });
+}
+
+int vsg_render_level(vsg_render* h, int* level) {
+  return Guard([&] {
+    if (!h || !level) Throw(VSG_ERR_INVALID, "null argument");
+    if (!h->level_resolved) Throw(VSG_ERR_STATE, "no frame has been rendered yet");
+    *level = h->level;
+  });
+}
+
+int vsg_render_last_stats(vsg_render* h, vsg_render_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->stats;
+  });
+}
+
+}  // extern "C"
