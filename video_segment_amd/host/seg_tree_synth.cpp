@@ -17,6 +17,7 @@
 #include <fstream>
 #include <string>
 
+#include "dense_flow_unit.h"
 #include "flow_reader.h"
 #include "raw_video_reader.h"
 #include "segmentation_io.h"
@@ -231,6 +232,8 @@ struct Flags {
                                    // driver always stops after the dense over-segmentation)
   bool write_to_file = false;      // writes <input_file>.pb (or --output_file)
   bool save_flow = false;          // writes <input base>.flow from the synthetic source
+  bool compute_flow = false;       // opt-in: with --flow and no .flow file, LuminanceUnit -> DenseFlowUnit
+                                   // compute the flow (seg_tree.cpp:170-187) instead of the source
   // dense_segmentation.cpp
   std::string dense_smoothing = "bilateral";   // none | bilateral
   std::string dense_color_dist = "l2";         // l1 | l2
@@ -270,7 +273,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
       has_v = true;
     }
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
-                                   "two_stage_oversegment", "region_segmentation", "render_concat"};
+                                   "two_stage_oversegment", "region_segmentation", "render_concat",
+                                   "compute_flow"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -294,6 +298,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "over_segment") f->over_segment = bv;
     else if (a == "write_to_file") f->write_to_file = bv;
     else if (a == "save_flow") f->save_flow = bv;
+    else if (a == "compute_flow") f->compute_flow = bv;
     else if (a == "two_stage_oversegment") f->two_stage_oversegment = bv;
     else if (a == "region_segmentation") f->region_segmentation = bv;
     else if (a == "render_concat") f->render_concat = bv;
@@ -344,7 +349,7 @@ int main(int argc, char** argv) {
     if (use_flow && flow_file.empty()) {
       const std::string candidate = input_base + ".flow";
       if (std::ifstream(candidate.c_str()).good()) flow_file = candidate;
-      else use_flow = false;   // no flow unit in this build: segment without temporal displacement
+      else if (!FLAGS.compute_flow) use_flow = false;   // segment without temporal displacement
     }
   }
   const bool flow_from_file = use_flow && !flow_file.empty();
@@ -352,8 +357,11 @@ int main(int argc, char** argv) {
       !FLAGS.flow_output_file.empty() ? FLAGS.flow_output_file
       : FLAGS.save_flow ? (FLAGS.input_file.empty() ? std::string("synth.flow") : input_base + ".flow")
                         : std::string();
-  SyntheticVideoUnit source(FLAGS.width, FLAGS.height, frames, use_flow && !flow_from_file,
-                            FLAGS.input == "bench" ? 1 : (FLAGS.input == "soft" ? 2 : 0), save_flow);
+  // --compute_flow: the flow comes from the flow units below, which also write --save_flow's file
+  const bool compute_flow = FLAGS.compute_flow && use_flow && !flow_from_file;
+  SyntheticVideoUnit source(FLAGS.width, FLAGS.height, frames, use_flow && !flow_from_file && !compute_flow,
+                            FLAGS.input == "bench" ? 1 : (FLAGS.input == "soft" ? 2 : 0),
+                            compute_flow ? std::string() : save_flow);
   VideoUnit* root = raw_reader ? static_cast<VideoUnit*>(raw_reader.get()) : &source;
   VideoUnit* input = root;
 
@@ -374,6 +382,19 @@ int main(int argc, char** argv) {
     flow_reader.reset(new DenseFlowReaderUnit(DenseFlowReaderOptions(), flow_file));
     flow_reader->AttachTo(input);
     input = flow_reader.get();
+  }
+
+  std::unique_ptr<LuminanceUnit> luminance;
+  std::unique_ptr<DenseFlowUnit> flow_unit;
+  if (compute_flow) {   // seg_tree.cpp:170-187
+    luminance.reset(new LuminanceUnit());
+    luminance->AttachTo(input);
+    DenseFlowOptions flow_options;
+    flow_options.flow_output_file = save_flow;
+    flow_options.device = FLAGS.device;
+    flow_unit.reset(new DenseFlowUnit(flow_options));
+    flow_unit->AttachTo(luminance.get());
+    input = flow_unit.get();
   }
 
   DenseSegmentationUnitOptions unit_options;
