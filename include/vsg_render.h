@@ -6,8 +6,23 @@
  * (segment_util/segmentation_util.cpp:741-770) on an MI355X: a serialized SegmentationDesc goes in,
  * a BGR24 picture of its regions at a hierarchy level (or an int32 image of their ids at a level)
  * comes out, in host or in device memory.  The library is independent of libvsg_hip.so; it reads the
- * few proto fields it needs (region.id, region.raster.scan_inter, hierarchy[l].region{id,parent_id},
- * frame_width, frame_height) with a reader of its own.
+ * few proto fields it needs (region.id, region.raster.scan_inter,
+ * region.vectorization.polygon{coord_idx, hole}, vector_mesh.coord, rasterization_removed,
+ * hierarchy[l].region{id,parent_id}, frame_width, frame_height) with a reader of its own.
+ *
+ * Vector-only descs.  The reference's result files carry no rasters: its writer strips them, sets
+ * rasterization_removed and keeps Region2D.vectorization and the vector_mesh, and every consumer
+ * rebuilds the scan intervals with RasterVectorization (segment_util/segmentation_util.cpp:1103-1246).
+ * A desc with rasterization_removed = true and a vector_mesh is rendered from its polygons: the
+ * scan conversion runs on the device (three stages: edge walk, radix sort by region and row, pairing)
+ * with the reference's f32 arithmetic, operation for operation, and hands the same interval list to
+ * the same two kernels.  Such a desc may have another frame size than the handle: its mesh is then
+ * scaled to the handle's size as ScaleVectorization does (:1248-1267).  A desc without that flag is
+ * handled as before, from its rasters, and has to have the handle's size.
+ * A vectorization with a row the reference does not define is refused with VSG_ERR_INVALID: an odd
+ * number of active edges; edges its comparator cannot order (three crossings chained within its
+ * eps of 1e-3, or two it cannot tell apart at different x); an interval with left_x outside [0, W]
+ * or right_x outside [-1, W - 1]; a coord_idx outside the mesh; a line outside rows [0, H].
  *
  * Conventions are those of vsg.h: every function returns VSG_OK (0) or a negative status,
  * vsg_render_last_error() is a thread-local message of the last failure, a handle is
@@ -103,6 +118,32 @@ int vsg_render_level(vsg_render* h, int* level);
 size_t vsg_render_default_stride(int width);
 
 int vsg_render_last_stats(vsg_render* h, vsg_render_stats* s);
+
+/* ReplaceRasterizationFromVectorization (segmentation_util.cpp:1238-1246) as a service: the scan
+ * intervals of every region's vectorization, scaled to the handle's frame size, as int32 quadruples
+ * {y, left_x, right_x, region_id} in the reference's order: regions in the desc's order, rows
+ * upwards, left to right.  The empty intervals the reference emits where two edges start at one
+ * vertex (left_x = right_x + 1) are included.  The desc needs a vector_mesh; rasterization_removed
+ * is not looked at, rasters are ignored, and the handle's kept hierarchy is left alone.
+ * *count is the number of intervals of the frame; when capacity_intervals is smaller the call
+ * fails with VSG_ERR_INVALID, *count set and out untouched.  out: mem_out memory.
+ * out == NULL with capacity_intervals == 0 asks for the count only: the desc is decoded and its lines
+ * are checked on the host, nothing runs on the device, and the call returns VSG_OK with *count. */
+int vsg_render_rasterize(vsg_render* h, const uint8_t* seg, size_t seg_len, int32_t* out,
+                         size_t capacity_intervals, size_t* count, int mem_out);
+
+/* What the vector path of the handle's last call did (all zero after a call on a desc with
+ * rasters).  Device times are HIP events around the stages. */
+typedef struct vsg_render_vector_stats {
+  int64_t lines;           /* polygon lines kept (|dy| >= 1e-3)                                    */
+  int64_t crossings;       /* line x row crossings = 2 * intervals                                 */
+  int64_t groups;          /* (region, row) pairs with at least one crossing                       */
+  int64_t largest_group;   /* most crossings of one region in one row                              */
+  float walk_us, sort_us, pairs_us;   /* k_vec_walk, the radix sort, k_vec_pairs                   */
+  int launches;            /* enqueued by the vector stages; the radix sort counts as one          */
+} vsg_render_vector_stats;
+
+int vsg_render_last_vector_stats(vsg_render* h, vsg_render_vector_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -9,6 +9,14 @@ memory, default options (edges, blend 0.5).  In the same run a device-to-device 
 pixel is timed with torch events: it reads and writes as many bytes as the two kernels have to move
 (plane write 4 + plane read 4 + frame read 3 + frame write 3 = 14 per pixel).  Medians over the
 repetitions after a warm-up, with the 10th and 90th percentile as the spread.
+
+    python tools/render_probe.py --vector [--out profiles/vector_raster.json]
+
+The vector leg: the same four chunk results computed with compute_vectorization, once as they are
+(rasters: the path above) and once as the reference's writer leaves them (rasters cleared,
+rasterization_removed set).  For the vector-only desc the three scan conversion stages (k_vec_walk,
+radix sort, k_vec_pairs; vsg_render_last_vector_stats), host decode and upload and the fill are
+recorded, for the desc with rasters decode, upload and fill: the yardstick beside them.
 """
 import argparse
 import json
@@ -32,9 +40,12 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=60)
     ap.add_argument("--warmup", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "render_kernels.json"))
+    ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="1920x1080,3840x2160")
+    ap.add_argument("--vector", action="store_true", help="the vector leg instead (profiles/vector_raster.json)")
     args = ap.parse_args()
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "vector_raster.json" if args.vector else "render_kernels.json")
 
     import torch
     import synth
@@ -44,6 +55,8 @@ def main():
         sys.exit("render_probe needs a HIP device: a time from anywhere else says nothing")
     dev = torch.device("cuda", 0)
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
+    if args.vector:
+        return vector_leg(args, result, dev)
     for size in args.sizes.split(","):
         W, H = (int(v) for v in size.split("x"))
         px = W * H
@@ -100,6 +113,62 @@ def main():
                 "host_upload_ms": med["upload_ms"],
                 "call_wall_ms": med["call_ms"],
             }
+            result["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+    print("wrote", args.out)
+
+
+def vector_leg(args, result, dev):
+    import torch
+    import synth
+    import vector_raster_model as vm
+    import video_segment_amd as vsg
+    from test_proto_wire import build_schema
+    Msg = build_schema()
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        for kind, frame_fn in (("checker", synth.bench_frame), ("noise", synth.noise_frame)):
+            N = 3
+            fl = torch.from_numpy(synth.const_flow(W, H)).to(dev)
+            d = vsg.DenseSegmentation(W, H, vsg.default_options(chunk_size=20, compute_vectorization=1), has_flow=True)
+            frames, segs = [], []
+            for k in range(N):
+                frames.append(torch.from_numpy(frame_fn(W, H, k)).to(dev))
+                n = d.process_frame(frames[k], fl if k > 0 else None, flush=(k == N - 1))
+                segs += [d.result_bytes(i) for i in range(n)]
+            d.close()
+            m = Msg()
+            m.ParseFromString(segs[1])
+            stripped = vm.remove_rasterization(m)
+            stripped.frame_width, stripped.frame_height = W, H
+            frame = frames[1]
+            out = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            case = {"size": size, "input": kind, "regions": len(m.region)}
+            for leg, seg in (("raster", segs[1]), ("vector", stripped.SerializeToString())):
+                r = vsg.SegmentationRenderer(W, H)
+                keys = ["decode_ms", "upload_ms", "clear_us", "fill_us", "compose_us", "call_ms"]
+                if leg == "vector":
+                    keys += ["walk_us", "sort_us", "pairs_us"]
+                rows = {k: [] for k in keys}
+                for it in range(args.warmup + args.reps):
+                    t0 = time.perf_counter()
+                    r.render(seg, frame, out=out)
+                    call_ms = (time.perf_counter() - t0) * 1e3
+                    st = dict(r.last_stats(), call_ms=call_ms, **r.last_vector_stats())
+                    if it >= args.warmup:
+                        for k in keys:
+                            rows[k].append(st[k])
+                st = dict(r.last_stats(), **r.last_vector_stats())
+                r.close()
+                entry = {k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()}
+                entry.update(seg_bytes=len(seg), intervals=st["intervals"], launches_per_frame=st["launches"])
+                if leg == "vector":
+                    entry.update(lines=st["lines"], crossings=st["crossings"], groups=st["groups"],
+                                 largest_group=st["largest_group"])
+                case[leg] = entry
             result["cases"].append(case)
             print(json.dumps(case), flush=True)
             with open(args.out, "w") as f:

@@ -10,6 +10,12 @@
 //   --render_level <float> [--render_concat] [--render_blend_alpha <float>]
 // puts a SegmentationRenderUnit (seg_tree.cpp --render_and_save) behind the segmentation and prints a
 // second line, render_frames=N render_fnv1a32=<FNV-1a-32 of the rendered frames' pixel bytes>.
+//
+//   --write_to_file --remove_rasterization [--original_width W --original_height H]
+// writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
+// size where the source says it was downscaled; a render unit in the same run is then put behind the
+// writer and given the same vector-only descs (at the stream's size), which is what a consumer of the
+// file renders.  --rewrite_pb FILE applies the writer's edit to a container (no GPU).
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -41,14 +47,16 @@ class SyntheticVideoUnit : public VideoUnit {
  public:
   // kind: 0 probe, 1 bench, 2 soft (tests/synth.py: soft_frame, the input of the hierarchical stage)
   SyntheticVideoUnit(int width, int height, int frames, bool flow, int kind,
-                     const std::string& save_flow = std::string())
+                     const std::string& save_flow = std::string(), int original_width = 0, int original_height = 0)
       : width_(width), height_(height), frames_(frames), flow_(flow), bench_(kind != 0), soft_(kind == 2),
-        save_flow_(save_flow) {}
+        save_flow_(save_flow), original_width_(original_width), original_height_(original_height) {}
 
   bool OpenStreams(StreamSet* set) override {
     width_step_ = (width_ * 3 + 3) / 4 * 4;   // padded like video_reader_unit.cpp:200-206
-    set->push_back(std::shared_ptr<DataStream>(
-        new VideoStream(width_, height_, width_step_, 25.0f, PIXEL_FORMAT_BGR24, "VideoStream")));
+    std::shared_ptr<VideoStream> video(
+        new VideoStream(width_, height_, width_step_, 25.0f, PIXEL_FORMAT_BGR24, "VideoStream"));
+    if (original_width_ > 0 && original_height_ > 0) video->set_original_size(original_width_, original_height_);
+    set->push_back(video);
     if (flow_) {
       set->push_back(std::shared_ptr<DataStream>(
           new DenseFlowStream(width_, height_, "BackwardFlowStream")));
@@ -110,8 +118,30 @@ class SyntheticVideoUnit : public VideoUnit {
   bool flow_, bench_, soft_;
   std::string save_flow_;
   std::unique_ptr<DenseFlowWriter> flow_writer_;
+  int original_width_, original_height_;
   int width_step_ = 0;
   int k_ = 0;
+};
+
+// Replaces the stream's desc by its vector-only form (RemoveRasterization): what a reader of a file
+// written with remove_rasterization hands to the units behind it.
+class RemoveRasterizationUnit : public VideoUnit {
+ public:
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    return seg_idx_ >= 0;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const PointerFrame<SegmentationDesc>& frame = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>();
+    std::unique_ptr<SegmentationDesc> desc(new SegmentationDesc(frame.Ref()));
+    VF_CHECK(HasVectorMesh(desc->wire), "--remove_rasterization needs a vectorization (--over_segment)");
+    VF_CHECK(RemoveRasterization(&desc->wire), "malformed SegmentationDesc");
+    input->at(seg_idx_).reset(new PointerFrame<SegmentationDesc>(std::move(desc), frame.pts()));
+    output->push_back(input);
+  }
+
+ private:
+  int seg_idx_ = -1;
 };
 
 // Consumes "SegmentationStream" like the reference's writer / renderer units do
@@ -221,6 +251,27 @@ int ReadBack(const std::string& file) {
   return 0;
 }
 
+// --rewrite_pb FILE --output_file OUT [--remove_rasterization] [--original_width W --original_height H]:
+// every desc of FILE through the writer unit's edit (PrepareDescForWriting) into OUT.  No GPU.
+int Rewrite(const std::string& file, const std::string& out_file, bool remove_rasterization, int original_width,
+            int original_height) {
+  SegmentationReader reader(file);
+  if (!reader.OpenFileAndReadHeaders() || out_file.empty()) return 1;
+  SegmentationWriterUnitOptions wo;
+  wo.filename = out_file;
+  wo.remove_rasterization = remove_rasterization;
+  SegmentationWriter writer(out_file);
+  if (!writer.OpenFile(std::vector<int>{1, 0})) return 1;
+  for (int k = 0; reader.RemainingFrames() > 0; ++k) {
+    SegmentationDesc desc;
+    if (!reader.ReadNextFrame(&desc)) return 1;
+    if (!PrepareDescForWriting(wo, original_width, original_height, &desc.wire)) return 1;
+    writer.AddSegmentationDataToChunk(desc.wire, reader.TimeStamps()[k]);
+  }
+  writer.WriteTermHeaderAndClose();
+  return 0;
+}
+
 // Flags: the reference's names where it has them (seg_tree.cpp:52-72, dense_segmentation.cpp:39-46),
 // gflags syntax (--flag=value, --flag value, --flag / --noflag for booleans).
 struct Flags {
@@ -253,6 +304,11 @@ struct Flags {
   double render_level = -1;
   bool render_concat = false;
   double render_blend_alpha = 0.5;
+  // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
+  // here it is opt-in, so that the files of existing runs stay what they were)
+  bool remove_rasterization = false;
+  int original_width = 0, original_height = 0;   // the video's size before a downscale; 0 = the frame size
+  std::string rewrite_pb;
 };
 
 bool ParseFlags(int argc, char** argv, Flags* f) {
@@ -274,7 +330,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     }
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
-                                   "compute_flow"};
+                                   "compute_flow", "remove_rasterization"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -302,6 +358,10 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "two_stage_oversegment") f->two_stage_oversegment = bv;
     else if (a == "region_segmentation") f->region_segmentation = bv;
     else if (a == "render_concat") f->render_concat = bv;
+    else if (a == "remove_rasterization") f->remove_rasterization = bv;
+    else if (a == "original_width") f->original_width = atoi(v.c_str());
+    else if (a == "original_height") f->original_height = atoi(v.c_str());
+    else if (a == "rewrite_pb") f->rewrite_pb = v;
     else if (a == "render_level") f->render_level = atof(v.c_str());
     else if (a == "render_blend_alpha") f->render_blend_alpha = atof(v.c_str());
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
@@ -334,6 +394,10 @@ int main(int argc, char** argv) {
   Flags FLAGS;
   if (!ParseFlags(argc, argv, &FLAGS)) return 2;
   if (!FLAGS.read_pb.empty()) return ReadBack(FLAGS.read_pb);
+  if (!FLAGS.rewrite_pb.empty()) {
+    return Rewrite(FLAGS.rewrite_pb, FLAGS.output_file, FLAGS.remove_rasterization, FLAGS.original_width,
+                   FLAGS.original_height);
+  }
   bool use_flow = FLAGS.flow;
   int frames = FLAGS.frames;
   std::string flow_file = FLAGS.flow_file;
@@ -361,7 +425,7 @@ int main(int argc, char** argv) {
   const bool compute_flow = FLAGS.compute_flow && use_flow && !flow_from_file;
   SyntheticVideoUnit source(FLAGS.width, FLAGS.height, frames, use_flow && !flow_from_file && !compute_flow,
                             FLAGS.input == "bench" ? 1 : (FLAGS.input == "soft" ? 2 : 0),
-                            compute_flow ? std::string() : save_flow);
+                            compute_flow ? std::string() : save_flow, FLAGS.original_width, FLAGS.original_height);
   VideoUnit* root = raw_reader ? static_cast<VideoUnit*>(raw_reader.get()) : &source;
   VideoUnit* input = root;
 
@@ -439,6 +503,32 @@ int main(int argc, char** argv) {
     if (FLAGS.use_pipeline) cut();
   }
 
+  // With --remove_rasterization the label sink and the writer come first (they read the rasters), then
+  // the descs are made vector-only for the render unit.
+  HashSinkUnit sink;
+  std::unique_ptr<SegmentationWriterUnit> writer;
+  auto attach_sink_and_writer = [&]() {
+    sink.AttachTo(input);
+    input = &sink;
+    if (FLAGS.write_to_file || !FLAGS.output_file.empty()) {   // seg_tree.cpp:296-312
+      SegmentationWriterUnitOptions wo;
+      wo.filename = !FLAGS.output_file.empty() ? FLAGS.output_file
+                    : (FLAGS.input_file.empty() ? std::string("synth.pb") : FLAGS.input_file + ".pb");
+      wo.remove_rasterization = FLAGS.remove_rasterization;
+      writer.reset(new SegmentationWriterUnit(wo));
+      writer->AttachTo(input);
+      input = writer.get();
+    }
+  };
+  RemoveRasterizationUnit remove_unit;
+  if (FLAGS.remove_rasterization) {
+    attach_sink_and_writer();
+    if (FLAGS.render_level >= 0) {
+      remove_unit.AttachTo(input);
+      input = &remove_unit;
+    }
+  }
+
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
   if (FLAGS.render_level >= 0) {
@@ -453,18 +543,7 @@ int main(int argc, char** argv) {
     input = &render_sink;
   }
 
-  HashSinkUnit sink;
-  sink.AttachTo(input);
-  input = &sink;
-  std::unique_ptr<SegmentationWriterUnit> writer;
-  if (FLAGS.write_to_file || !FLAGS.output_file.empty()) {   // seg_tree.cpp:296-312
-    SegmentationWriterUnitOptions wo;
-    wo.filename = !FLAGS.output_file.empty() ? FLAGS.output_file
-                  : (FLAGS.input_file.empty() ? std::string("synth.pb") : FLAGS.input_file + ".pb");
-    writer.reset(new SegmentationWriterUnit(wo));
-    writer->AttachTo(input);
-    input = writer.get();
-  }
+  if (!FLAGS.remove_rasterization) attach_sink_and_writer();
 
   if (!root->PrepareProcessing()) {
     std::fprintf(stderr, "ERROR: Setup failed.\n");

@@ -1,10 +1,200 @@
 // segmentation_io.cpp -- see segmentation_io.h.
 #include "segmentation_io.h"
 
+#include <algorithm>
 #include <cstdio>
 #include <cstring>
 
 namespace segmentation {
+
+namespace {
+// ---- edits of a serialized SegmentationDesc ---------------------------------------------------
+bool GetVarint(const std::string& s, size_t* at, size_t end, uint64_t* v) {
+  *v = 0;
+  for (int shift = 0; *at < end && shift < 64; shift += 7) {
+    const uint8_t b = (uint8_t)s[(*at)++];
+    *v |= (uint64_t)(b & 0x7f) << shift;
+    if (!(b & 0x80)) return true;
+  }
+  return false;
+}
+
+void PutVarint(uint64_t v, std::string* out) {
+  while (v >= 0x80) {
+    out->push_back((char)(v | 0x80));
+    v >>= 7;
+  }
+  out->push_back((char)v);
+}
+
+// One field of the message in s[at, end): number, wire type, the whole field's bytes [begin, *at)
+// and, for a length-delimited one, its payload [pay, *at).
+struct Field {
+  int number, wire_type;
+  size_t begin, pay;
+  uint64_t value;
+};
+
+bool NextField(const std::string& s, size_t* at, size_t end, Field* f) {
+  f->begin = *at;
+  uint64_t tag;
+  if (!GetVarint(s, at, end, &tag)) return false;
+  f->number = (int)(tag >> 3);
+  f->wire_type = (int)(tag & 7);
+  f->pay = *at;
+  f->value = 0;
+  if (f->wire_type == 0) return GetVarint(s, at, end, &f->value);
+  uint64_t n = 0;
+  if (f->wire_type == 2) {
+    if (!GetVarint(s, at, end, &n)) return false;
+    f->pay = *at;
+  } else if (f->wire_type == 5) {
+    n = 4;
+  } else if (f->wire_type == 1) {
+    n = 8;
+  } else {
+    return false;
+  }
+  if (n > end - *at) return false;
+  *at += n;
+  return true;
+}
+
+void PutTag(int number, int wire_type, std::string* out) { PutVarint((uint64_t)number << 3 | wire_type, out); }
+
+void PutBytesField(int number, const std::string& payload, std::string* out) {
+  PutTag(number, 2, out);
+  PutVarint(payload.size(), out);
+  out->append(payload);
+}
+}  // namespace
+
+bool HasVectorMesh(const std::string& wire) {
+  size_t at = 0;
+  Field f;
+  bool mesh = false;
+  while (at < wire.size()) {
+    if (!NextField(wire, &at, wire.size(), &f)) return false;
+    if (f.number == 11 && f.wire_type == 2) mesh = true;
+  }
+  return mesh;
+}
+
+bool RemoveRasterization(std::string* wire) {
+  const std::string& in = *wire;
+  std::string out;
+  out.reserve(in.size());
+  size_t at = 0;
+  Field f;
+  while (at < in.size()) {
+    if (!NextField(in, &at, in.size(), &f)) return false;
+    if (f.number == 13) continue;   // set below
+    if (f.number == 2 && f.wire_type == 2) {   // Region2D without its raster (field 3)
+      std::string region;
+      size_t r = f.pay;
+      Field g;
+      while (r < at) {
+        if (!NextField(in, &r, at, &g)) return false;
+        if (g.number != 3) region.append(in, g.begin, r - g.begin);
+      }
+      PutBytesField(2, region, &out);
+      continue;
+    }
+    out.append(in, f.begin, at - f.begin);
+  }
+  PutTag(13, 0, &out);   // the last field of the message: serialized in field order
+  PutVarint(1, &out);
+  wire->swap(out);
+  return true;
+}
+
+bool ScaleVectorization(int width, int height, std::string* wire) {
+  const std::string& in = *wire;
+  int frame_w = 0, frame_h = 0;
+  size_t at = 0;
+  Field f;
+  while (at < in.size()) {
+    if (!NextField(in, &at, in.size(), &f)) return false;
+    if (f.number == 4 && f.wire_type == 0) frame_w = (int)(int64_t)f.value;
+    if (f.number == 5 && f.wire_type == 0) frame_h = (int)(int64_t)f.value;
+  }
+  if (frame_w <= 0 || frame_h <= 0) return false;
+  const float scale_x = width * (1.0f / frame_w);    // :1253
+  const float scale_y = height * (1.0f / frame_h);   // :1254
+  std::string out;
+  out.reserve(in.size());
+  bool size_written = false;
+  at = 0;
+  while (at < in.size()) {
+    if (!NextField(in, &at, in.size(), &f)) return false;
+    if ((f.number == 4 || f.number == 5) && f.wire_type == 0) {
+      PutTag(f.number, 0, &out);
+      PutVarint((uint64_t)(int64_t)(f.number == 4 ? width : height), &out);
+      size_written = true;
+      continue;
+    }
+    if (f.number == 11 && f.wire_type == 2) {   // vector_mesh: coord (1), packed or not, in list order
+      std::string mesh;
+      int parity = 0;   // :1251
+      auto scaled = [&](const char* p) {
+        float coord;
+        std::memcpy(&coord, p, 4);
+        coord = parity % 2 == 0 ? std::min<float>((float)width, coord * scale_x)     // :1261
+                                : std::min<float>((float)height, coord * scale_y);   // :1263
+        ++parity;
+        return coord;
+      };
+      size_t m = f.pay;
+      Field g;
+      while (m < at) {
+        if (!NextField(in, &m, at, &g)) return false;
+        if (g.number == 1 && g.wire_type == 2) {
+          if ((m - g.pay) % 4) return false;
+          std::string packed(m - g.pay, '\0');
+          for (size_t k = 0; k < packed.size(); k += 4) {
+            const float c = scaled(in.data() + g.pay + k);
+            std::memcpy(&packed[k], &c, 4);
+          }
+          PutBytesField(1, packed, &mesh);
+        } else if (g.number == 1 && g.wire_type == 5) {
+          const float c = scaled(in.data() + g.pay);
+          PutTag(1, 5, &mesh);
+          mesh.append(reinterpret_cast<const char*>(&c), 4);
+        } else {
+          mesh.append(in, g.begin, m - g.begin);
+        }
+      }
+      PutBytesField(11, mesh, &out);
+      continue;
+    }
+    out.append(in, f.begin, at - f.begin);
+  }
+  if (!size_written) return false;
+  wire->swap(out);
+  return true;
+}
+
+bool PrepareDescForWriting(const SegmentationWriterUnitOptions& options, int original_width, int original_height,
+                           std::string* wire) {
+  SegmentationDesc desc;
+  desc.wire = *wire;
+  int width = 0, height = 0;
+  const bool sized = desc.FrameSize(&width, &height);
+  const bool mesh = HasVectorMesh(*wire);
+  if (original_width > 0 && original_height > 0 && sized && (original_width != width || original_height != height)) {
+    if (!mesh) {
+      std::fprintf(stderr, "WARNING: Downscale requested but vector mesh is not present.\n");
+      return true;
+    }
+    if (!options.remove_rasterization) {
+      std::fprintf(stderr, "ERROR: a scaled desc has to be re-rasterized; write it with remove_rasterization\n");
+      return false;
+    }
+    return ScaleVectorization(original_width, original_height, wire) && RemoveRasterization(wire);
+  }
+  if (mesh && options.remove_rasterization) return RemoveRasterization(wire);
+  return true;
+}
 
 namespace {
 // Little-endian POD records, appended to a byte string that goes out in one write per section.
@@ -75,9 +265,15 @@ void SegmentationWriter::WriteTermHeaderAndClose() {
 }
 
 bool SegmentationWriterUnit::OpenStreams(StreamSet* set) {
-  if (!options_.video_stream_name.empty() && FindStreamIdx(options_.video_stream_name, set) < 0) {
-    std::fprintf(stderr, "ERROR: Could not find Video stream!\n");
-    return false;
+  if (!options_.video_stream_name.empty()) {
+    const int video_stream_idx = FindStreamIdx(options_.video_stream_name, set);
+    if (video_stream_idx < 0) {
+      std::fprintf(stderr, "ERROR: Could not find Video stream!\n");
+      return false;
+    }
+    const VideoStream& vid_stream = set->at(video_stream_idx)->As<VideoStream>();
+    original_width_ = vid_stream.original_width();
+    original_height_ = vid_stream.original_height();
   }
   seg_stream_idx_ = FindStreamIdx(options_.segment_stream_name, set);
   if (seg_stream_idx_ < 0) {
@@ -91,7 +287,10 @@ bool SegmentationWriterUnit::OpenStreams(StreamSet* set) {
 void SegmentationWriterUnit::ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) {
   const PointerFrame<SegmentationDesc>& seg_frame =
       input->at(seg_stream_idx_)->As<PointerFrame<SegmentationDesc>>();
-  writer_.AddSegmentationDataToChunk(seg_frame.Ref().wire, seg_frame.pts());
+  std::string wire = seg_frame.Ref().wire;   // a local copy, as the reference makes one
+  VF_CHECK(PrepareDescForWriting(options_, original_width_, original_height_, &wire),
+           "SegmentationWriterUnit: the desc cannot be written as asked");
+  writer_.AddSegmentationDataToChunk(wire, seg_frame.pts());
   output->push_back(input);
   ++frame_number_;
 }

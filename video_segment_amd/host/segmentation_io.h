@@ -69,11 +69,33 @@ class SegmentationReader {
   int curr_frame_ = 0;
 };
 
+// The writer's edits of a desc, done on the serialized message (segment_util/segmentation_util.cpp).
+// Each returns false on a malformed message and leaves *wire alone then.
+//   HasVectorMesh        desc.has_vector_mesh()
+//   RemoveRasterization  :1269-1275: clears every Region2D.raster (field 3), sets
+//                        rasterization_removed (field 13)
+//   ScaleVectorization   :1248-1267: frame_width / frame_height := width, height; every
+//                        vector_mesh.coord scaled in f32 and clamped, x and y by the list's parity
+bool HasVectorMesh(const std::string& wire);
+bool RemoveRasterization(std::string* wire);
+bool ScaleVectorization(int width, int height, std::string* wire);
+
 struct SegmentationWriterUnitOptions {
   std::string video_stream_name = "VideoStream";
   std::string segment_stream_name = "SegmentationStream";
   std::string filename;
+  // Write vector-only descs, as seg_tree_sample --write_to_file does (seg_tree.cpp:308).  Off by
+  // default: the bytes written are then the bytes the stream carries.
+  bool remove_rasterization = false;
 };
+
+// What SegmentationWriterUnit::ProcessFrame does to a desc before it is written
+// (segmentation_unit.cpp:379-395) for a video of original_width x original_height.  False where the
+// reference would re-rasterize a scaled desc on the host (remove_rasterization off, sizes differ, a
+// mesh present): this host layer has no scan conversion of its own (libvsg_render.so has:
+// vsg_render_rasterize).
+bool PrepareDescForWriting(const SegmentationWriterUnitOptions& options, int original_width, int original_height,
+                           std::string* wire);
 
 // Like the reference's unit, frames are only buffered while streaming and the whole video is
 // written as ONE chunk when the stream ends.
@@ -90,6 +112,7 @@ class SegmentationWriterUnit : public VideoUnit {
   SegmentationWriter writer_;
   int seg_stream_idx_ = -1;
   int frame_number_ = 0;
+  int original_width_ = 0, original_height_ = 0;   // 0: no video stream, nothing to scale to
 };
 
 struct SegmentationReaderUnitOptions {

@@ -156,11 +156,20 @@ class VideoStream : public DataStream {
   int width_step() const { return width_step_; }
   float fps() const { return fps_; }
   VideoPixelFormat pixel_format() const { return pixel_format_; }
+  // The size of the video before a reader downscaled it (video_unit.h: original_width / _height);
+  // the frame size unless a source says otherwise.
+  int original_width() const { return original_width_ > 0 ? original_width_ : frame_width_; }
+  int original_height() const { return original_height_ > 0 ? original_height_ : frame_height_; }
+  void set_original_size(int width, int height) {
+    original_width_ = width;
+    original_height_ = height;
+  }
 
  private:
   int frame_width_, frame_height_, width_step_;
   float fps_;
   VideoPixelFormat pixel_format_;
+  int original_width_ = 0, original_height_ = 0;
 };
 
 class DenseFlowStream : public DataStream {

@@ -44,11 +44,22 @@ class VsgRenderStats(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+class VsgRenderVectorStats(C.Structure):
+    _fields_ = [
+        ("lines", C.c_int64), ("crossings", C.c_int64), ("groups", C.c_int64), ("largest_group", C.c_int64),
+        ("walk_us", C.c_float), ("sort_us", C.c_float), ("pairs_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 # Every symbol include/vsg_render.h declares.
 EXPORTED_SYMBOLS = [
     "vsg_render_last_error", "vsg_render_default_options", "vsg_render_create", "vsg_render_destroy",
     "vsg_render_frame", "vsg_render_id_image", "vsg_render_level", "vsg_render_default_stride",
-    "vsg_render_last_stats", "vsg_render_color",
+    "vsg_render_last_stats", "vsg_render_color", "vsg_render_rasterize", "vsg_render_last_vector_stats",
 ]
 
 
@@ -88,6 +99,8 @@ def lib():
     L.vsg_render_last_stats.argtypes = [vp, C.POINTER(VsgRenderStats)]
     L.vsg_render_color.argtypes = [C.c_int, C.POINTER(C.c_uint8 * 3)]
     L.vsg_render_color.restype = None
+    L.vsg_render_rasterize.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_vector_stats.argtypes = [vp, C.POINTER(VsgRenderVectorStats)]
     _handle = L
     return L
 
@@ -222,6 +235,42 @@ class SegmentationRenderer:
         seg_bytes = bytes(seg_bytes)
         check(lib().vsg_render_id_image(self.h, seg_bytes, len(seg_bytes), int(level), p, mem))
         return out
+
+    def rasterize(self, seg_bytes, out=None):
+        """The scan intervals of a desc's vectorization at the renderer's frame size (the reference's
+        ReplaceRasterizationFromVectorization): an (n, 4) int32 array of {y, left_x, right_x,
+        region id} in the reference's order, its empty intervals included.  out: a contiguous
+        (capacity, 4) int32 numpy array or torch CUDA tensor to fill instead; the first n rows of it
+        are returned."""
+        seg_bytes = bytes(seg_bytes)
+        n = C.c_size_t()
+        if out is None:
+            # the count first (host work only, done again by the call below), then a buffer of that size
+            check(lib().vsg_render_rasterize(self.h, seg_bytes, len(seg_bytes), None, 0, C.byref(n), VSG_MEM_HOST))
+            out = np.empty((n.value, 4), np.int32)
+            if n.value == 0:
+                return out
+        if len(out.shape) != 2 or out.shape[1] != 4 or str(out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("out has to be (capacity, 4) int32")
+        if _is_torch(out):
+            if not out.is_contiguous():
+                raise ValueError("out has to be contiguous")
+            p, mem = C.c_void_p(out.data_ptr()), VSG_MEM_DEVICE if out.is_cuda else VSG_MEM_HOST
+            if out.is_cuda:
+                import torch
+                torch.cuda.current_stream(out.device).synchronize()
+        else:
+            if not out.flags["C_CONTIGUOUS"]:
+                raise ValueError("out has to be C-contiguous")
+            p, mem = out.ctypes.data_as(C.c_void_p), VSG_MEM_HOST
+        check(lib().vsg_render_rasterize(self.h, seg_bytes, len(seg_bytes), p, out.shape[0], C.byref(n), mem))
+        return out[:n.value]
+
+    def last_vector_stats(self):
+        """vsg_render_last_vector_stats of the last call, as a dict."""
+        s = VsgRenderVectorStats()
+        check(lib().vsg_render_last_vector_stats(self.h, C.byref(s)))
+        return s.as_dict()
 
     def last_stats(self):
         """vsg_render_last_stats of the last render / id_image call, as a dict."""

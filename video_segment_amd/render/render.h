@@ -33,6 +33,46 @@ void LaunchCompose(const uint32_t* plane, int pitch, int width, int height, cons
                    size_t src_stride, uint8_t* out, size_t out_stride, int highlight_edges, int mode,
                    float alpha, hipStream_t stream);
 
+// ---- vector path (vector.hip): scan intervals from polygon lines ------------------------------------
+
+// One kept polygon line (|dy| >= 1e-3f), points ordered by y: what the reference's EdgeEntry holds,
+// the row it is inserted at, and where its crossings go.  Built and checked by the host: y0 >= 0,
+// y_max <= H, and [offset, offset + count) is this line's own slice of the crossing arrays.
+struct VecLine {
+  int32_t region;    // index of the Region2D in the desc
+  int32_t y0;        // (int)p1.y, the row of insertion
+  float x;           // p1.x
+  float y_max;       // p2.y
+  float dx;          // (p2.x - p1.x) / (p2.y - p1.y)
+  int32_t is_left;   // 0 when the points were swapped
+  uint32_t offset;   // prefix sum of count
+  uint32_t count;    // rows y0, y0 + 1, ... with !(y_max < y + 1)
+};
+static_assert(sizeof(VecLine) == 32, "uploaded as is");
+
+constexpr int kVecRowBits = 16;   // sort key = region index << 16 | row; frames have at most 2^15 rows
+
+enum VecFlag { VEC_FLAG_UNSPECIFIED = 1, VEC_FLAG_INTERNAL = 2 };
+
+// Written by the vector kernels, read once by the host at the end of a call.
+struct VecStatus {
+  uint32_t flags, pad;
+  unsigned long long groups, largest_group;
+};
+
+void LaunchVecWalk(const VecLine* lines, int n_lines, unsigned long long* keys, unsigned long long* vals,
+                   VecStatus* status, hipStream_t stream);
+// The library radix sort on bits [0, end_bit) of the keys.
+size_t VecSortTempBytes(int64_t n, int end_bit);
+hipError_t VecSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                   const unsigned long long* vals_in, unsigned long long* vals_out, int64_t n, int end_bit,
+                   hipStream_t stream);
+// n sorted crossings (n even) -> n / 2 intervals, dense, in region / row / left-to-right order.
+// `intervals` has to be cleared to zero before.  value = region_value[region index].
+void LaunchVecPairs(const unsigned long long* keys, const unsigned long long* vals, const VecLine* lines,
+                    uint32_t n_lines, const uint32_t* region_value, uint32_t n_regions, int64_t n, int width,
+                    int height, Interval* intervals, VecStatus* status, hipStream_t stream);
+
 }  // namespace vsg_render_impl
 
 #endif  // VSG_RENDER_RENDER_H_

@@ -18,6 +18,8 @@
 namespace {
 
 using vsg_render_impl::Interval;
+using vsg_render_impl::VecLine;
+using vsg_render_impl::VecStatus;
 
 struct Error : std::runtime_error {
   int code;
@@ -164,12 +166,107 @@ struct ParsedDesc {
   std::vector<int32_t> region_ids;
   std::vector<size_t> region_begin;   // region_ids.size() + 1 entries
   Hierarchy hierarchy;
+  // the vector form: Region2D.vectorization.polygon.coord_idx of all regions back to back,
+  // vector_mesh.coord, rasterization_removed
+  int frame_w = 0, frame_h = 0;
+  bool has_mesh = false, rasterization_removed = false;
+  std::vector<float> mesh;
+  std::vector<int32_t> coord_idx;
+  std::vector<size_t> poly_begin;          // polygons + 1 entries into coord_idx
+  std::vector<size_t> region_poly_begin;   // region_ids.size() + 1 entries into poly_begin
 };
 
-void ParseDesc(const uint8_t* seg, size_t len, int W, int H, ParsedDesc* d, std::vector<Interval>* intervals) {
+// repeated int32, packed or not
+void ReadInt32s(int wt, Cursor sub, uint64_t v, std::vector<int32_t>* out) {
+  if (wt == 0) {
+    out->push_back((int32_t)(int64_t)v);
+  } else if (wt == 2) {
+    while (sub.p < sub.end && sub.ok) out->push_back((int32_t)(int64_t)sub.Varint());
+    if (!sub.ok) Throw(VSG_ERR_INVALID, "malformed packed int32");
+  }
+}
+
+// Region2D.vectorization: polygon{coord_idx = 1, hole = 2}.  A hole is a polygon like any other to
+// the scan conversion (its lines run the other way round), so the flag is read past.
+void ParseVectorization(Cursor vec, ParsedDesc* d) {
+  int f, wt;
+  uint64_t v;
+  Cursor poly{nullptr, nullptr}, sub{nullptr, nullptr};
+  while (vec.Next(&f, &wt, &poly, &v)) {
+    if (f != 1 || wt != 2) continue;   // Vectorization.polygon
+    while (poly.Next(&f, &wt, &sub, &v)) {
+      if (f == 1) ReadInt32s(wt, sub, v, &d->coord_idx);   // Polygon.coord_idx
+    }
+    if (!poly.ok) Throw(VSG_ERR_INVALID, "malformed Polygon");
+    d->poly_begin.push_back(d->coord_idx.size());
+  }
+  if (!vec.ok) Throw(VSG_ERR_INVALID, "malformed Vectorization");
+}
+
+// VectorMesh.coord: repeated float, packed or not.
+void ParseMesh(Cursor mesh, std::vector<float>* out) {
+  while (mesh.p < mesh.end) {
+    const uint64_t tag = mesh.Varint();
+    if (!mesh.ok) break;
+    const int f = (int)(tag >> 3), wt = (int)(tag & 7);
+    const uint8_t* from = nullptr;
+    size_t count = 0;
+    if (wt == 5) {
+      if (mesh.end - mesh.p < 4) Throw(VSG_ERR_INVALID, "malformed VectorMesh");
+      from = mesh.p;
+      count = 1;
+      mesh.p += 4;
+    } else if (wt == 2) {
+      const uint64_t n = mesh.Varint();
+      if (!mesh.ok || n > (uint64_t)(mesh.end - mesh.p)) Throw(VSG_ERR_INVALID, "malformed VectorMesh");
+      if (f == 1 && n % 4) Throw(VSG_ERR_INVALID, "packed VectorMesh.coord is not a whole number of floats");
+      from = mesh.p;
+      count = n / 4;
+      mesh.p += n;
+    } else if (wt == 0) {
+      (void)mesh.Varint();
+    } else if (wt == 1) {
+      if (mesh.end - mesh.p < 8) Throw(VSG_ERR_INVALID, "malformed VectorMesh");
+      mesh.p += 8;
+    } else {
+      Throw(VSG_ERR_INVALID, "malformed VectorMesh");
+    }
+    if (f == 1 && from) {
+      const size_t at = out->size();
+      out->resize(at + count);
+      std::memcpy(out->data() + at, from, count * 4);   // little-endian IEEE floats on the wire
+    }
+  }
+  if (!mesh.ok) Throw(VSG_ERR_INVALID, "malformed VectorMesh");
+}
+
+// Whether the desc is rendered from its vectorization: rasterization_removed (13) is set and there
+// is a vector_mesh (11).  Looks at top-level fields only.
+bool IsVectorOnly(const uint8_t* seg, size_t len) {
+  Cursor top{seg, seg + len};
+  int f, wt;
+  uint64_t v;
+  Cursor sub{nullptr, nullptr};
+  bool removed = false, mesh = false;
+  while (top.Next(&f, &wt, &sub, &v)) {
+    if (f == 13 && wt == 0) removed = v != 0;
+    if (f == 11 && wt == 2) mesh = true;
+  }
+  return removed && mesh;
+}
+
+// vector: read the vectorizations and the mesh instead of the rasters; the desc's frame size may
+// then differ from W x H (the caller scales the mesh).
+void ParseDesc(const uint8_t* seg, size_t len, int W, int H, bool vector, ParsedDesc* d,
+               std::vector<Interval>* intervals) {
   d->region_ids.clear();
   d->region_begin.clear();
   d->hierarchy.clear();
+  d->has_mesh = d->rasterization_removed = false;
+  d->mesh.clear();
+  d->coord_idx.clear();
+  d->poly_begin.assign(1, 0);
+  d->region_poly_begin.clear();
   intervals->clear();
   Cursor top{seg, seg + len};
   int f, wt;
@@ -179,18 +276,25 @@ void ParseDesc(const uint8_t* seg, size_t len, int W, int H, ParsedDesc* d, std:
   while (top.Next(&f, &wt, &sub, &v)) {
     if (f == 4 && wt == 0) frame_w = (int)(int64_t)v;
     if (f == 5 && wt == 0) frame_h = (int)(int64_t)v;
+    if (f == 13 && wt == 0) d->rasterization_removed = v != 0;
+    if (f == 11 && wt == 2) {   // SegmentationDesc.vector_mesh
+      d->has_mesh = true;
+      if (vector) ParseMesh(sub, &d->mesh);
+    }
     if (f == 2 && wt == 2) {   // SegmentationDesc.region
       int id = -1;
       Cursor region = sub, raster{nullptr, nullptr}, rsub{nullptr, nullptr};
       bool has_raster = false;
+      d->region_poly_begin.push_back(d->poly_begin.size() - 1);
       while (region.Next(&f, &wt, &rsub, &v)) {
         if (f == 1 && wt == 0) id = (int)(int64_t)v;                      // Region2D.id
         if (f == 3 && wt == 2) { raster = rsub; has_raster = true; }      // Region2D.raster
+        if (f == 6 && wt == 2 && vector) ParseVectorization(rsub, d);     // Region2D.vectorization
       }
       if (!region.ok) Throw(VSG_ERR_INVALID, "malformed Region2D");
       d->region_ids.push_back(id);
       d->region_begin.push_back(intervals->size());
-      if (!has_raster) continue;
+      if (!has_raster || vector) continue;
       Cursor scan{nullptr, nullptr}, none{nullptr, nullptr};
       while (raster.Next(&f, &wt, &scan, &v)) {
         if (f != 1 || wt != 2) continue;   // Rasterization.scan_inter
@@ -233,6 +337,10 @@ void ParseDesc(const uint8_t* seg, size_t len, int W, int H, ParsedDesc* d, std:
   }
   if (!top.ok) Throw(VSG_ERR_INVALID, "malformed SegmentationDesc");
   d->region_begin.push_back(intervals->size());
+  d->region_poly_begin.push_back(d->poly_begin.size() - 1);
+  d->frame_w = frame_w;
+  d->frame_h = frame_h;
+  if (vector) return;
   if ((frame_w && frame_w != W) || (frame_h && frame_h != H)) {
     Throw(VSG_ERR_INVALID, "SegmentationDesc is " + std::to_string(frame_w) + "x" + std::to_string(frame_h) +
                                ", the handle " + std::to_string(W) + "x" + std::to_string(H));
@@ -293,13 +401,27 @@ struct vsg_render {
   std::vector<Interval> intervals;
   std::unordered_map<int32_t, uint32_t> colors;   // mapped id -> packed colour (a pure function)
   Block d_intervals, h_intervals, d_plane, d_src, d_out, d_ids;
+  // the vector path: lines and per-region values (host, then one upload), crossings (two key and two
+  // value arrays for the sort), the sort's work space, the status words
+  std::vector<VecLine> lines;
+  std::vector<uint32_t> region_value;
+  std::vector<float> scaled_mesh;
+  Block d_vec_in, d_cross, d_sort_temp, d_status, h_status;
+  hipEvent_t vev[4] = {nullptr, nullptr, nullptr, nullptr};
   int64_t allocations = 0;
   vsg_render_stats stats;
+  vsg_render_vector_stats vstats;
 
   ~vsg_render() {
     if (stream) (void)hipStreamSynchronize(stream);
-    for (Block* b : {&d_intervals, &h_intervals, &d_plane, &d_src, &d_out, &d_ids}) b->Release();
+    for (Block* b : {&d_intervals, &h_intervals, &d_plane, &d_src, &d_out, &d_ids, &d_vec_in, &d_cross, &d_sort_temp,
+                     &d_status, &h_status}) {
+      b->Release();
+    }
     for (hipEvent_t e : ev) {
+      if (e) (void)hipEventDestroy(e);
+    }
+    for (hipEvent_t e : vev) {
       if (e) (void)hipEventDestroy(e);
     }
     if (stream) (void)hipStreamDestroy(stream);
@@ -328,6 +450,142 @@ struct vsg_render {
     stats.compose_us = ms * 1000.0f;
     stats.device_allocations = allocations;
   }
+
+  // ---- vector path ----
+  // Scales the mesh where the desc's frame size is not the handle's (ScaleVectorization,
+  // segmentation_util.cpp:1248-1267), then one VecLine per kept polygon line (:1159-1189) with its
+  // crossing count and the prefix sum.  Returns the number of crossings.
+  int64_t BuildLines() {
+    const ParsedDesc& d = desc;
+    const float* coord = d.mesh.data();
+    const size_t n_coord = d.mesh.size();
+    if (d.frame_w > 0 && d.frame_h > 0 && (d.frame_w != W || d.frame_h != H)) {
+      const float scale_x = (float)W * (1.0f / (float)d.frame_w);
+      const float scale_y = (float)H * (1.0f / (float)d.frame_h);
+      scaled_mesh.resize(n_coord);
+      for (size_t k = 0; k < n_coord; ++k) {
+        scaled_mesh[k] = k % 2 == 0 ? std::min<float>((float)W, d.mesh[k] * scale_x)
+                                    : std::min<float>((float)H, d.mesh[k] * scale_y);
+      }
+      coord = scaled_mesh.data();
+    }
+    lines.clear();
+    uint64_t total = 0;
+    for (size_t r = 0; r < d.region_ids.size(); ++r) {
+      for (size_t p = d.region_poly_begin[r]; p < d.region_poly_begin[r + 1]; ++p) {
+        for (size_t c = d.poly_begin[p] + 1; c < d.poly_begin[p + 1]; ++c) {
+          const int32_t i1 = d.coord_idx[c - 1], i2 = d.coord_idx[c];
+          if (i1 < 0 || i2 < 0 || (size_t)i1 + 1 >= n_coord || (size_t)i2 + 1 >= n_coord) {
+            Throw(VSG_ERR_INVALID, "coord_idx outside the vector mesh");
+          }
+          float x1 = coord[i1], y1 = coord[i1 + 1], x2 = coord[i2], y2 = coord[i2 + 1];
+          // bounds the accumulated x of every row far inside f32's range
+          if (!(std::fabs(x1) <= 16777216.0f && std::fabs(x2) <= 16777216.0f && std::isfinite(y1) &&
+                std::isfinite(y2))) {
+            Throw(VSG_ERR_INVALID, "vector mesh coordinate is not a usable number");
+          }
+          if (std::fabs(y1 - y2) < 1e-3f) continue;   // horizontal, :1168
+          VecLine l;
+          l.is_left = 1;
+          if (y2 < y1) {
+            std::swap(x1, x2);
+            std::swap(y1, y2);
+            l.is_left = 0;
+          }
+          // the reference DCHECKs 0 <= p1.y <= frame_height; its edge_list has frame_height + 1 rows
+          if (!(y1 >= 0.0f && y2 <= (float)H)) Throw(VSG_ERR_INVALID, "polygon line outside the frame's rows");
+          l.region = (int32_t)r;
+          l.y0 = (int)y1;
+          l.x = x1;
+          l.y_max = y2;
+          l.dx = (x2 - x1) / (y2 - y1);
+          // active in rows y0, y0 + 1, ... while !(y_max < y + 1): that is floor(y_max) - y0 rows
+          const int rows = (int)std::floor(y2) - l.y0;
+          l.count = (uint32_t)std::max(rows, 0);
+          l.offset = (uint32_t)total;
+          total += l.count;
+          if (total > (1ull << 31)) Throw(VSG_ERR_INVALID, "more than 2^31 edge crossings in one frame");
+          lines.push_back(l);
+        }
+      }
+    }
+    if (lines.size() > (1u << 30) || d.region_ids.size() > (1u << 30)) {
+      Throw(VSG_ERR_INVALID, "too many polygon lines or regions");
+    }
+    // an odd total has an odd row somewhere: the reference reads past its active edge list there
+    if (total & 1) Throw(VSG_ERR_INVALID, "odd number of edge crossings: a polygon is not closed");
+    return (int64_t)total;
+  }
+
+  // Uploads lines and region values, then walk -> sort -> pairs on the stream.  Leaves n_cross / 2
+  // intervals in d_intervals.  CheckVector has to be called after the stream has drained.
+  void RunVector(int64_t n_cross) {
+    using namespace vsg_render_impl;
+    std::memset(&vstats, 0, sizeof(vstats));
+    vstats.lines = (int64_t)lines.size();
+    vstats.crossings = n_cross;
+    if (n_cross == 0) return;
+    const size_t n = (size_t)n_cross;
+    const size_t lines_bytes = lines.size() * sizeof(VecLine);
+    const size_t values_bytes = region_value.size() * sizeof(uint32_t);
+    int region_bits = 1;
+    while (region_bits < 31 && (region_value.size() >> region_bits)) ++region_bits;
+    const int end_bit = kVecRowBits + region_bits;
+    const size_t temp_bytes = std::max<size_t>(VecSortTempBytes(n_cross, end_bit), 16);
+    h_intervals.Reserve(lines_bytes + values_bytes, &allocations);
+    d_vec_in.Reserve(lines_bytes + values_bytes, &allocations);
+    d_cross.Reserve(4 * n * sizeof(unsigned long long), &allocations);
+    d_sort_temp.Reserve(temp_bytes, &allocations);
+    d_intervals.Reserve(n / 2 * sizeof(Interval), &allocations);
+    d_status.Reserve(sizeof(VecStatus), &allocations);
+    h_status.Reserve(sizeof(VecStatus), &allocations);
+    std::memcpy(h_intervals.p, lines.data(), lines_bytes);
+    std::memcpy(static_cast<char*>(h_intervals.p) + lines_bytes, region_value.data(), values_bytes);
+    RENDER_HIP(hipMemcpyAsync(d_vec_in.p, h_intervals.p, lines_bytes + values_bytes, hipMemcpyHostToDevice, stream));
+    const VecLine* d_lines = static_cast<const VecLine*>(d_vec_in.p);
+    const uint32_t* d_values = reinterpret_cast<const uint32_t*>(static_cast<const char*>(d_vec_in.p) + lines_bytes);
+    unsigned long long* keys = static_cast<unsigned long long*>(d_cross.p);
+    unsigned long long* vals = keys + n;
+    unsigned long long* keys_sorted = keys + 2 * n;
+    unsigned long long* vals_sorted = keys + 3 * n;
+    VecStatus* status = static_cast<VecStatus*>(d_status.p);
+    RENDER_HIP(hipMemsetAsync(status, 0, sizeof(VecStatus), stream));
+    // every entry of the list is in the frame whatever the pairs stage leaves unwritten on bad input
+    RENDER_HIP(hipMemsetAsync(d_intervals.p, 0, n / 2 * sizeof(Interval), stream));
+    RENDER_HIP(hipEventRecord(vev[0], stream));
+    LaunchVecWalk(d_lines, (int)lines.size(), keys, vals, status, stream);
+    RENDER_HIP(hipEventRecord(vev[1], stream));
+    RENDER_HIP(VecSort(d_sort_temp.p, temp_bytes, keys, keys_sorted, vals, vals_sorted, n_cross, end_bit, stream));
+    RENDER_HIP(hipEventRecord(vev[2], stream));
+    LaunchVecPairs(keys_sorted, vals_sorted, d_lines, (uint32_t)lines.size(), d_values,
+                   (uint32_t)region_value.size(), n_cross, W, H, static_cast<Interval*>(d_intervals.p), status, stream);
+    RENDER_HIP(hipGetLastError());
+    RENDER_HIP(hipEventRecord(vev[3], stream));
+    RENDER_HIP(hipMemcpyAsync(h_status.p, status, sizeof(VecStatus), hipMemcpyDeviceToHost, stream));
+    vstats.launches = 7;   // upload, two clears, walk, the sort counted as one, pairs, status
+    stats.launches += vstats.launches;
+  }
+
+  // After the call's one synchronisation: stage times, group statistics, the device flag.
+  void CheckVector() {
+    if (vstats.crossings == 0) return;
+    float ms = 0;
+    RENDER_HIP(hipEventElapsedTime(&ms, vev[0], vev[1]));
+    vstats.walk_us = ms * 1000.0f;
+    RENDER_HIP(hipEventElapsedTime(&ms, vev[1], vev[2]));
+    vstats.sort_us = ms * 1000.0f;
+    RENDER_HIP(hipEventElapsedTime(&ms, vev[2], vev[3]));
+    vstats.pairs_us = ms * 1000.0f;
+    const VecStatus* st = static_cast<const VecStatus*>(h_status.p);
+    vstats.groups = (int64_t)st->groups;
+    vstats.largest_group = (int64_t)st->largest_group;
+    if (st->flags & vsg_render_impl::VEC_FLAG_INTERNAL) Throw(VSG_ERR_INTERNAL, "the edge walk and the host's row counts disagree");
+    if (st->flags & vsg_render_impl::VEC_FLAG_UNSPECIFIED) {
+      Throw(VSG_ERR_INVALID,
+            "the vectorization has a row the reference does not define: an odd number of active edges, edges "
+            "it cannot order, or an interval outside the frame");
+    }
+  }
 };
 
 namespace {
@@ -338,9 +596,10 @@ void CheckMem(int mem, const char* what) {
 
 // Parses the desc, applies the hierarchy bookkeeping both entry points share (a desc that carries a
 // hierarchy replaces the kept one) and returns the hierarchy to map ids with.
-const Hierarchy& Ingest(vsg_render* h, const uint8_t* seg, size_t seg_len) {
+const Hierarchy& Ingest(vsg_render* h, const uint8_t* seg, size_t seg_len, bool* vector) {
   if (!seg && seg_len) Throw(VSG_ERR_INVALID, "seg is null");
-  ParseDesc(seg, seg_len, h->W, h->H, &h->desc, &h->intervals);
+  *vector = IsVectorOnly(seg, seg_len);
+  ParseDesc(seg, seg_len, h->W, h->H, *vector, &h->desc, &h->intervals);
   if (!h->desc.hierarchy.empty()) h->kept = h->desc.hierarchy;
   return h->kept;
 }
@@ -356,6 +615,22 @@ int64_t AssignValues(vsg_render* h, int level, const Hierarchy& hier, ValueOf va
     auto it = seen.find(mapped);
     if (it == seen.end()) it = seen.emplace(mapped, value_of(mapped)).first;
     for (size_t k = d.region_begin[r]; k < d.region_begin[r + 1]; ++k) h->intervals[k].value = it->second;
+  }
+  return (int64_t)seen.size();
+}
+
+// The same for a vector-only desc: one value per region that has a polygon, in h->region_value.
+template <class ValueOf>
+int64_t AssignRegionValues(vsg_render* h, int level, const Hierarchy& hier, ValueOf value_of) {
+  std::unordered_map<int32_t, uint32_t> seen;
+  const ParsedDesc& d = h->desc;
+  h->region_value.assign(d.region_ids.size(), 0u);
+  for (size_t r = 0; r < d.region_ids.size(); ++r) {
+    if (d.region_poly_begin[r] == d.region_poly_begin[r + 1]) continue;
+    const int mapped = level > 0 ? ParentId(d.region_ids[r], level, hier) : d.region_ids[r];
+    auto it = seen.find(mapped);
+    if (it == seen.end()) it = seen.emplace(mapped, value_of(mapped)).first;
+    h->region_value[r] = it->second;
   }
   return (int64_t)seen.size();
 }
@@ -412,11 +687,14 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->pitch = vsg_render_impl::PlanePitch(width);
     std::memset(&h->stats, 0, sizeof(h->stats));
     h->h_intervals.pinned = true;
+    h->h_status.pinned = true;
+    std::memset(&h->vstats, 0, sizeof(h->vstats));
     if (opt.device >= 0) h->device = opt.device;
     else RENDER_HIP(hipGetDevice(&h->device));
     DeviceGuard guard(h->device);
     RENDER_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     for (hipEvent_t& ev : h->ev) RENDER_HIP(hipEventCreate(&ev));
+    for (hipEvent_t& ev : h->vev) RENDER_HIP(hipEventCreate(&ev));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -448,10 +726,12 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
     const int out_rows = h->opt.concat_with_source ? 2 * H : H;
     DeviceGuard guard(h->device);
     std::memset(&h->stats, 0, sizeof(h->stats));
+    std::memset(&h->vstats, 0, sizeof(h->vstats));
 
     // ---- host: decode, hierarchy state (segmentation_unit.cpp:567-591), colour table ----
     const double t0 = NowMs();
-    const Hierarchy& hier = Ingest(h, seg, seg_len);
+    bool vector = false;
+    const Hierarchy& hier = Ingest(h, seg, seg_len, &vector);
     if (!h->level_resolved) {
       const int size = (int)h->desc.hierarchy.size();   // the first frame's own hierarchy
       float lvl = h->opt.hierarchy_level;
@@ -464,7 +744,7 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
     if (level > 0 && hier.empty()) level = 0;
     if (!hier.empty() && level >= (int)hier.size()) level = (int)hier.size() - 1;
     if (h->colors.size() > (1u << 20)) h->colors.clear();
-    h->stats.distinct_ids = AssignValues(h, level, hier, [&](int mapped) {
+    auto color_of = [&](int mapped) {
       auto it = h->colors.find(mapped);
       if (it == h->colors.end()) {
         uint8_t c[3];
@@ -472,13 +752,22 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
         it = h->colors.emplace(mapped, (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16).first;
       }
       return it->second;
-    });
-    h->stats.intervals = (int64_t)h->intervals.size();
+    };
+    int64_t n_cross = 0;
+    if (vector) {
+      h->stats.distinct_ids = AssignRegionValues(h, level, hier, color_of);
+      n_cross = h->BuildLines();
+    } else {
+      h->stats.distinct_ids = AssignValues(h, level, hier, color_of);
+    }
+    const int64_t n_intervals = vector ? n_cross / 2 : (int64_t)h->intervals.size();
+    h->stats.intervals = n_intervals;
     const double t1 = NowMs();
     h->stats.decode_ms = t1 - t0;
 
-    // ---- uploads ----
-    h->UploadIntervals();
+    // ---- uploads (and, for a vector-only desc, the scan conversion that makes the list) ----
+    if (vector) h->RunVector(n_cross);
+    else h->UploadIntervals();
     const uint8_t* src = nullptr;
     size_t src_stride = 0;
     if (video) {
@@ -508,8 +797,8 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
     RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
     RENDER_HIP(hipMemsetAsync(plane, 0, (size_t)h->pitch * H * sizeof(uint32_t), h->stream));
     RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
-    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), (int64_t)h->intervals.size(), plane,
-                                h->pitch, h->stream);
+    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, plane, h->pitch,
+                                h->stream);
     RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
     const int mode = h->opt.concat_with_source ? vsg_render_impl::COMPOSE_CONCAT
                      : video                   ? vsg_render_impl::COMPOSE_BLEND
@@ -518,13 +807,14 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
                                    mode, h->opt.blend_alpha, h->stream);
     RENDER_HIP(hipGetLastError());
     RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
-    h->stats.launches += 2 + (h->intervals.empty() ? 0 : 1);
+    h->stats.launches += 2 + (n_intervals == 0 ? 0 : 1);
     if (mem_out == VSG_MEM_HOST) {
       RENDER_HIP(hipMemcpy2DAsync(out, out_stride, dst, dst_stride, row_bytes, out_rows, hipMemcpyDeviceToHost,
                                   h->stream));
       ++h->stats.launches;
     }
     h->FinishStats();
+    if (vector) h->CheckVector();
   });
 }
 
@@ -536,17 +826,28 @@ int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int l
     const int W = h->W, H = h->H;
     DeviceGuard guard(h->device);
     std::memset(&h->stats, 0, sizeof(h->stats));
+    std::memset(&h->vstats, 0, sizeof(h->vstats));
     const double t0 = NowMs();
-    const Hierarchy& hier = Ingest(h, seg, seg_len);
+    bool vector = false;
+    const Hierarchy& hier = Ingest(h, seg, seg_len, &vector);
     if (level < 0 || (level > 0 && level >= (int)hier.size())) {
       Throw(VSG_ERR_INVALID, "level " + std::to_string(level) + " is not in the hierarchy (" +
                                  std::to_string(hier.size()) + " levels)");
     }
-    h->stats.distinct_ids = AssignValues(h, level, hier, [](int mapped) { return (uint32_t)mapped; });
-    h->stats.intervals = (int64_t)h->intervals.size();
+    auto id_of = [](int mapped) { return (uint32_t)mapped; };
+    int64_t n_cross = 0;
+    if (vector) {
+      h->stats.distinct_ids = AssignRegionValues(h, level, hier, id_of);
+      n_cross = h->BuildLines();
+    } else {
+      h->stats.distinct_ids = AssignValues(h, level, hier, id_of);
+    }
+    const int64_t n_intervals = vector ? n_cross / 2 : (int64_t)h->intervals.size();
+    h->stats.intervals = n_intervals;
     const double t1 = NowMs();
     h->stats.decode_ms = t1 - t0;
-    h->UploadIntervals();
+    if (vector) h->RunVector(n_cross);
+    else h->UploadIntervals();
     const size_t bytes = (size_t)W * H * sizeof(int32_t);
     uint32_t* ids = reinterpret_cast<uint32_t*>(out);   // device output: painted in place
     if (mem_out == VSG_MEM_HOST) {
@@ -557,17 +858,66 @@ int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int l
     RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
     RENDER_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
     RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
-    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), (int64_t)h->intervals.size(), ids, W,
-                                h->stream);
+    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, W, h->stream);
     RENDER_HIP(hipGetLastError());
     RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
     RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
-    h->stats.launches += 1 + (h->intervals.empty() ? 0 : 1);
+    h->stats.launches += 1 + (n_intervals == 0 ? 0 : 1);
     if (mem_out == VSG_MEM_HOST) {
       RENDER_HIP(hipMemcpyAsync(out, ids, bytes, hipMemcpyDeviceToHost, h->stream));
       ++h->stats.launches;
     }
     h->FinishStats();
+    if (vector) h->CheckVector();
+  });
+}
+
+int vsg_render_rasterize(vsg_render* h, const uint8_t* seg, size_t seg_len, int32_t* out, size_t capacity_intervals,
+                         size_t* count, int mem_out) {
+  return Guard([&] {
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!count) Throw(VSG_ERR_INVALID, "count is null");
+    *count = 0;
+    CheckMem(mem_out, "out");
+    if (!seg && seg_len) Throw(VSG_ERR_INVALID, "seg is null");
+    DeviceGuard guard(h->device);
+    std::memset(&h->stats, 0, sizeof(h->stats));
+    std::memset(&h->vstats, 0, sizeof(h->vstats));
+    const double t0 = NowMs();
+    // the handle's kept hierarchy is left alone: this call renders nothing
+    ParseDesc(seg, seg_len, h->W, h->H, true, &h->desc, &h->intervals);
+    if (!h->desc.has_mesh) Throw(VSG_ERR_INVALID, "the SegmentationDesc has no vector_mesh");
+    h->region_value.assign(h->desc.region_ids.begin(), h->desc.region_ids.end());
+    const int64_t n_cross = h->BuildLines();
+    const size_t n = (size_t)(n_cross / 2);
+    h->stats.intervals = (int64_t)n;
+    h->stats.distinct_ids = (int64_t)h->desc.region_ids.size();
+    *count = n;
+    if (!out && capacity_intervals == 0) return;   // asked for the count only
+    if (n > capacity_intervals) {
+      Throw(VSG_ERR_INVALID, "capacity_intervals is " + std::to_string(capacity_intervals) + ", the frame has " +
+                                 std::to_string(n) + " intervals");
+    }
+    if (n && !out) Throw(VSG_ERR_INVALID, "out is null");
+    const double t1 = NowMs();
+    h->stats.decode_ms = t1 - t0;
+    h->RunVector(n_cross);
+    h->stats.upload_ms = NowMs() - t1;
+    if (n) {
+      RENDER_HIP(hipMemcpyAsync(out, h->d_intervals.p, n * sizeof(Interval),
+                                mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+      ++h->stats.launches;
+    }
+    RENDER_HIP(hipStreamSynchronize(h->stream));
+    h->stats.device_allocations = h->allocations;
+    h->CheckVector();
+  });
+}
+
+int vsg_render_last_vector_stats(vsg_render* h, vsg_render_vector_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->vstats;
   });
 }
 
