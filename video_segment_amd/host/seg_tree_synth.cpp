@@ -16,6 +16,12 @@
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
 // writer and given the same vector-only descs (at the stream's size), which is what a consumer of the
 // file renders.  --rewrite_pb FILE applies the writer's edit to a container (no GPU).
+//
+//   --downscale_min_size N
+// puts a DownscaleUnit (the reader's DOWNSCALE_TO_MIN_SIZE, seg_tree.cpp:136-139) directly behind the
+// source: everything after it sees the smaller frames, and the writer scales its vectorization back to
+// the source's size.  --run_on_server applies the overrides of seg_tree.cpp:90-98 that exist here:
+// use_pipeline on, write_to_file on, downscale_min_size 360, no render unit.
 #include <chrono>
 #include <cstdio>
 #include <cstdlib>
@@ -24,6 +30,8 @@
 #include <string>
 
 #include "dense_flow_unit.h"
+#include "../../include/vsg_resize.h"
+#include "downscale_unit.h"
 #include "flow_reader.h"
 #include "raw_video_reader.h"
 #include "segmentation_io.h"
@@ -47,9 +55,11 @@ class SyntheticVideoUnit : public VideoUnit {
  public:
   // kind: 0 probe, 1 bench, 2 soft (tests/synth.py: soft_frame, the input of the hierarchical stage)
   SyntheticVideoUnit(int width, int height, int frames, bool flow, int kind,
-                     const std::string& save_flow = std::string(), int original_width = 0, int original_height = 0)
+                     const std::string& save_flow = std::string(), int original_width = 0, int original_height = 0,
+                     int flow_width = 0, int flow_height = 0)
       : width_(width), height_(height), frames_(frames), flow_(flow), bench_(kind != 0), soft_(kind == 2),
-        save_flow_(save_flow), original_width_(original_width), original_height_(original_height) {}
+        save_flow_(save_flow), original_width_(original_width), original_height_(original_height),
+        flow_width_(flow_width > 0 ? flow_width : width), flow_height_(flow_height > 0 ? flow_height : height) {}
 
   bool OpenStreams(StreamSet* set) override {
     width_step_ = (width_ * 3 + 3) / 4 * 4;   // padded like video_reader_unit.cpp:200-206
@@ -59,11 +69,11 @@ class SyntheticVideoUnit : public VideoUnit {
     set->push_back(video);
     if (flow_) {
       set->push_back(std::shared_ptr<DataStream>(
-          new DenseFlowStream(width_, height_, "BackwardFlowStream")));
+          new DenseFlowStream(flow_width_, flow_height_, "BackwardFlowStream")));
     }
     if (!save_flow_.empty()) {   // what DenseFlowUnit does with --save_flow (flow_reader.cpp:240-248)
       flow_writer_.reset(new DenseFlowWriter(save_flow_));
-      if (!flow_writer_->OpenAndWriteHeader(width_, height_, FLOW_BACKWARD)) return false;
+      if (!flow_writer_->OpenAndWriteHeader(flow_width_, flow_height_, FLOW_BACKWARD)) return false;
     }
     return true;
   }
@@ -99,9 +109,9 @@ class SyntheticVideoUnit : public VideoUnit {
     }
     fs->push_back(vf);
     if (flow_ || flow_writer_) {
-      std::shared_ptr<DenseFlowFrame> ff(new DenseFlowFrame(width_, height_, true, vf->pts()));
+      std::shared_ptr<DenseFlowFrame> ff(new DenseFlowFrame(flow_width_, flow_height_, true, vf->pts()));
       float* f = ff->mutable_flow();
-      for (size_t i = 0; i < (size_t)width_ * height_; ++i) {
+      for (size_t i = 0; i < (size_t)flow_width_ * flow_height_; ++i) {
         f[2 * i] = -2.0f;
         f[2 * i + 1] = 0.0f;
       }
@@ -119,6 +129,7 @@ class SyntheticVideoUnit : public VideoUnit {
   std::string save_flow_;
   std::unique_ptr<DenseFlowWriter> flow_writer_;
   int original_width_, original_height_;
+  int flow_width_, flow_height_;   // the frame size behind a downscale: the flow belongs to those frames
   int width_step_ = 0;
   int k_ = 0;
 };
@@ -309,6 +320,11 @@ struct Flags {
   bool remove_rasterization = false;
   int original_width = 0, original_height = 0;   // the video's size before a downscale; 0 = the frame size
   std::string rewrite_pb;
+  // VideoReaderOptions::DOWNSCALE_TO_MIN_SIZE with this size (seg_tree.cpp:136-139); 0: no downscale
+  int downscale_min_size = 0;
+  // seg_tree.cpp:90-98: sets use_pipeline, write_to_file, downscale_min_size = 360 and switches the
+  // render unit off (this driver has no display, logging or display_flow to override)
+  bool run_on_server = false;
 };
 
 bool ParseFlags(int argc, char** argv, Flags* f) {
@@ -330,7 +346,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     }
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
-                                   "compute_flow", "remove_rasterization"};
+                                   "compute_flow", "remove_rasterization", "run_on_server", "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -359,6 +375,16 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "region_segmentation") f->region_segmentation = bv;
     else if (a == "render_concat") f->render_concat = bv;
     else if (a == "remove_rasterization") f->remove_rasterization = bv;
+    else if (a == "run_on_server") f->run_on_server = bv;
+    else if (a == "downscale_min_size") f->downscale_min_size = atoi(v.c_str());
+    else if (a == "help") {
+      std::printf(
+          "seg_tree_synth: see the head of seg_tree_synth.cpp for the flags.\n"
+          "  --downscale_min_size N  downscale every frame so that its smaller side is N (0: off)\n"
+          "  --run_on_server         sets --use_pipeline, --write_to_file, --downscale_min_size 360 and\n"
+          "                          switches --render_level off (seg_tree.cpp:90-98)\n");
+      std::exit(0);
+    }
     else if (a == "original_width") f->original_width = atoi(v.c_str());
     else if (a == "original_height") f->original_height = atoi(v.c_str());
     else if (a == "rewrite_pb") f->rewrite_pb = v;
@@ -393,6 +419,12 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
 int main(int argc, char** argv) {
   Flags FLAGS;
   if (!ParseFlags(argc, argv, &FLAGS)) return 2;
+  if (FLAGS.run_on_server) {   // seg_tree.cpp:90-98
+    FLAGS.use_pipeline = true;
+    FLAGS.render_level = -1;
+    FLAGS.write_to_file = true;
+    FLAGS.downscale_min_size = 360;
+  }
   if (!FLAGS.read_pb.empty()) return ReadBack(FLAGS.read_pb);
   if (!FLAGS.rewrite_pb.empty()) {
     return Rewrite(FLAGS.rewrite_pb, FLAGS.output_file, FLAGS.remove_rasterization, FLAGS.original_width,
@@ -423,11 +455,33 @@ int main(int argc, char** argv) {
                         : std::string();
   // --compute_flow: the flow comes from the flow units below, which also write --save_flow's file
   const bool compute_flow = FLAGS.compute_flow && use_flow && !flow_from_file;
+  // the synthetic flow is one of the frames the segmentation sees, so of the downscaled size
+  int flow_width = 0, flow_height = 0;
+  if (FLAGS.downscale_min_size > 0 &&
+      vsg_resize_output_size(VSG_RESIZE_TO_MIN_SIZE, 1.0f, FLAGS.downscale_min_size, FLAGS.width, FLAGS.height,
+                             &flow_width, &flow_height, nullptr) != VSG_OK) {
+    std::fprintf(stderr, "ERROR: --downscale_min_size: %s\n", vsg_resize_last_error());
+    return 2;
+  }
   SyntheticVideoUnit source(FLAGS.width, FLAGS.height, frames, use_flow && !flow_from_file && !compute_flow,
                             FLAGS.input == "bench" ? 1 : (FLAGS.input == "soft" ? 2 : 0),
-                            compute_flow ? std::string() : save_flow, FLAGS.original_width, FLAGS.original_height);
+                            compute_flow ? std::string() : save_flow, FLAGS.original_width, FLAGS.original_height,
+                            flow_width, flow_height);
   VideoUnit* root = raw_reader ? static_cast<VideoUnit*>(raw_reader.get()) : &source;
   VideoUnit* input = root;
+
+  // The reference's reader scales its own frames (video_reader_unit.cpp:155-206); here the unit that
+  // does it follows the root directly, in the root's pipeline segment.
+  std::unique_ptr<DownscaleUnit> downscale_unit;
+  if (FLAGS.downscale_min_size > 0) {   // seg_tree.cpp:136-139
+    DownscaleUnitOptions downscale_options;
+    downscale_options.downscale = DownscaleUnitOptions::DOWNSCALE_TO_MIN_SIZE;
+    downscale_options.downscale_size = FLAGS.downscale_min_size;
+    downscale_options.device = FLAGS.device;
+    downscale_unit.reset(new DownscaleUnit(downscale_options));
+    downscale_unit->AttachTo(input);
+    input = downscale_unit.get();
+  }
 
   // Pipeline segments as in seg_tree.cpp:155-163, 211-217: reader | [flow reader] dense
   // segmentation | sink + writer, each on its own thread.
