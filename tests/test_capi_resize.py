@@ -132,6 +132,24 @@ def test_create_checks_arguments_before_the_device(library):
     library.vsg_resize_destroy(None)
 
 
+def test_last_error_is_each_librarys_own(library):
+    """The three libraries compile the same support header and are loaded into one process: a failure
+    in one must not replace the text the others return for this thread."""
+    from video_segment_amd import flow, render
+    flow.build()
+    render.build()
+    h = C.c_void_p()
+    assert _create(library, 96, 72, mode=resize.DOWNSCALE_BY_FACTOR, factor=1.25) == -1
+    o = flow.default_flow_options(iterations=0)
+    assert flow.lib().vsg_flow_create(C.byref(o), 96, 72, C.byref(h)) == -1 and not h.value
+    o = render.default_render_options(hierarchy_level=-1.0)
+    assert render.lib().vsg_render_create(C.byref(o), 96, 72, C.byref(h)) == -1 and not h.value
+    for _ in range(2):   # reading one does not disturb another
+        assert library.vsg_resize_last_error() == b"Only downscaling is supported."
+        assert flow.lib().vsg_flow_last_error() == b"iterations has to be in [1, 1000]"
+        assert render.lib().vsg_render_last_error() == b"bad hierarchy_level"
+
+
 def test_no_cpu_fallback(library):
     """Without a HIP device vsg_resize_create must fail with VSG_ERR_DEVICE."""
     from video_segment_amd import _lib

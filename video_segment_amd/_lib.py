@@ -140,11 +140,7 @@ EXPORTED_SYMBOLS = [
 
 def build(force=False):
     """Compiles the HIP library in-tree (hipcc --offload-arch=gfx950)."""
-    if force or not os.path.exists(LIB_PATH):
-        subprocess.check_call(["make", "-C", CSRC_DIR, "-j8", "-s"])
-    else:
-        # make decides what is stale
-        subprocess.check_call(["make", "-C", CSRC_DIR, "-j8", "-s"])
+    subprocess.check_call(["make", "-C", CSRC_DIR, "-j8", "-s"])   # make decides what is stale
     return LIB_PATH
 
 

@@ -8,33 +8,27 @@ work happens in the HIP library; there is no Python or CPU fallback.  tests/flow
 the arithmetic.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError
+from . import _capi
+from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError  # noqa: F401 (part of the module)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-FLOW_DIR = os.path.join(_HERE, "flow")
-LIB_PATH = os.path.join(_HERE, "lib", "libvsg_flow.so")
+LIB_PATH = _capi.lib_path("vsg_flow")
 
 FLOW_BACKWARD, FLOW_FORWARD, FLOW_BOTH = 0, 1, 2
 
 
-class VsgFlowOptions(C.Structure):
+class VsgFlowOptions(_capi.Structure):
     _fields_ = [("flow_type", C.c_int), ("iterations", C.c_int), ("warps", C.c_int), ("device", C.c_int)]
 
 
-class VsgFlowStats(C.Structure):
+class VsgFlowStats(_capi.Structure):
     _fields_ = [
         ("scales", C.c_int), ("launches", C.c_int), ("iterations_run", C.c_int), ("host_syncs", C.c_int),
         ("device_allocations", C.c_int64),
         ("pyramid_us", C.c_float), ("warp_us", C.c_float), ("iterate_us", C.c_float), ("export_us", C.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # Every symbol include/vsg_flow.h declares.
@@ -47,7 +41,7 @@ EXPORTED_SYMBOLS = [
 
 def build(force=False):
     """Compiles libvsg_flow.so in-tree (hipcc --offload-arch=gfx950); make decides what is stale."""
-    subprocess.check_call(["make", "-C", FLOW_DIR, "-j8", "-s"] + (["-B"] if force else []))
+    _capi.make("flow", force)
     return LIB_PATH
 
 
@@ -58,14 +52,7 @@ def lib():
     global _handle
     if _handle is not None:
         return _handle
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libvsg_flow.so is missing (%s): build the HIP extension first; there is no "
-                           "fallback path" % LIB_PATH)
-    try:   # one HIP runtime per process: bind to the one torch loaded (see _lib.lib)
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
+    L = _capi.load(LIB_PATH, "libvsg_flow.so")
     vp = C.c_void_p
     L.vsg_flow_last_error.restype = C.c_char_p
     L.vsg_flow_default_options.argtypes = [C.POINTER(VsgFlowOptions)]
@@ -82,19 +69,11 @@ def lib():
     return L
 
 
-def check(rc):
-    if rc != VSG_OK:
-        raise VsgError("vsg_flow error %d: %s" % (rc, lib().vsg_flow_last_error().decode()), rc)
+check = _capi.checker("vsg_flow", lambda: lib().vsg_flow_last_error())
 
 
 def default_flow_options(**kw):
-    o = VsgFlowOptions()
-    lib().vsg_flow_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise TypeError("unknown flow option %r" % k)
-        setattr(o, k, v)
-    return o
+    return _capi.default_options(VsgFlowOptions, lib().vsg_flow_default_options, "flow", **kw)
 
 
 def luminance(bgr):
@@ -108,11 +87,7 @@ def luminance(bgr):
     return out
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-class DenseFlow:
+class DenseFlow(_capi.Handle):
     """Dual TV-L1 flow between consecutive frames on one MI355X.
 
     options: flow_type (FLOW_BACKWARD), iterations (10), warps (2), device (-1).  The first frame
@@ -128,41 +103,18 @@ class DenseFlow:
         self._dev_out = None
 
     def close(self):
-        if getattr(self, "h", None):
-            self._destroy(self.h)
-            self.h = None
+        super().close()
         self._dev_out = None
-
-    def __del__(self):
-        self.close()
 
     def restart(self):
         check(lib().vsg_flow_restart(self.h))
 
     def _input(self, frame):
         """(pointer, row stride, mem kind, entry point) of an H x W x 3 or H x W uint8 frame."""
-        shape = tuple(frame.shape)
-        if shape == (self.H, self.W, 3):
-            fn, px = lib().vsg_flow_process_frame, 3
-        elif shape == (self.H, self.W):
-            fn, px = lib().vsg_flow_process_luminance, 1
-        else:
-            raise ValueError("frame has to be %d x %d x 3 (BGR) or %d x %d (luminance), got %s"
-                             % (self.H, self.W, self.H, self.W, shape))
-        if str(frame.dtype).replace("torch.", "") != "uint8":
-            raise TypeError("frame has to be uint8")
-        if _is_torch(frame):
-            strides = tuple(s for s in frame.stride())
-            ptr, mem = frame.data_ptr(), VSG_MEM_DEVICE if frame.is_cuda else VSG_MEM_HOST
-            if frame.is_cuda:
-                import torch
-                torch.cuda.current_stream(frame.device).synchronize()   # the library works on its own stream
-        else:
-            strides, ptr, mem = frame.strides, frame.ctypes.data, VSG_MEM_HOST
-        packed = strides[1] == px and (px == 1 or strides[2] == 1)
-        if not packed or (self.H > 1 and strides[0] < px * self.W):
-            raise ValueError("frame: pixels have to be packed")
-        return C.c_void_p(ptr), strides[0], mem, fn
+        bgr = len(frame.shape) == 3
+        fn = lib().vsg_flow_process_frame if bgr else lib().vsg_flow_process_luminance
+        expected = "%d x %d x 3 (BGR) or %d x %d (luminance)" % (self.H, self.W, self.H, self.W)
+        return _capi.frame_ptr(frame, self.H, self.W, 3 if bgr else 1, "frame", expected) + (fn,)
 
     def _which(self):
         t = self.opts.flow_type

@@ -8,20 +8,16 @@ frame does, or where ``out=`` says.  All per-pixel work happens in the HIP libra
 Python or CPU fallback.
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from . import _lib
-from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError
+from . import _capi, _lib
+from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError  # noqa: F401 (part of the module)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-RENDER_DIR = os.path.join(_HERE, "render")
-LIB_PATH = os.path.join(_HERE, "lib", "libvsg_render.so")
+LIB_PATH = _capi.lib_path("vsg_render")
 
 
-class VsgRenderOptions(C.Structure):
+class VsgRenderOptions(_capi.Structure):
     _fields_ = [
         ("blend_alpha", C.c_float),
         ("hierarchy_level", C.c_float),
@@ -32,7 +28,7 @@ class VsgRenderOptions(C.Structure):
     ]
 
 
-class VsgRenderStats(C.Structure):
+class VsgRenderStats(_capi.Structure):
     _fields_ = [
         ("decode_ms", C.c_double), ("upload_ms", C.c_double),
         ("clear_us", C.c_float), ("fill_us", C.c_float), ("compose_us", C.c_float),
@@ -40,19 +36,13 @@ class VsgRenderStats(C.Structure):
         ("intervals", C.c_int64), ("distinct_ids", C.c_int64), ("device_allocations", C.c_int64),
     ]
 
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
-
-class VsgRenderVectorStats(C.Structure):
+class VsgRenderVectorStats(_capi.Structure):
     _fields_ = [
         ("lines", C.c_int64), ("crossings", C.c_int64), ("groups", C.c_int64), ("largest_group", C.c_int64),
         ("walk_us", C.c_float), ("sort_us", C.c_float), ("pairs_us", C.c_float),
         ("launches", C.c_int),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # Every symbol include/vsg_render.h declares.
@@ -65,7 +55,7 @@ EXPORTED_SYMBOLS = [
 
 def build(force=False):
     """Compiles libvsg_render.so in-tree (hipcc --offload-arch=gfx950); make decides what is stale."""
-    subprocess.check_call(["make", "-C", RENDER_DIR, "-j8", "-s"] + (["-B"] if force else []))
+    _capi.make("render", force)
     return LIB_PATH
 
 
@@ -76,14 +66,7 @@ def lib():
     global _handle
     if _handle is not None:
         return _handle
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libvsg_render.so is missing (%s): build the HIP extension first; there is no "
-                           "fallback path" % LIB_PATH)
-    try:   # one HIP runtime per process: bind to the one torch loaded (see _lib.lib)
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
+    L = _capi.load(LIB_PATH, "libvsg_render.so")
     vp = C.c_void_p
     L.vsg_render_last_error.restype = C.c_char_p
     L.vsg_render_default_options.argtypes = [C.POINTER(VsgRenderOptions)]
@@ -105,19 +88,11 @@ def lib():
     return L
 
 
-def check(rc):
-    if rc != VSG_OK:
-        raise VsgError("vsg_render error %d: %s" % (rc, lib().vsg_render_last_error().decode()), rc)
+check = _capi.checker("vsg_render", lambda: lib().vsg_render_last_error())
 
 
 def default_render_options(**kw):
-    o = VsgRenderOptions()
-    lib().vsg_render_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise TypeError("unknown render option %r" % k)
-        setattr(o, k, v)
-    return o
+    return _capi.default_options(VsgRenderOptions, lib().vsg_render_default_options, "render", **kw)
 
 
 def render_color(region_id):
@@ -134,30 +109,11 @@ def default_stride(width):
     return (3 * width + 3) // 4 * 4
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
 def _frame_ptr(x, rows, width, what):
-    """(pointer, row stride in bytes, mem kind) of a rows x width x 3 uint8 array or tensor whose
-    pixels are packed and whose rows may be further apart."""
-    if tuple(x.shape) != (rows, width, 3):
-        raise ValueError("%s has to be %d x %d x 3, got %s" % (what, rows, width, tuple(x.shape)))
-    if str(x.dtype).replace("torch.", "") != "uint8":
-        raise TypeError("%s has to be uint8" % what)
-    if _is_torch(x):
-        if x.stride(2) != 1 or x.stride(1) != 3 or (rows > 1 and x.stride(0) < 3 * width):
-            raise ValueError("%s: pixels have to be packed BGR24" % what)
-        if x.is_cuda:
-            import torch
-            torch.cuda.current_stream(x.device).synchronize()   # the library works on its own stream
-        return C.c_void_p(x.data_ptr()), x.stride(0), VSG_MEM_DEVICE if x.is_cuda else VSG_MEM_HOST
-    if x.strides[2] != 1 or x.strides[1] != 3 or (rows > 1 and x.strides[0] < 3 * width):
-        raise ValueError("%s: pixels have to be packed BGR24" % what)
-    return x.ctypes.data_as(C.c_void_p), x.strides[0], VSG_MEM_HOST
+    return _capi.frame_ptr(x, rows, width, 3, what, unpacked="pixels have to be packed BGR24")
 
 
-class SegmentationRenderer:
+class SegmentationRenderer(_capi.Handle):
     """Renders SegmentationDesc messages at a hierarchy level on one MI355X.
 
     options: blend_alpha (0.5), hierarchy_level (0; fractional = fraction of the hierarchy's height),
@@ -170,14 +126,6 @@ class SegmentationRenderer:
         check(lib().vsg_render_create(C.byref(self.opts), width, height, C.byref(h)))
         self.h = h
         self._destroy = lib().vsg_render_destroy
-
-    def close(self):
-        if getattr(self, "h", None):
-            self._destroy(self.h)
-            self.h = None
-
-    def __del__(self):
-        self.close()
 
     @property
     def out_rows(self):
@@ -203,7 +151,7 @@ class SegmentationRenderer:
                 raise ValueError("the renderer was created with has_video: pass the source frame")
             p_bgr, stride, mem_in = _frame_ptr(bgr, self.H, self.W, "bgr")
         if out is None:
-            if bgr is not None and self.opts.has_video and _is_torch(bgr) and bgr.is_cuda:
+            if bgr is not None and self.opts.has_video and _capi.is_torch(bgr) and bgr.is_cuda:
                 import torch
                 out = torch.empty((self.out_rows, self.W, 3), dtype=torch.uint8, device=bgr.device)
             else:
@@ -221,17 +169,7 @@ class SegmentationRenderer:
             out = np.empty((self.H, self.W), np.int32)
         if tuple(out.shape) != (self.H, self.W) or str(out.dtype).replace("torch.", "") != "int32":
             raise ValueError("out has to be %d x %d int32" % (self.H, self.W))
-        if _is_torch(out):
-            if not out.is_contiguous():
-                raise ValueError("out has to be contiguous")
-            p, mem = C.c_void_p(out.data_ptr()), VSG_MEM_DEVICE if out.is_cuda else VSG_MEM_HOST
-            if out.is_cuda:
-                import torch
-                torch.cuda.current_stream(out.device).synchronize()
-        else:
-            if not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("out has to be C-contiguous")
-            p, mem = out.ctypes.data_as(C.c_void_p), VSG_MEM_HOST
+        p, mem = _capi.contiguous_ptr(out)
         seg_bytes = bytes(seg_bytes)
         check(lib().vsg_render_id_image(self.h, seg_bytes, len(seg_bytes), int(level), p, mem))
         return out
@@ -252,17 +190,7 @@ class SegmentationRenderer:
                 return out
         if len(out.shape) != 2 or out.shape[1] != 4 or str(out.dtype).replace("torch.", "") != "int32":
             raise ValueError("out has to be (capacity, 4) int32")
-        if _is_torch(out):
-            if not out.is_contiguous():
-                raise ValueError("out has to be contiguous")
-            p, mem = C.c_void_p(out.data_ptr()), VSG_MEM_DEVICE if out.is_cuda else VSG_MEM_HOST
-            if out.is_cuda:
-                import torch
-                torch.cuda.current_stream(out.device).synchronize()
-        else:
-            if not out.flags["C_CONTIGUOUS"]:
-                raise ValueError("out has to be C-contiguous")
-            p, mem = out.ctypes.data_as(C.c_void_p), VSG_MEM_HOST
+        p, mem = _capi.contiguous_ptr(out)
         check(lib().vsg_render_rasterize(self.h, seg_bytes, len(seg_bytes), p, out.shape[0], C.byref(n), mem))
         return out[:n.value]
 

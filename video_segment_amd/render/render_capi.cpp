@@ -6,7 +6,6 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <stdexcept>
 #include <string>
 #include <unordered_map>
 #include <utility>
@@ -14,6 +13,7 @@
 
 #include "../../include/vsg_render.h"
 #include "render.h"
+#include "../common/capi_support.h"
 
 namespace {
 
@@ -21,56 +21,8 @@ using vsg_render_impl::Interval;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
 
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] void Throw(int code, const std::string& msg) { throw Error(code, msg); }
-
-#define RENDER_HIP(call)                                                                        \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) Throw(VSG_ERR_DEVICE, std::string(hipGetErrorString(e_)) + " in " #call); \
-  } while (0)
-
-thread_local std::string g_last_error;
-
-template <class F>
-int Guard(F&& f) {
-  try {
-    f();
-    return VSG_OK;
-  } catch (const Error& e) {
-    g_last_error = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return VSG_ERR_INTERNAL;
-  }
-}
-
-// Binds the calling thread to the handle's device for the duration of a call (a handle may be
-// driven from any thread; the HIP current device is a per-thread setting).
-class DeviceGuard {
- public:
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev_) != hipSuccess) return;
-    if (prev_ != device) {
-      RENDER_HIP(hipSetDevice(device));
-      changed_ = true;
-    }
-  }
-  ~DeviceGuard() {
-    if (changed_) (void)hipSetDevice(prev_);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-
- private:
-  int prev_ = -1;
-  bool changed_ = false;
-};
+enum Stage { STAGE_CLEAR = 0, STAGE_FILL, STAGE_COMPOSE, STAGE_COUNT };
+enum VecStage { VEC_WALK = 0, VEC_SORT, VEC_PAIRS, VEC_COUNT };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -362,36 +314,13 @@ int ParentId(int region_id, int level, const Hierarchy& hier) {
   return id;
 }
 
-// A device or pinned-host block that only grows; every runtime allocation is counted.
-struct Block {
-  void* p = nullptr;
-  size_t cap = 0;
-  bool pinned = false;
-  void Reserve(size_t bytes, int64_t* allocations) {
-    if (bytes <= cap) return;
-    Release();
-    const size_t want = std::max(bytes, cap + cap / 2);
-    if (pinned) RENDER_HIP(hipHostMalloc(&p, want, hipHostMallocDefault));
-    else RENDER_HIP(hipMalloc(&p, want));
-    cap = want;
-    ++*allocations;
-  }
-  void Release() {
-    if (!p) return;
-    if (pinned) (void)hipHostFree(p);
-    else (void)hipFree(p);
-    p = nullptr;
-    cap = 0;
-  }
-};
-
 }  // namespace
 
 struct vsg_render {
   vsg_render_options opt;
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  StageClock clock, vclock;   // clear, fill, compose; the vector path's walk, sort, pairs
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -407,24 +336,14 @@ struct vsg_render {
   std::vector<uint32_t> region_value;
   std::vector<float> scaled_mesh;
   Block d_vec_in, d_cross, d_sort_temp, d_status, h_status;
-  hipEvent_t vev[4] = {nullptr, nullptr, nullptr, nullptr};
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
 
   ~vsg_render() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (Block* b : {&d_intervals, &h_intervals, &d_plane, &d_src, &d_out, &d_ids, &d_vec_in, &d_cross, &d_sort_temp,
-                     &d_status, &h_status}) {
-      b->Release();
-    }
-    for (hipEvent_t e : ev) {
-      if (e) (void)hipEventDestroy(e);
-    }
-    for (hipEvent_t e : vev) {
-      if (e) (void)hipEventDestroy(e);
-    }
-    if (stream) (void)hipStreamDestroy(stream);
+    if (!stream) return;
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
   }
 
   // Interval list to the device through the pinned block (rewritten only after the stream drained:
@@ -435,19 +354,17 @@ struct vsg_render {
     h_intervals.Reserve(bytes, &allocations);
     d_intervals.Reserve(bytes, &allocations);
     std::memcpy(h_intervals.p, intervals.data(), bytes);
-    RENDER_HIP(hipMemcpyAsync(d_intervals.p, h_intervals.p, bytes, hipMemcpyHostToDevice, stream));
+    VSG_HIP(hipMemcpyAsync(d_intervals.p, h_intervals.p, bytes, hipMemcpyHostToDevice, stream));
     ++stats.launches;
   }
 
   void FinishStats() {
-    RENDER_HIP(hipStreamSynchronize(stream));
-    float ms = 0;
-    RENDER_HIP(hipEventElapsedTime(&ms, ev[0], ev[1]));
-    stats.clear_us = ms * 1000.0f;
-    RENDER_HIP(hipEventElapsedTime(&ms, ev[1], ev[2]));
-    stats.fill_us = ms * 1000.0f;
-    RENDER_HIP(hipEventElapsedTime(&ms, ev[2], ev[3]));
-    stats.compose_us = ms * 1000.0f;
+    VSG_HIP(hipStreamSynchronize(stream));
+    float us[STAGE_COUNT];
+    clock.Read(us, STAGE_COUNT);
+    stats.clear_us = us[STAGE_CLEAR];
+    stats.fill_us = us[STAGE_FILL];
+    stats.compose_us = us[STAGE_COMPOSE];
     stats.device_allocations = allocations;
   }
 
@@ -541,7 +458,7 @@ struct vsg_render {
     h_status.Reserve(sizeof(VecStatus), &allocations);
     std::memcpy(h_intervals.p, lines.data(), lines_bytes);
     std::memcpy(static_cast<char*>(h_intervals.p) + lines_bytes, region_value.data(), values_bytes);
-    RENDER_HIP(hipMemcpyAsync(d_vec_in.p, h_intervals.p, lines_bytes + values_bytes, hipMemcpyHostToDevice, stream));
+    VSG_HIP(hipMemcpyAsync(d_vec_in.p, h_intervals.p, lines_bytes + values_bytes, hipMemcpyHostToDevice, stream));
     const VecLine* d_lines = static_cast<const VecLine*>(d_vec_in.p);
     const uint32_t* d_values = reinterpret_cast<const uint32_t*>(static_cast<const char*>(d_vec_in.p) + lines_bytes);
     unsigned long long* keys = static_cast<unsigned long long*>(d_cross.p);
@@ -549,19 +466,19 @@ struct vsg_render {
     unsigned long long* keys_sorted = keys + 2 * n;
     unsigned long long* vals_sorted = keys + 3 * n;
     VecStatus* status = static_cast<VecStatus*>(d_status.p);
-    RENDER_HIP(hipMemsetAsync(status, 0, sizeof(VecStatus), stream));
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(VecStatus), stream));
     // every entry of the list is in the frame whatever the pairs stage leaves unwritten on bad input
-    RENDER_HIP(hipMemsetAsync(d_intervals.p, 0, n / 2 * sizeof(Interval), stream));
-    RENDER_HIP(hipEventRecord(vev[0], stream));
+    VSG_HIP(hipMemsetAsync(d_intervals.p, 0, n / 2 * sizeof(Interval), stream));
+    vclock.Begin(stream);
     LaunchVecWalk(d_lines, (int)lines.size(), keys, vals, status, stream);
-    RENDER_HIP(hipEventRecord(vev[1], stream));
-    RENDER_HIP(VecSort(d_sort_temp.p, temp_bytes, keys, keys_sorted, vals, vals_sorted, n_cross, end_bit, stream));
-    RENDER_HIP(hipEventRecord(vev[2], stream));
+    vclock.Mark(VEC_WALK);
+    VSG_HIP(VecSort(d_sort_temp.p, temp_bytes, keys, keys_sorted, vals, vals_sorted, n_cross, end_bit, stream));
+    vclock.Mark(VEC_SORT);
     LaunchVecPairs(keys_sorted, vals_sorted, d_lines, (uint32_t)lines.size(), d_values,
                    (uint32_t)region_value.size(), n_cross, W, H, static_cast<Interval*>(d_intervals.p), status, stream);
-    RENDER_HIP(hipGetLastError());
-    RENDER_HIP(hipEventRecord(vev[3], stream));
-    RENDER_HIP(hipMemcpyAsync(h_status.p, status, sizeof(VecStatus), hipMemcpyDeviceToHost, stream));
+    VSG_HIP(hipGetLastError());
+    vclock.Mark(VEC_PAIRS);
+    VSG_HIP(hipMemcpyAsync(h_status.p, status, sizeof(VecStatus), hipMemcpyDeviceToHost, stream));
     vstats.launches = 7;   // upload, two clears, walk, the sort counted as one, pairs, status
     stats.launches += vstats.launches;
   }
@@ -569,13 +486,11 @@ struct vsg_render {
   // After the call's one synchronisation: stage times, group statistics, the device flag.
   void CheckVector() {
     if (vstats.crossings == 0) return;
-    float ms = 0;
-    RENDER_HIP(hipEventElapsedTime(&ms, vev[0], vev[1]));
-    vstats.walk_us = ms * 1000.0f;
-    RENDER_HIP(hipEventElapsedTime(&ms, vev[1], vev[2]));
-    vstats.sort_us = ms * 1000.0f;
-    RENDER_HIP(hipEventElapsedTime(&ms, vev[2], vev[3]));
-    vstats.pairs_us = ms * 1000.0f;
+    float us[VEC_COUNT];
+    vclock.Read(us, VEC_COUNT);
+    vstats.walk_us = us[VEC_WALK];
+    vstats.sort_us = us[VEC_SORT];
+    vstats.pairs_us = us[VEC_PAIRS];
     const VecStatus* st = static_cast<const VecStatus*>(h_status.p);
     vstats.groups = (int64_t)st->groups;
     vstats.largest_group = (int64_t)st->largest_group;
@@ -589,10 +504,6 @@ struct vsg_render {
 };
 
 namespace {
-
-void CheckMem(int mem, const char* what) {
-  if (mem != VSG_MEM_HOST && mem != VSG_MEM_DEVICE) Throw(VSG_ERR_INVALID, std::string(what) + ": unknown memory kind");
-}
 
 // Parses the desc, applies the hierarchy bookkeeping both entry points share (a desc that carries a
 // hierarchy replaces the kept one) and returns the hierarchy to map ids with.
@@ -673,14 +584,8 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
       Throw(VSG_ERR_INVALID, "Request concatenation with source but no video stream present.");
     }
     if (!opt.has_video) opt.blend_alpha = 1.0f;   // segmentation_unit.cpp:486-490
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-      Throw(VSG_ERR_DEVICE, "no usable HIP device (libvsg_render has no CPU fallback): " +
-                                std::string(e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
-    }
-    if (opt.device >= n) Throw(VSG_ERR_DEVICE, "device ordinal out of range");
     std::unique_ptr<vsg_render> h(new vsg_render);
+    h->device = SelectDevice(opt.device, "libvsg_render");
     h->opt = opt;
     h->W = width;
     h->H = height;
@@ -689,25 +594,16 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->h_intervals.pinned = true;
     h->h_status.pinned = true;
     std::memset(&h->vstats, 0, sizeof(h->vstats));
-    if (opt.device >= 0) h->device = opt.device;
-    else RENDER_HIP(hipGetDevice(&h->device));
     DeviceGuard guard(h->device);
-    RENDER_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& ev : h->ev) RENDER_HIP(hipEventCreate(&ev));
-    for (hipEvent_t& ev : h->vev) RENDER_HIP(hipEventCreate(&ev));
+    VSG_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->clock.Create(STAGE_COUNT + 1);
+    h->vclock.Create(VEC_COUNT + 1);
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
 }
 
-void vsg_render_destroy(vsg_render* h) {
-  if (!h) return;
-  int prev = -1;
-  const bool have = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(h->device);
-  delete h;
-  if (have) (void)hipSetDevice(prev);
-}
+void vsg_render_destroy(vsg_render* h) { DestroyOnDevice(h); }
 
 int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const uint8_t* bgr, size_t stride,
                      int mem_in, uint8_t* out, size_t out_stride, int mem_out) {
@@ -777,8 +673,8 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
       } else {
         src_stride = vsg_render_default_stride(W);
         h->d_src.Reserve(src_stride * H, &h->allocations);
-        RENDER_HIP(hipMemcpy2DAsync(h->d_src.p, src_stride, bgr, stride, row_bytes, H, hipMemcpyHostToDevice,
-                                    h->stream));
+        VSG_HIP(hipMemcpy2DAsync(h->d_src.p, src_stride, bgr, stride, row_bytes, H, hipMemcpyHostToDevice,
+                                 h->stream));
         ++h->stats.launches;
         src = static_cast<const uint8_t*>(h->d_src.p);
       }
@@ -794,23 +690,23 @@ int vsg_render_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const ui
 
     // ---- device: clear, fill, compose ----
     uint32_t* plane = static_cast<uint32_t*>(h->d_plane.p);
-    RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
-    RENDER_HIP(hipMemsetAsync(plane, 0, (size_t)h->pitch * H * sizeof(uint32_t), h->stream));
-    RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
+    h->clock.Begin(h->stream);
+    VSG_HIP(hipMemsetAsync(plane, 0, (size_t)h->pitch * H * sizeof(uint32_t), h->stream));
+    h->clock.Mark(STAGE_CLEAR);
     vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, plane, h->pitch,
                                 h->stream);
-    RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
+    h->clock.Mark(STAGE_FILL);
     const int mode = h->opt.concat_with_source ? vsg_render_impl::COMPOSE_CONCAT
                      : video                   ? vsg_render_impl::COMPOSE_BLEND
                                                : vsg_render_impl::COMPOSE_RENDER;
     vsg_render_impl::LaunchCompose(plane, h->pitch, W, H, src, src_stride, dst, dst_stride, h->opt.highlight_edges,
                                    mode, h->opt.blend_alpha, h->stream);
-    RENDER_HIP(hipGetLastError());
-    RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
+    VSG_HIP(hipGetLastError());
+    h->clock.Mark(STAGE_COMPOSE);
     h->stats.launches += 2 + (n_intervals == 0 ? 0 : 1);
     if (mem_out == VSG_MEM_HOST) {
-      RENDER_HIP(hipMemcpy2DAsync(out, out_stride, dst, dst_stride, row_bytes, out_rows, hipMemcpyDeviceToHost,
-                                  h->stream));
+      VSG_HIP(hipMemcpy2DAsync(out, out_stride, dst, dst_stride, row_bytes, out_rows, hipMemcpyDeviceToHost,
+                               h->stream));
       ++h->stats.launches;
     }
     h->FinishStats();
@@ -855,16 +751,16 @@ int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int l
       ids = static_cast<uint32_t*>(h->d_ids.p);
     }
     h->stats.upload_ms = NowMs() - t1;
-    RENDER_HIP(hipEventRecord(h->ev[0], h->stream));
-    RENDER_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
-    RENDER_HIP(hipEventRecord(h->ev[1], h->stream));
+    h->clock.Begin(h->stream);
+    VSG_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
+    h->clock.Mark(STAGE_CLEAR);
     vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, W, h->stream);
-    RENDER_HIP(hipGetLastError());
-    RENDER_HIP(hipEventRecord(h->ev[2], h->stream));
-    RENDER_HIP(hipEventRecord(h->ev[3], h->stream));
+    VSG_HIP(hipGetLastError());
+    h->clock.Mark(STAGE_FILL);
+    h->clock.Mark(STAGE_COMPOSE);   // nothing is composed: the two marks are back to back
     h->stats.launches += 1 + (n_intervals == 0 ? 0 : 1);
     if (mem_out == VSG_MEM_HOST) {
-      RENDER_HIP(hipMemcpyAsync(out, ids, bytes, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(out, ids, bytes, hipMemcpyDeviceToHost, h->stream));
       ++h->stats.launches;
     }
     h->FinishStats();
@@ -904,11 +800,11 @@ int vsg_render_rasterize(vsg_render* h, const uint8_t* seg, size_t seg_len, int3
     h->RunVector(n_cross);
     h->stats.upload_ms = NowMs() - t1;
     if (n) {
-      RENDER_HIP(hipMemcpyAsync(out, h->d_intervals.p, n * sizeof(Interval),
-                                mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
+      VSG_HIP(hipMemcpyAsync(out, h->d_intervals.p, n * sizeof(Interval),
+                             mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice, h->stream));
       ++h->stats.launches;
     }
-    RENDER_HIP(hipStreamSynchronize(h->stream));
+    VSG_HIP(hipStreamSynchronize(h->stream));
     h->stats.device_allocations = h->allocations;
     h->CheckVector();
   });

@@ -8,35 +8,29 @@ The output size is the reference's rule; the resampling is defined by tests/resi
 with swscale is unpinned).
 """
 import ctypes as C
-import os
-import subprocess
 
 import numpy as np
 
-from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError
+from . import _capi
+from ._lib import VSG_MEM_DEVICE, VSG_MEM_HOST, VSG_OK, VsgError  # noqa: F401 (part of the module)
 
-_HERE = os.path.dirname(os.path.abspath(__file__))
-RESIZE_DIR = os.path.join(_HERE, "resize")
-LIB_PATH = os.path.join(_HERE, "lib", "libvsg_resize.so")
+LIB_PATH = _capi.lib_path("vsg_resize")
 
 DOWNSCALE_NONE, DOWNSCALE_BY_FACTOR, DOWNSCALE_TO_MIN_SIZE, DOWNSCALE_TO_MAX_SIZE = 0, 1, 2, 3
 MAX_TAPS_H = 1024
 
 
-class VsgResizeOptions(C.Structure):
+class VsgResizeOptions(_capi.Structure):
     _fields_ = [("mode", C.c_int), ("factor", C.c_float), ("size", C.c_int), ("device", C.c_int)]
 
 
-class VsgResizeStats(C.Structure):
+class VsgResizeStats(_capi.Structure):
     _fields_ = [
         ("launches", C.c_int), ("host_syncs", C.c_int), ("taps_h", C.c_int), ("taps_v", C.c_int),
         ("device_allocations", C.c_int64),
         ("upload_us", C.c_float), ("horizontal_us", C.c_float), ("vertical_us", C.c_float),
         ("download_us", C.c_float), ("copy_us", C.c_float),
     ]
-
-    def as_dict(self):
-        return {k: getattr(self, k) for k, _ in self._fields_}
 
 
 # Every symbol include/vsg_resize.h declares.
@@ -49,7 +43,7 @@ EXPORTED_SYMBOLS = [
 
 def build(force=False):
     """Compiles libvsg_resize.so in-tree (hipcc --offload-arch=gfx950); make decides what is stale."""
-    subprocess.check_call(["make", "-C", RESIZE_DIR, "-j8", "-s"] + (["-B"] if force else []))
+    _capi.make("resize", force)
     return LIB_PATH
 
 
@@ -60,14 +54,7 @@ def lib():
     global _handle
     if _handle is not None:
         return _handle
-    if not os.path.exists(LIB_PATH):
-        raise RuntimeError("libvsg_resize.so is missing (%s): build the HIP extension first; there is no "
-                           "fallback path" % LIB_PATH)
-    try:   # one HIP runtime per process: bind to the one torch loaded (see _lib.lib)
-        import torch  # noqa: F401
-    except ImportError:
-        pass
-    L = C.CDLL(LIB_PATH)
+    L = _capi.load(LIB_PATH, "libvsg_resize.so")
     vp, ip = C.c_void_p, C.POINTER(C.c_int)
     L.vsg_resize_last_error.restype = C.c_char_p
     L.vsg_resize_default_options.argtypes = [C.POINTER(VsgResizeOptions)]
@@ -84,19 +71,11 @@ def lib():
     return L
 
 
-def check(rc):
-    if rc != VSG_OK:
-        raise VsgError("vsg_resize error %d: %s" % (rc, lib().vsg_resize_last_error().decode()), rc)
+check = _capi.checker("vsg_resize", lambda: lib().vsg_resize_last_error())
 
 
 def default_resize_options(**kw):
-    o = VsgResizeOptions()
-    lib().vsg_resize_default_options(C.byref(o))
-    for k, v in kw.items():
-        if not hasattr(o, k):
-            raise TypeError("unknown resize option %r" % k)
-        setattr(o, k, v)
-    return o
+    return _capi.default_options(VsgResizeOptions, lib().vsg_resize_default_options, "resize", **kw)
 
 
 def output_size(mode, in_w, in_h, size=0, factor=1.0):
@@ -119,11 +98,7 @@ def filter_tables(n_in, n_out):
     return first, count, weights
 
 
-def _is_torch(x):
-    return type(x).__module__.startswith("torch")
-
-
-class Downscaler:
+class Downscaler(_capi.Handle):
     """The reader's downscale on one MI355X.
 
     mode: DOWNSCALE_NONE / BY_FACTOR (factor) / TO_MIN_SIZE / TO_MAX_SIZE (size).  ``out_size`` is
@@ -143,31 +118,12 @@ class Downscaler:
         self._dev_out = None
 
     def close(self):
-        if getattr(self, "h", None):
-            self._destroy(self.h)
-            self.h = None
+        super().close()
         self._dev_out = None
-
-    def __del__(self):
-        self.close()
 
     def _input(self, frame):
         """(pointer, row stride, mem kind) of an H x W x 3 uint8 frame with packed pixels."""
-        if tuple(frame.shape) != (self.H, self.W, 3):
-            raise ValueError("frame has to be %d x %d x 3 (BGR), got %s" % (self.H, self.W, tuple(frame.shape)))
-        if str(frame.dtype).replace("torch.", "") != "uint8":
-            raise TypeError("frame has to be uint8")
-        if _is_torch(frame):
-            strides = tuple(frame.stride())
-            ptr, mem = frame.data_ptr(), VSG_MEM_DEVICE if frame.is_cuda else VSG_MEM_HOST
-            if frame.is_cuda:
-                import torch
-                torch.cuda.current_stream(frame.device).synchronize()   # the library works on its own stream
-        else:
-            strides, ptr, mem = frame.strides, frame.ctypes.data, VSG_MEM_HOST
-        if strides[2] != 1 or strides[1] != 3 or (self.H > 1 and strides[0] < 3 * self.W):
-            raise ValueError("frame: pixels have to be packed")
-        return C.c_void_p(ptr), strides[0], mem
+        return _capi.frame_ptr(frame, self.H, self.W, 3, "frame", "%d x %d x 3 (BGR)" % (self.H, self.W))
 
     def process_frame(self, frame):
         """The downscaled frame as out_h x out_w x 3 uint8 numpy."""

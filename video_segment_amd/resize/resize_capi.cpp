@@ -5,65 +5,15 @@
 #include <cmath>
 #include <cstring>
 #include <memory>
-#include <stdexcept>
 #include <string>
 
 #include "../../include/vsg_resize.h"
 #include "resize.h"
+#include "../common/capi_support.h"
 
 namespace {
 
 using namespace vsg_resize_impl;
-
-struct Error : std::runtime_error {
-  int code;
-  Error(int c, const std::string& m) : std::runtime_error(m), code(c) {}
-};
-
-[[noreturn]] void Throw(int code, const std::string& msg) { throw Error(code, msg); }
-
-#define RESIZE_HIP(call)                                                                        \
-  do {                                                                                          \
-    hipError_t e_ = (call);                                                                     \
-    if (e_ != hipSuccess) Throw(VSG_ERR_DEVICE, std::string(hipGetErrorString(e_)) + " in " #call); \
-  } while (0)
-
-thread_local std::string g_last_error;
-
-template <class F>
-int Guard(F&& f) {
-  try {
-    f();
-    return VSG_OK;
-  } catch (const Error& e) {
-    g_last_error = e.what();
-    return e.code;
-  } catch (const std::exception& e) {
-    g_last_error = e.what();
-    return VSG_ERR_INTERNAL;
-  }
-}
-
-// Binds the calling thread to the handle's device for the duration of a call.
-class DeviceGuard {
- public:
-  explicit DeviceGuard(int device) {
-    if (hipGetDevice(&prev_) != hipSuccess) return;
-    if (prev_ != device) {
-      RESIZE_HIP(hipSetDevice(device));
-      changed_ = true;
-    }
-  }
-  ~DeviceGuard() {
-    if (changed_) (void)hipSetDevice(prev_);
-  }
-  DeviceGuard(const DeviceGuard&) = delete;
-  DeviceGuard& operator=(const DeviceGuard&) = delete;
-
- private:
-  int prev_ = -1;
-  bool changed_ = false;
-};
 
 const int kMaxSide = 65535;
 
@@ -114,38 +64,20 @@ struct vsg_resize {
   int taps_h = 0, taps_v = 0;
   int tile_cols = 0, span_stride = 0, pitch = 0;
   hipStream_t stream = nullptr;
-  hipEvent_t events[STAGE_COUNT + 1] = {};
+  StageClock clock;
   // device blocks: tables and the intermediate from creation, the staging blocks on first use
-  int32_t *d_first_h = nullptr, *d_count_h = nullptr, *d_first_v = nullptr, *d_count_v = nullptr;
-  float *d_weights_ht = nullptr, *d_weights_v = nullptr, *d_inter = nullptr;
-  uint8_t *d_in = nullptr, *d_out = nullptr;
+  Block d_first_h, d_count_h, d_first_v, d_count_v, d_weights_ht, d_weights_v, d_inter, d_in, d_out;
   int64_t allocations = 0;
   vsg_resize_stats stats;
 
-  template <class T>
-  void Alloc(T** p, size_t count) {
-    RESIZE_HIP(hipMalloc(reinterpret_cast<void**>(p), std::max<size_t>(count, 1) * sizeof(T)));
-    ++allocations;
-  }
-
   ~vsg_resize() {
-    if (stream) (void)hipStreamSynchronize(stream);
-    for (void* p : {(void*)d_first_h, (void*)d_count_h, (void*)d_first_v, (void*)d_count_v, (void*)d_weights_ht,
-                    (void*)d_weights_v, (void*)d_inter, (void*)d_in, (void*)d_out}) {
-      if (p) (void)hipFree(p);
-    }
-    for (hipEvent_t e : events) {
-      if (e) (void)hipEventDestroy(e);
-    }
-    if (stream) (void)hipStreamDestroy(stream);
+    if (!stream) return;
+    (void)hipStreamSynchronize(stream);
+    (void)hipStreamDestroy(stream);
   }
 };
 
 namespace {
-
-void CheckMem(int mem, const char* what) {
-  if (mem != VSG_MEM_HOST && mem != VSG_MEM_DEVICE) Throw(VSG_ERR_INVALID, std::string(what) + ": unknown memory kind");
-}
 
 // The widest tile of output columns whose source spans, H_ROWS of them, fit the LDS budget.
 void ChooseTile(vsg_resize* h) {
@@ -179,12 +111,7 @@ void Process(vsg_resize* h, const uint8_t* in, size_t stride_in, int mem_in, uin
   DeviceGuard guard(h->device);
   std::memset(&h->stats, 0, sizeof(h->stats));
   hipStream_t st = h->stream;
-  bool ran[STAGE_COUNT] = {false, false, false, false, false};
-  auto mark = [&](int stage) {   // events[k + 1] ends stage k; events[0] starts the call
-    RESIZE_HIP(hipEventRecord(h->events[stage + 1], st));
-    ran[stage] = true;
-  };
-  RESIZE_HIP(hipEventRecord(h->events[0], st));
+  h->clock.Begin(st);
 
   if (h->identity) {   // out == in on both axes: the frame is copied, no filter runs
     if (mem_in == VSG_MEM_HOST && mem_out == VSG_MEM_HOST) {   // nothing for the device to do
@@ -193,57 +120,51 @@ void Process(vsg_resize* h, const uint8_t* in, size_t stride_in, int mem_in, uin
       const hipMemcpyKind kind = mem_in == VSG_MEM_HOST    ? hipMemcpyHostToDevice
                                  : mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost
                                                            : hipMemcpyDeviceToDevice;
-      RESIZE_HIP(hipMemcpy2DAsync(out, stride_out, in, stride_in, row_in, (size_t)h->in_h, kind, st));
+      VSG_HIP(hipMemcpy2DAsync(out, stride_out, in, stride_in, row_in, (size_t)h->in_h, kind, st));
       ++h->stats.launches;
     }
-    mark(STAGE_COPY);
+    h->clock.Mark(STAGE_COPY);
   } else {
     const uint8_t* src = in;
     size_t src_stride = stride_in;
     if (mem_in == VSG_MEM_HOST) {
       const size_t packed = (size_t)RoundUp4((int)row_in);
-      if (!h->d_in) h->Alloc(&h->d_in, packed * h->in_h);
-      RESIZE_HIP(hipMemcpy2DAsync(h->d_in, packed, in, stride_in, row_in, (size_t)h->in_h, hipMemcpyHostToDevice, st));
+      h->d_in.Reserve(packed * h->in_h, &h->allocations);
+      VSG_HIP(hipMemcpy2DAsync(h->d_in.p, packed, in, stride_in, row_in, (size_t)h->in_h, hipMemcpyHostToDevice, st));
       ++h->stats.launches;
-      mark(STAGE_UPLOAD);
-      src = h->d_in;
+      h->clock.Mark(STAGE_UPLOAD);
+      src = h->d_in.As<uint8_t>();
       src_stride = packed;
     }
     uint8_t* dst = out;
     size_t dst_stride = stride_out;
     if (mem_out == VSG_MEM_HOST) {
-      if (!h->d_out) h->Alloc(&h->d_out, (size_t)h->width_step * h->out_h);
-      dst = h->d_out;
+      h->d_out.Reserve((size_t)h->width_step * h->out_h, &h->allocations);
+      dst = h->d_out.As<uint8_t>();
       dst_stride = (size_t)h->width_step;
     }
-    LaunchResizeH(src, src_stride, h->in_w, h->in_h, h->out_w, h->d_first_h, h->d_count_h, h->d_weights_ht,
-                  h->tile_cols, h->span_stride, h->d_inter, h->pitch, st);
-    RESIZE_HIP(hipGetLastError());
-    mark(STAGE_H);
-    LaunchResizeV(h->d_inter, h->pitch, h->in_h, h->out_w, h->out_h, h->d_first_v, h->d_count_v, h->d_weights_v,
-                  h->taps_v, dst, dst_stride, st);
-    RESIZE_HIP(hipGetLastError());
-    mark(STAGE_V);
+    float* inter = h->d_inter.As<float>();
+    LaunchResizeH(src, src_stride, h->in_w, h->in_h, h->out_w, h->d_first_h.As<int32_t>(), h->d_count_h.As<int32_t>(),
+                  h->d_weights_ht.As<float>(), h->tile_cols, h->span_stride, inter, h->pitch, st);
+    VSG_HIP(hipGetLastError());
+    h->clock.Mark(STAGE_H);
+    LaunchResizeV(inter, h->pitch, h->in_h, h->out_w, h->out_h, h->d_first_v.As<int32_t>(), h->d_count_v.As<int32_t>(),
+                  h->d_weights_v.As<float>(), h->taps_v, dst, dst_stride, st);
+    VSG_HIP(hipGetLastError());
+    h->clock.Mark(STAGE_V);
     h->stats.launches += 2;
     if (mem_out == VSG_MEM_HOST) {
-      RESIZE_HIP(hipMemcpy2DAsync(out, stride_out, dst, dst_stride, row_out, (size_t)h->out_h, hipMemcpyDeviceToHost, st));
+      VSG_HIP(hipMemcpy2DAsync(out, stride_out, dst, dst_stride, row_out, (size_t)h->out_h, hipMemcpyDeviceToHost, st));
       ++h->stats.launches;
-      mark(STAGE_DOWNLOAD);
+      h->clock.Mark(STAGE_DOWNLOAD);
     }
     h->stats.taps_h = h->taps_h;
     h->stats.taps_v = h->taps_v;
   }
-  RESIZE_HIP(hipStreamSynchronize(st));
+  VSG_HIP(hipStreamSynchronize(st));
   h->stats.host_syncs = 1;
-  float us[STAGE_COUNT] = {0, 0, 0, 0, 0};
-  int prev = 0;   // index into events of the last one recorded
-  for (int k = 0; k < STAGE_COUNT; ++k) {
-    if (!ran[k]) continue;
-    float ms = 0;
-    RESIZE_HIP(hipEventElapsedTime(&ms, h->events[prev], h->events[k + 1]));
-    us[k] = ms * 1000.0f;
-    prev = k + 1;
-  }
+  float us[STAGE_COUNT];
+  h->clock.Read(us, STAGE_COUNT);
   h->stats.upload_us = us[STAGE_UPLOAD];
   h->stats.horizontal_us = us[STAGE_H];
   h->stats.vertical_us = us[STAGE_V];
@@ -319,41 +240,31 @@ int vsg_resize_create(const vsg_resize_options* o, int in_w, int in_h, vsg_resiz
       h->pitch = RoundUp4(h->out_w * 3);
       ChooseTile(h.get());
     }
-    int n = 0;
-    const hipError_t e = hipGetDeviceCount(&n);
-    if (e != hipSuccess || n <= 0) {
-      Throw(VSG_ERR_DEVICE, "no usable HIP device (libvsg_resize has no CPU fallback): " +
-                                std::string(e != hipSuccess ? hipGetErrorString(e) : "device count is 0"));
-    }
-    if (opt.device >= n) Throw(VSG_ERR_DEVICE, "device ordinal out of range");
-    if (opt.device >= 0) h->device = opt.device;
-    else RESIZE_HIP(hipGetDevice(&h->device));
+    h->device = SelectDevice(opt.device, "libvsg_resize");
     DeviceGuard guard(h->device);
-    RESIZE_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-    for (hipEvent_t& ev : h->events) RESIZE_HIP(hipEventCreate(&ev));
+    VSG_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
+    h->clock.Create(STAGE_COUNT + 1);
     if (!h->identity) {
       const size_t nw = (size_t)h->out_w, nh = (size_t)h->out_h;
       std::vector<float> wt((size_t)h->taps_h * nw);   // max_taps x out_w: a tap's weights are contiguous
       for (size_t oo = 0; oo < nw; ++oo) {
         for (size_t j = 0; j < (size_t)h->taps_h; ++j) wt[j * nw + oo] = h->fh.weights[oo * h->taps_h + j];
       }
-      h->Alloc(&h->d_first_h, nw);
-      h->Alloc(&h->d_count_h, nw);
-      h->Alloc(&h->d_weights_ht, wt.size());
-      h->Alloc(&h->d_first_v, nh);
-      h->Alloc(&h->d_count_v, nh);
-      h->Alloc(&h->d_weights_v, h->fv.weights.size());
-      h->Alloc(&h->d_inter, (size_t)h->pitch * in_h);
+      const size_t inter_bytes = (size_t)h->pitch * in_h * sizeof(float);
+      const struct { Block* block; const void* from; size_t bytes; } tables[] = {
+          {&h->d_first_h, h->fh.first.data(), nw * sizeof(int32_t)},
+          {&h->d_count_h, h->fh.count.data(), nw * sizeof(int32_t)},
+          {&h->d_weights_ht, wt.data(), wt.size() * sizeof(float)},
+          {&h->d_first_v, h->fv.first.data(), nh * sizeof(int32_t)},
+          {&h->d_count_v, h->fv.count.data(), nh * sizeof(int32_t)},
+          {&h->d_weights_v, h->fv.weights.data(), h->fv.weights.size() * sizeof(float)},
+      };
+      for (const auto& t : tables) t.block->Reserve(t.bytes, &h->allocations);
+      h->d_inter.Reserve(inter_bytes, &h->allocations);
       hipStream_t st = h->stream;
-      RESIZE_HIP(hipMemcpyAsync(h->d_first_h, h->fh.first.data(), nw * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemcpyAsync(h->d_count_h, h->fh.count.data(), nw * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemcpyAsync(h->d_weights_ht, wt.data(), wt.size() * sizeof(float), hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemcpyAsync(h->d_first_v, h->fv.first.data(), nh * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemcpyAsync(h->d_count_v, h->fv.count.data(), nh * sizeof(int32_t), hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemcpyAsync(h->d_weights_v, h->fv.weights.data(), h->fv.weights.size() * sizeof(float),
-                                hipMemcpyHostToDevice, st));
-      RESIZE_HIP(hipMemsetAsync(h->d_inter, 0, (size_t)h->pitch * in_h * sizeof(float), st));   // the rows' padding
-      RESIZE_HIP(hipStreamSynchronize(st));
+      for (const auto& t : tables) VSG_HIP(hipMemcpyAsync(t.block->p, t.from, t.bytes, hipMemcpyHostToDevice, st));
+      VSG_HIP(hipMemsetAsync(h->d_inter.p, 0, inter_bytes, st));   // the rows' padding
+      VSG_HIP(hipStreamSynchronize(st));
       h->fh.weights = std::vector<float>();
       h->fv.weights = std::vector<float>();
     }
@@ -361,14 +272,7 @@ int vsg_resize_create(const vsg_resize_options* o, int in_w, int in_h, vsg_resiz
   });
 }
 
-void vsg_resize_destroy(vsg_resize* h) {
-  if (!h) return;
-  int prev = -1;
-  const bool have = hipGetDevice(&prev) == hipSuccess;
-  (void)hipSetDevice(h->device);
-  delete h;
-  if (have) (void)hipSetDevice(prev);
-}
+void vsg_resize_destroy(vsg_resize* h) { DestroyOnDevice(h); }
 
 int vsg_resize_get_output_size(vsg_resize* h, int* out_w, int* out_h, int* width_step) {
   return Guard([&] {
