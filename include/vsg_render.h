@@ -33,7 +33,10 @@
  *
  * Not offered (the reference has them): draw_shape_descriptors, and the two cv::putText overlays
  * ("Frame #...", "Change to chunk id ...") -- the Hershey glyphs are OpenCV's data.  A rendered
- * frame therefore equals the reference's up to those text pixels.
+ * frame therefore equals the reference's up to those text pixels.  The inputs of
+ * draw_shape_descriptors are available, though: vsg_render_level_regions returns every region of a
+ * level with its merged rasterization, its area and its shape moments; the ellipse's axes and angle
+ * (GetShapeDescriptorFromShapeMoments) and the drawing itself are left to the caller.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -144,6 +147,59 @@ typedef struct vsg_render_vector_stats {
 } vsg_render_vector_stats;
 
 int vsg_render_last_vector_stats(vsg_render* h, vsg_render_vector_stats* s);
+
+/* One region of a hierarchy level, as vsg_render_level_regions returns it. */
+typedef struct vsg_render_level_region {      /* 56 bytes, no padding */
+  int32_t id;                /* region id at `level` (GetParentId(overseg_id, 0, level))            */
+  int32_t first_interval;    /* index of its first interval in the interval list                    */
+  int32_t num_intervals;
+  int32_t area;              /* RasterizationArea of the merged rasterization                       */
+  int32_t min_x, min_y, max_x, max_y;          /* bounding box, inclusive                           */
+  float size, mean_x, mean_y, moment_xx, moment_xy, moment_yy;   /* ShapeMomentsFromRasterization   */
+} vsg_render_level_region;
+
+/* The regions of hierarchy level `level` with their rasterizations, areas and shape moments: what
+ * GetParentMap + GetCompoundRegionRasterizations (segment_util/segmentation_util.cpp:199-213,
+ * 592-605), RasterizationArea (:644-650) and ShapeMomentsFromRasterization (:652-693) give, computed
+ * on the device from the id plane of vsg_render_id_image.
+ * regions: ordered by ascending id.  intervals: int32 quadruples {y, left_x, right_x, region_id} as
+ * vsg_render_rasterize writes them, grouped by region in the order of the region list, within a
+ * region in ScanIntervalComparator order (y, then left_x).  Both in mem_out memory.
+ * Level and hierarchy are those of vsg_render_id_image: the desc's own hierarchy when it carries one
+ * (it then replaces the kept one), else the kept one; level 0 needs none; level < 0, or level > 0
+ * and not below the hierarchy's height, an unsorted level or an id missing from one is
+ * VSG_ERR_INVALID.  A vector-only desc (rasterization_removed) is scan converted on the device
+ * first, at the handle's size.  Region ids have to be non-negative.
+ *
+ * A region's rasterization is the set of maximal runs of its id per row of the id plane; pixels
+ * without a region (-1) belong to no run and a run ends with its row.  Where no region has two
+ * touching intervals in one row (left_x = right_x + 1 of its neighbour) this is exactly what
+ * MergeRasterizations returns, whatever the order of the children; every desc this project or the
+ * reference's dense unit writes is of that kind.  Where one region does have touching intervals, the
+ * reference joins them only in rows that a second child shares (MergeRasterization copies a row
+ * only one side has), so its result depends on the children; this call returns the maximal runs.
+ * Overlapping intervals are unspecified, as for the picture.
+ * The moments are ShapeMomentsFromRasterization applied to that list in its order, f32 operation
+ * for operation: every sum is accumulated interval by interval, so the bits are the reference's.
+ *
+ * *num_regions and *num_intervals are always set on VSG_OK and when a capacity is too small; in
+ * that case the call fails with VSG_ERR_INVALID and neither output is touched.  regions == NULL and
+ * intervals == NULL with both capacities 0 asks for the counts only (VSG_OK); the counts come from
+ * the plane, so this needs the device too.  A null handle or a null count pointer is
+ * VSG_ERR_INVALID and touches no device. */
+int vsg_render_level_regions(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
+                             vsg_render_level_region* regions, size_t capacity_regions, size_t* num_regions,
+                             int32_t* intervals, size_t capacity_intervals, size_t* num_intervals, int mem_out);
+
+/* What the last vsg_render_level_regions call of the handle did.  Device times are HIP events around
+ * the stages: k_level_runs; the radix sort; the scan and k_level_table; k_level_moments (not run,
+ * like largest_region_intervals not known, in a count-only call). */
+typedef struct vsg_render_level_stats {
+  int64_t runs, regions, largest_region_intervals;
+  float runs_us, sort_us, table_us, moments_us;
+  int launches;
+} vsg_render_level_stats;
+int vsg_render_last_level_stats(vsg_render* h, vsg_render_level_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -17,6 +17,14 @@ The vector leg: the same four chunk results computed with compute_vectorization,
 rasterization_removed set).  For the vector-only desc the three scan conversion stages (k_vec_walk,
 radix sort, k_vec_pairs; vsg_render_last_vector_stats), host decode and upload and the fill are
 recorded, for the desc with rasters decode, upload and fill: the yardstick beside them.
+
+    python tools/render_probe.py --level-regions [--reps 30] [--out profiles/level_regions.json]
+
+The level leg: a dense-unit chunk result given a hierarchy by RegionSegmentation, asked for its regions
+(vsg_render_level_regions, outputs in device memory) at the lowest, a middle and the top level.  Per
+call the four stage times of vsg_render_level_stats, the launch count and the runs of the frame are
+recorded; in the same run vsg_render_id_image on the same desc and level is timed, which is what
+painting the plane the answer is read from costs.  No pass or fail threshold.
 """
 import argparse
 import json
@@ -43,9 +51,14 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--sizes", default="1920x1080,3840x2160")
     ap.add_argument("--vector", action="store_true", help="the vector leg instead (profiles/vector_raster.json)")
+    ap.add_argument("--level-regions", action="store_true",
+                    help="the level leg instead (profiles/level_regions.json)")
     args = ap.parse_args()
+    if args.level_regions and "--reps" not in sys.argv:
+        args.reps = 30
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "vector_raster.json" if args.vector else "render_kernels.json")
+        name = "level_regions.json" if args.level_regions else "vector_raster.json" if args.vector else "render_kernels.json"
+        args.out = os.path.join(ROOT, "profiles", name)
 
     import torch
     import synth
@@ -57,6 +70,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.level_regions:
+        return level_leg(args, result, dev)
     for size in args.sizes.split(","):
         W, H = (int(v) for v in size.split("x"))
         px = W * H
@@ -174,6 +189,66 @@ def vector_leg(args, result, dev):
             with open(args.out, "w") as f:
                 json.dump(result, f, indent=1)
                 f.write("\n")
+    print("wrote", args.out)
+
+
+def level_leg(args, result, dev):
+    import torch
+    import synth
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    from test_proto_wire import build_schema
+    Msg = build_schema()
+    for size in args.sizes.split(","):
+        W, H = (int(v) for v in size.split("x"))
+        N = 3
+        fl = synth.const_flow(W, H)
+        frames = [synth.bench_frame(W, H, k) for k in range(N)]
+        d = vsg.DenseSegmentation(W, H, vsg.default_options(chunk_size=20), has_flow=True)
+        reg = vsg.RegionSegmentation(W, H, vsg.default_region_options())
+        over, segs = [], []
+        for k in range(N):
+            n = d.process_frame(frames[k], fl if k > 0 else None, flush=(k == N - 1))
+            over += [d.result_bytes(i) for i in range(n)]
+        for k, seg in enumerate(over):
+            n = reg.process_frame(seg, frames[k], fl if k > 0 else None, flush=(k == N - 1))
+            segs += [reg.result_bytes(i) for i in range(n)]
+        d.close()
+        reg.close()
+        m = Msg()
+        m.ParseFromString(segs[0])          # the chunk's first frame carries the hierarchy
+        height = len(m.hierarchy)
+        r = vsg.SegmentationRenderer(W, H, has_video=False)
+        ids = torch.empty((H, W), dtype=torch.int32, device=dev)
+        for level in sorted({0, height // 2, max(height - 1, 0)}):
+            nr, ni = (len(a) for a in r.level_regions(segs[0], level))
+            regions = torch.empty((nr, render.LEVEL_REGION_WORDS), dtype=torch.int32, device=dev)
+            intervals = torch.empty((ni, 4), dtype=torch.int32, device=dev)
+            keys = ["runs_us", "sort_us", "table_us", "moments_us", "call_ms", "id_image_call_ms", "id_image_fill_us",
+                    "id_image_clear_us"]
+            rows = {k: [] for k in keys}
+            for it in range(args.warmup + args.reps):
+                t0 = time.perf_counter()
+                r.level_regions(segs[0], level, regions_out=regions, intervals_out=intervals)
+                st = dict(r.last_level_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
+                t0 = time.perf_counter()
+                r.id_image(segs[0], level, out=ids)
+                ist = r.last_stats()
+                st.update(id_image_call_ms=(time.perf_counter() - t0) * 1e3, id_image_fill_us=ist["fill_us"],
+                          id_image_clear_us=ist["clear_us"])
+                if it >= args.warmup:
+                    for k in keys:
+                        rows[k].append(st[k])
+            case = {"size": size, "level": level, "hierarchy_levels": height, "runs": st["runs"],
+                    "regions": st["regions"], "largest_region_intervals": st["largest_region_intervals"],
+                    "launches": st["launches"]}
+            case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+            result["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+        r.close()
     print("wrote", args.out)
 
 

@@ -11,6 +11,10 @@
 // puts a SegmentationRenderUnit (seg_tree.cpp --render_and_save) behind the segmentation and prints a
 // second line, render_frames=N render_fnv1a32=<FNV-1a-32 of the rendered frames' pixel bytes>.
 //
+//   --level_regions <level>
+// asks vsg_render_level_regions for that hierarchy level's regions of every frame and prints a line
+// level_regions=<sum over frames> level_intervals=<sum> level_fnv1a32=<hash of both lists' bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -227,6 +231,65 @@ class RenderHashSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_regions: asks the renderer library for the regions of one hierarchy level of every
+// "SegmentationStream" frame (vsg_render_level_regions) and hashes both lists' bytes, regions first.
+class LevelRegionsSinkUnit : public VideoUnit {
+ public:
+  LevelRegionsSinkUnit(int level, int device) : level_(level), device_(device) {}
+  ~LevelRegionsSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t nr = 0, ni = 0;
+    VF_CHECK(vsg_render_level_regions(render_, seg, desc.wire.size(), level_, nullptr, 0, &nr, nullptr, 0, &ni,
+                                      VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    regions_buf_.resize(nr);
+    intervals_buf_.resize(4 * ni);
+    VF_CHECK(vsg_render_level_regions(render_, seg, desc.wire.size(), level_, regions_buf_.data(), nr, &nr,
+                                      intervals_buf_.data(), ni, &ni, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    Hash(regions_buf_.data(), nr * sizeof(vsg_render_level_region));
+    Hash(intervals_buf_.data(), ni * 4 * sizeof(int32_t));
+    regions_ += (long)nr;
+    intervals_ += (long)ni;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long regions() const { return regions_; }
+  long intervals() const { return intervals_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_region> regions_buf_;
+  std::vector<int32_t> intervals_buf_;
+  long regions_ = 0, intervals_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -315,6 +378,8 @@ struct Flags {
   double render_level = -1;
   bool render_concat = false;
   double render_blend_alpha = 0.5;
+  // vsg_render_level_regions at this level for every frame; < 0: off
+  int level_regions = -1;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -390,6 +455,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "rewrite_pb") f->rewrite_pb = v;
     else if (a == "render_level") f->render_level = atof(v.c_str());
     else if (a == "render_blend_alpha") f->render_blend_alpha = atof(v.c_str());
+    else if (a == "level_regions") f->level_regions = atoi(v.c_str());
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -583,6 +649,14 @@ int main(int argc, char** argv) {
     }
   }
 
+  // the regions of a level, from the descs as the segmentation leaves them (rasters or vector-only)
+  std::unique_ptr<LevelRegionsSinkUnit> level_sink;
+  if (FLAGS.level_regions >= 0) {
+    level_sink.reset(new LevelRegionsSinkUnit(FLAGS.level_regions, FLAGS.device));
+    level_sink->AttachTo(input);
+    input = level_sink.get();
+  }
+
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
   if (FLAGS.render_level >= 0) {
@@ -624,6 +698,10 @@ int main(int argc, char** argv) {
   if (render_unit) {
     std::printf("render_frames=%d render_fnv1a32=%08x render_level=%d\n", render_sink.frames(), render_sink.hash(),
                 render_unit->hierarchy_level());
+  }
+  if (level_sink) {
+    std::printf("level_regions=%ld level_intervals=%ld level_fnv1a32=%08x\n", level_sink->regions(),
+                level_sink->intervals(), level_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

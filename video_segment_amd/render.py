@@ -45,11 +45,31 @@ class VsgRenderVectorStats(_capi.Structure):
     ]
 
 
+class VsgRenderLevelStats(_capi.Structure):
+    _fields_ = [
+        ("runs", C.c_int64), ("regions", C.c_int64), ("largest_region_intervals", C.c_int64),
+        ("runs_us", C.c_float), ("sort_us", C.c_float), ("table_us", C.c_float), ("moments_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
+# vsg_render_level_region: 56 bytes, no padding
+LEVEL_REGION_DTYPE = np.dtype([
+    ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
+    ("min_x", np.int32), ("min_y", np.int32), ("max_x", np.int32), ("max_y", np.int32),
+    ("size", np.float32), ("mean_x", np.float32), ("mean_y", np.float32),
+    ("moment_xx", np.float32), ("moment_xy", np.float32), ("moment_yy", np.float32),
+])
+assert LEVEL_REGION_DTYPE.itemsize == 56
+LEVEL_REGION_WORDS = 14
+
+
 # Every symbol include/vsg_render.h declares.
 EXPORTED_SYMBOLS = [
     "vsg_render_last_error", "vsg_render_default_options", "vsg_render_create", "vsg_render_destroy",
     "vsg_render_frame", "vsg_render_id_image", "vsg_render_level", "vsg_render_default_stride",
     "vsg_render_last_stats", "vsg_render_color", "vsg_render_rasterize", "vsg_render_last_vector_stats",
+    "vsg_render_level_regions", "vsg_render_last_level_stats",
 ]
 
 
@@ -84,6 +104,9 @@ def lib():
     L.vsg_render_color.restype = None
     L.vsg_render_rasterize.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_vector_stats.argtypes = [vp, C.POINTER(VsgRenderVectorStats)]
+    L.vsg_render_level_regions.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                           vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_level_stats.argtypes = [vp, C.POINTER(VsgRenderLevelStats)]
     _handle = L
     return L
 
@@ -193,6 +216,48 @@ class SegmentationRenderer(_capi.Handle):
         p, mem = _capi.contiguous_ptr(out)
         check(lib().vsg_render_rasterize(self.h, seg_bytes, len(seg_bytes), p, out.shape[0], C.byref(n), mem))
         return out[:n.value]
+
+    def level_regions(self, seg_bytes, level=0, regions_out=None, intervals_out=None):
+        """The regions of hierarchy level `level` (GetCompoundRegionRasterizations, RasterizationArea,
+        ShapeMomentsFromRasterization): (regions, intervals).  regions: a LEVEL_REGION_DTYPE array
+        ordered by id; intervals: (n, 4) int32 {y, left_x, right_x, region id}, grouped by region in
+        that order.  Without outputs the counts are asked for first and both arrays are allocated
+        exactly.  regions_out / intervals_out: buffers to fill instead, both numpy (a LEVEL_REGION_DTYPE
+        array and a (capacity, 4) int32 array) or both torch CUDA tensors ((capacity, 14) int32, the
+        float fields as bit views, and (capacity, 4) int32); the filled parts of them are returned."""
+        seg_bytes = bytes(seg_bytes)
+        nr, ni = C.c_size_t(), C.c_size_t()
+        if (regions_out is None) != (intervals_out is None):
+            raise ValueError("pass both outputs or neither")
+        if regions_out is None:
+            check(lib().vsg_render_level_regions(self.h, seg_bytes, len(seg_bytes), int(level), None, 0, C.byref(nr),
+                                                 None, 0, C.byref(ni), VSG_MEM_HOST))
+            regions_out = np.empty(nr.value, LEVEL_REGION_DTYPE)
+            intervals_out = np.empty((ni.value, 4), np.int32)
+        if _capi.is_torch(regions_out) != _capi.is_torch(intervals_out):
+            raise ValueError("both outputs have to be numpy arrays or both torch tensors")
+        if _capi.is_torch(regions_out):
+            if (regions_out.dim() != 2 or regions_out.shape[1] != LEVEL_REGION_WORDS
+                    or str(regions_out.dtype) != "torch.int32"):
+                raise ValueError("regions_out has to be (capacity, %d) int32" % LEVEL_REGION_WORDS)
+        elif regions_out.dtype != LEVEL_REGION_DTYPE or regions_out.ndim != 1:
+            raise ValueError("regions_out has to be a one-dimensional LEVEL_REGION_DTYPE array")
+        if (len(intervals_out.shape) != 2 or intervals_out.shape[1] != 4
+                or str(intervals_out.dtype).replace("torch.", "") != "int32"):
+            raise ValueError("intervals_out has to be (capacity, 4) int32")
+        pr, mem = _capi.contiguous_ptr(regions_out)
+        pi, mem_i = _capi.contiguous_ptr(intervals_out)
+        if mem != mem_i:
+            raise ValueError("both outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_regions(self.h, seg_bytes, len(seg_bytes), int(level), pr, regions_out.shape[0],
+                                             C.byref(nr), pi, intervals_out.shape[0], C.byref(ni), mem))
+        return regions_out[:nr.value], intervals_out[:ni.value]
+
+    def last_level_stats(self):
+        """vsg_render_last_level_stats of the last level_regions call, as a dict."""
+        s = VsgRenderLevelStats()
+        check(lib().vsg_render_last_level_stats(self.h, C.byref(s)))
+        return s.as_dict()
 
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""

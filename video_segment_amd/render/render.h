@@ -1,4 +1,5 @@
-// render.h -- launchers of the two render kernels (render.hip), called by render_capi.cpp.
+// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip), called by
+// render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
 
@@ -72,6 +73,43 @@ hipError_t VecSort(void* temp, size_t temp_bytes, const unsigned long long* keys
 void LaunchVecPairs(const unsigned long long* keys, const unsigned long long* vals, const VecLine* lines,
                     uint32_t n_lines, const uint32_t* region_value, uint32_t n_regions, int64_t n, int width,
                     int height, Interval* intervals, VecStatus* status, hipStream_t stream);
+
+// ---- level regions (level.hip): runs, regions and moments from the filled id plane ------------------
+
+constexpr int kLevelRegionWords = 14;   // vsg_render_level_region as int32 words
+
+// Written by the level kernels; read by the host after k_level_runs and at the end of a call.
+struct LevelStatus {
+  uint32_t runs;       // maximal runs of the plane
+  uint32_t overflow;   // a run had no slot: the host's bound on the runs was wrong
+  uint32_t regions;    // distinct ids among the runs
+  uint32_t largest;    // most intervals of one region
+};
+
+// Runs of the H x W id plane (-1: no run): keys[k] = id << 32 | (y * W + left_x), rights[k] = right_x,
+// in no particular order, status->runs of them.  Slots at or beyond `capacity` are not written.
+void LaunchLevelRuns(const int32_t* plane, int pitch, int width, int height, uint32_t capacity,
+                     unsigned long long* keys, uint32_t* rights, LevelStatus* status, hipStream_t stream);
+// Work space of LevelSort and LevelRank (the larger of the two).
+size_t LevelTempBytes(int64_t n, int end_bit);
+// The library radix sort on bits [0, end_bit) of the keys.
+hipError_t LevelSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                     const uint32_t* rights_in, uint32_t* rights_out, int64_t n, int end_bit, hipStream_t stream);
+// rank[i] = number of distinct ids among sorted runs [0, i].
+hipError_t LevelRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, uint32_t* rank, int64_t n,
+                     hipStream_t stream);
+// n sorted runs -> n intervals, and id and first_interval of every region; status->regions.
+// `regions` has room for capacity_regions entries of kLevelRegionWords words.
+void LaunchLevelTable(const unsigned long long* keys_sorted, const uint32_t* rights_sorted, const uint32_t* rank,
+                      uint32_t n, int width, uint32_t capacity_regions, Interval* intervals, int32_t* regions,
+                      LevelStatus* status, hipStream_t stream);
+// The remaining fields of every region; status->largest.
+void LaunchLevelMoments(const Interval* intervals, uint32_t n, uint32_t capacity_regions, int32_t* regions,
+                        LevelStatus* status, hipStream_t stream);
+// Copies status->regions regions and n intervals, or nothing when there are more regions than
+// capacity_regions.
+void LaunchLevelCopy(const int32_t* regions, const Interval* intervals, uint32_t n, uint32_t capacity_regions,
+                     int32_t* regions_out, int32_t* intervals_out, const LevelStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

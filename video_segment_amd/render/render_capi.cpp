@@ -18,11 +18,13 @@
 namespace {
 
 using vsg_render_impl::Interval;
+using vsg_render_impl::LevelStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
 
 enum Stage { STAGE_CLEAR = 0, STAGE_FILL, STAGE_COMPOSE, STAGE_COUNT };
 enum VecStage { VEC_WALK = 0, VEC_SORT, VEC_PAIRS, VEC_COUNT };
+enum LevelStage { LVL_RUNS = 0, LVL_SORT, LVL_TABLE, LVL_MOMENTS, LVL_COUNT };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -320,7 +322,7 @@ struct vsg_render {
   vsg_render_options opt;
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
-  StageClock clock, vclock;   // clear, fill, compose; the vector path's walk, sort, pairs
+  StageClock clock, vclock, lclock;   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -336,9 +338,13 @@ struct vsg_render {
   std::vector<uint32_t> region_value;
   std::vector<float> scaled_mesh;
   Block d_vec_in, d_cross, d_sort_temp, d_status, h_status;
+  // level regions: unsorted runs (keys, right ends), sorted runs with their ranks, the two lists,
+  // the status words, and the pinned block the status and host outputs come back through
+  Block d_runs, d_sorted, d_level_regions, d_level_intervals, d_level_status, h_level;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
+  vsg_render_level_stats lstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -546,6 +552,47 @@ int64_t AssignRegionValues(vsg_render* h, int level, const Hierarchy& hier, Valu
   return (int64_t)seen.size();
 }
 
+// The front half of vsg_render_id_image: ingests the desc, checks the level, maps every region to
+// value_of(its id at `level`) and paints the W-pitched plane `ids` (device memory; -1 where no region
+// is).  Leaves clock between STAGE_FILL and the next mark, and the vector path's status in flight:
+// the caller calls CheckVector after its synchronisation when the desc was vector-only (returned).
+template <class ValueOf>
+bool PaintIds(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint32_t* ids, ValueOf value_of) {
+  const int W = h->W, H = h->H;
+  std::memset(&h->stats, 0, sizeof(h->stats));
+  std::memset(&h->vstats, 0, sizeof(h->vstats));
+  const double t0 = NowMs();
+  bool vector = false;
+  const Hierarchy& hier = Ingest(h, seg, seg_len, &vector);
+  if (level < 0 || (level > 0 && level >= (int)hier.size())) {
+    Throw(VSG_ERR_INVALID, "level " + std::to_string(level) + " is not in the hierarchy (" +
+                               std::to_string(hier.size()) + " levels)");
+  }
+  int64_t n_cross = 0;
+  if (vector) {
+    h->stats.distinct_ids = AssignRegionValues(h, level, hier, value_of);
+    n_cross = h->BuildLines();
+  } else {
+    h->stats.distinct_ids = AssignValues(h, level, hier, value_of);
+  }
+  const int64_t n_intervals = vector ? n_cross / 2 : (int64_t)h->intervals.size();
+  h->stats.intervals = n_intervals;
+  const double t1 = NowMs();
+  h->stats.decode_ms = t1 - t0;
+  if (vector) h->RunVector(n_cross);
+  else h->UploadIntervals();
+  const size_t bytes = (size_t)W * H * sizeof(int32_t);
+  h->stats.upload_ms = NowMs() - t1;
+  h->clock.Begin(h->stream);
+  VSG_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
+  h->clock.Mark(STAGE_CLEAR);
+  vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, W, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->clock.Mark(STAGE_FILL);
+  h->stats.launches += 1 + (n_intervals == 0 ? 0 : 1);
+  return vector;
+}
+
 }  // namespace
 
 extern "C" {
@@ -594,10 +641,13 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->h_intervals.pinned = true;
     h->h_status.pinned = true;
     std::memset(&h->vstats, 0, sizeof(h->vstats));
+    h->h_level.pinned = true;
+    std::memset(&h->lstats, 0, sizeof(h->lstats));
     DeviceGuard guard(h->device);
     VSG_HIP(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
     h->clock.Create(STAGE_COUNT + 1);
     h->vclock.Create(VEC_COUNT + 1);
+    h->lclock.Create(LVL_COUNT + 1);
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -719,52 +769,171 @@ int vsg_render_id_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int l
     if (!h) Throw(VSG_ERR_INVALID, "handle is null");
     if (!out) Throw(VSG_ERR_INVALID, "out is null");
     CheckMem(mem_out, "out");
-    const int W = h->W, H = h->H;
+    const size_t bytes = (size_t)h->W * h->H * sizeof(int32_t);
     DeviceGuard guard(h->device);
-    std::memset(&h->stats, 0, sizeof(h->stats));
-    std::memset(&h->vstats, 0, sizeof(h->vstats));
-    const double t0 = NowMs();
-    bool vector = false;
-    const Hierarchy& hier = Ingest(h, seg, seg_len, &vector);
-    if (level < 0 || (level > 0 && level >= (int)hier.size())) {
-      Throw(VSG_ERR_INVALID, "level " + std::to_string(level) + " is not in the hierarchy (" +
-                                 std::to_string(hier.size()) + " levels)");
-    }
-    auto id_of = [](int mapped) { return (uint32_t)mapped; };
-    int64_t n_cross = 0;
-    if (vector) {
-      h->stats.distinct_ids = AssignRegionValues(h, level, hier, id_of);
-      n_cross = h->BuildLines();
-    } else {
-      h->stats.distinct_ids = AssignValues(h, level, hier, id_of);
-    }
-    const int64_t n_intervals = vector ? n_cross / 2 : (int64_t)h->intervals.size();
-    h->stats.intervals = n_intervals;
-    const double t1 = NowMs();
-    h->stats.decode_ms = t1 - t0;
-    if (vector) h->RunVector(n_cross);
-    else h->UploadIntervals();
-    const size_t bytes = (size_t)W * H * sizeof(int32_t);
     uint32_t* ids = reinterpret_cast<uint32_t*>(out);   // device output: painted in place
     if (mem_out == VSG_MEM_HOST) {
       h->d_ids.Reserve(bytes, &h->allocations);
       ids = static_cast<uint32_t*>(h->d_ids.p);
     }
-    h->stats.upload_ms = NowMs() - t1;
-    h->clock.Begin(h->stream);
-    VSG_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
-    h->clock.Mark(STAGE_CLEAR);
-    vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, W, h->stream);
-    VSG_HIP(hipGetLastError());
-    h->clock.Mark(STAGE_FILL);
+    const bool vector = PaintIds(h, seg, seg_len, level, ids, [](int mapped) { return (uint32_t)mapped; });
     h->clock.Mark(STAGE_COMPOSE);   // nothing is composed: the two marks are back to back
-    h->stats.launches += 1 + (n_intervals == 0 ? 0 : 1);
     if (mem_out == VSG_MEM_HOST) {
       VSG_HIP(hipMemcpyAsync(out, ids, bytes, hipMemcpyDeviceToHost, h->stream));
       ++h->stats.launches;
     }
     h->FinishStats();
     if (vector) h->CheckVector();
+  });
+}
+
+int vsg_render_level_regions(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
+                             vsg_render_level_region* regions, size_t capacity_regions, size_t* num_regions,
+                             int32_t* intervals, size_t capacity_intervals, size_t* num_intervals, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_level_region) == kLevelRegionWords * sizeof(int32_t), "moved as int32 words");
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_regions || !num_intervals) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_regions = *num_intervals = 0;
+    CheckMem(mem_out, "outputs");
+    const bool count_only = !regions && !intervals && capacity_regions == 0 && capacity_intervals == 0;
+    const int W = h->W, H = h->H;
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+    DeviceGuard guard(h->device);
+    std::memset(&h->lstats, 0, sizeof(h->lstats));
+
+    // ---- the id plane, as vsg_render_id_image paints it ----
+    h->d_ids.Reserve((size_t)W * H * sizeof(int32_t), &h->allocations);
+    int32_t max_id = 0;
+    const bool vector = PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(), [&](int mapped) {
+      // -1 is the plane's "no region"; the sort key takes the id as an unsigned number
+      if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
+      max_id = std::max(max_id, mapped);
+      return (uint32_t)mapped;
+    });
+
+    // ---- runs ----
+    // Intervals that do not overlap give at most one run each; every end of an interval that lies
+    // on another one can add a run.  The kernel drops what has no slot and says so.
+    const uint64_t painted = (uint64_t)h->stats.intervals;
+    const uint32_t cap_runs = (uint32_t)std::min<uint64_t>(2 * painted + 1, (uint64_t)W * H);
+    h->d_runs.Reserve((size_t)cap_runs * 12, &h->allocations);
+    h->d_level_status.Reserve(sizeof(LevelStatus), &h->allocations);
+    h->h_level.Reserve(2 * sizeof(LevelStatus), &h->allocations);
+    unsigned long long* keys = h->d_runs.As<unsigned long long>();
+    uint32_t* rights = reinterpret_cast<uint32_t*>(keys + cap_runs);
+    LevelStatus* status = h->d_level_status.As<LevelStatus>();
+    LevelStatus* seen = h->h_level.As<LevelStatus>();   // [0] after the runs, [1] at the end
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(LevelStatus), h->stream));
+    h->lclock.Begin(h->stream);
+    LaunchLevelRuns(h->d_ids.As<int32_t>(), W, W, H, cap_runs, keys, rights, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->lclock.Mark(LVL_RUNS);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
+    h->lstats.launches = 3;
+    VSG_HIP(hipStreamSynchronize(h->stream));   // the run count sizes everything below
+    {
+      float us[STAGE_COUNT], lus[LVL_COUNT];
+      h->clock.Read(us, STAGE_COUNT);
+      h->stats.clear_us = us[STAGE_CLEAR];
+      h->stats.fill_us = us[STAGE_FILL];
+      h->lclock.Read(lus, LVL_COUNT);
+      h->lstats.runs_us = lus[LVL_RUNS];
+    }
+    if (vector) h->CheckVector();
+    if (seen[0].overflow || seen[0].runs > cap_runs) Throw(VSG_ERR_INTERNAL, "more runs than the intervals allow");
+    const uint32_t n = seen[0].runs;
+    h->lstats.runs = n;
+    *num_intervals = n;
+
+    // ---- sort, table, moments, outputs ----
+    // every region has a run, and every id of the plane is one of the host's distinct mapped ids
+    const uint32_t cap_regions = (uint32_t)std::min<uint64_t>(n, (uint64_t)h->stats.distinct_ids);
+    const bool intervals_fit = n <= capacity_intervals;
+    const bool deliver = !count_only && intervals_fit;
+    const size_t region_bytes = (size_t)cap_regions * sizeof(vsg_render_level_region);
+    const size_t interval_bytes = (size_t)n * sizeof(Interval);
+    if (deliver && n && (!regions || !intervals)) Throw(VSG_ERR_INVALID, "an output is null");
+    if (n) {
+      int id_bits = 1;
+      while (id_bits < 31 && (max_id >> id_bits)) ++id_bits;
+      const int end_bit = 32 + id_bits;
+      const size_t temp_bytes = std::max<size_t>(LevelTempBytes(n, end_bit), 16);
+      h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+      h->d_sorted.Reserve((size_t)n * 16, &h->allocations);
+      h->d_level_regions.Reserve(region_bytes, &h->allocations);
+      h->d_level_intervals.Reserve(interval_bytes, &h->allocations);
+      unsigned long long* keys_sorted = h->d_sorted.As<unsigned long long>();
+      uint32_t* rights_sorted = reinterpret_cast<uint32_t*>(keys_sorted + n);
+      uint32_t* rank = rights_sorted + n;
+      int32_t* d_regions = h->d_level_regions.As<int32_t>();
+      Interval* d_intervals = h->d_level_intervals.As<Interval>();
+      h->lclock.Begin(h->stream);
+      VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, rights, rights_sorted, n, end_bit, h->stream));
+      h->lclock.Mark(LVL_SORT);
+      VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, keys_sorted, rank, n, h->stream));
+      LaunchLevelTable(keys_sorted, rights_sorted, rank, n, W, cap_regions, d_intervals, d_regions, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      h->lclock.Mark(LVL_TABLE);
+      h->lstats.launches += 3;   // the sort and the scan count as one each
+      if (!count_only) {
+        LaunchLevelMoments(d_intervals, n, cap_regions, d_regions, status, h->stream);
+        VSG_HIP(hipGetLastError());
+        h->lclock.Mark(LVL_MOMENTS);
+        ++h->lstats.launches;
+      }
+      if (deliver && mem_out == VSG_MEM_DEVICE) {
+        // the number of regions is on the device: the copy decides there whether they fit
+        LaunchLevelCopy(d_regions, d_intervals, n, (uint32_t)std::min<size_t>(capacity_regions, cap_regions),
+                        reinterpret_cast<int32_t*>(regions), intervals, status, h->stream);
+        VSG_HIP(hipGetLastError());
+        ++h->lstats.launches;
+      } else if (deliver) {
+        // through the pinned block; handed to the caller once the number of regions is known
+        h->h_level.Reserve(2 * sizeof(LevelStatus) + region_bytes + interval_bytes, &h->allocations);
+        seen = h->h_level.As<LevelStatus>();
+        char* stage = reinterpret_cast<char*>(seen + 2);
+        VSG_HIP(hipMemcpyAsync(stage, d_regions, region_bytes, hipMemcpyDeviceToHost, h->stream));
+        VSG_HIP(hipMemcpyAsync(stage + region_bytes, d_intervals, interval_bytes, hipMemcpyDeviceToHost, h->stream));
+        h->lstats.launches += 2;
+      }
+      VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
+      ++h->lstats.launches;
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      if (seen[1].regions == 0 || seen[1].regions > cap_regions) {
+        Throw(VSG_ERR_INTERNAL, "the plane has more regions than the desc has ids");
+      }
+      float us[LVL_COUNT];
+      h->lclock.Read(us, LVL_COUNT);
+      h->lstats.sort_us = us[LVL_SORT];
+      h->lstats.table_us = us[LVL_TABLE];
+      h->lstats.moments_us = us[LVL_MOMENTS];
+      h->lstats.regions = seen[1].regions;
+      h->lstats.largest_region_intervals = seen[1].largest;
+    }
+    h->stats.launches += h->lstats.launches;
+    h->stats.device_allocations = h->allocations;
+    const size_t n_regions = (size_t)h->lstats.regions;
+    *num_regions = n_regions;
+    if (count_only) return;
+    if (!intervals_fit || n_regions > capacity_regions) {
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_regions) + " regions and " + std::to_string(n) +
+                                 " intervals, the capacities are " + std::to_string(capacity_regions) + " and " +
+                                 std::to_string(capacity_intervals));
+    }
+    if (n && mem_out == VSG_MEM_HOST) {
+      const char* stage = reinterpret_cast<const char*>(h->h_level.As<LevelStatus>() + 2);
+      std::memcpy(regions, stage, n_regions * sizeof(vsg_render_level_region));
+      std::memcpy(intervals, stage + region_bytes, interval_bytes);
+    }
+  });
+}
+
+int vsg_render_last_level_stats(vsg_render* h, vsg_render_level_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->lstats;
   });
 }
 
