@@ -36,7 +36,11 @@
  * frame therefore equals the reference's up to those text pixels.  The inputs of
  * draw_shape_descriptors are available, though: vsg_render_level_regions returns every region of a
  * level with its merged rasterization, its area and its shape moments; the ellipse's axes and angle
- * (GetShapeDescriptorFromShapeMoments) and the drawing itself are left to the caller.
+ * (GetShapeDescriptorFromShapeMoments) and the drawing itself are left to the caller.  A region of a
+ * level above 0 is usually several blobs in one frame; vsg_render_level_components returns the same
+ * per connected component.  Boundary point lists (GetBoundary, segmentation/boundary.cpp) are not
+ * offered either, with and without that call: it splits a region as GetBoundary's first step does
+ * and traces nothing.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -200,6 +204,69 @@ typedef struct vsg_render_level_stats {
   int launches;
 } vsg_render_level_stats;
 int vsg_render_last_level_stats(vsg_render* h, vsg_render_level_stats* s);
+
+#define VSG_RENDER_CONNECT_N4 1   /* SegmentationDesc::N4_CONNECT */
+#define VSG_RENDER_CONNECT_N8 2   /* SegmentationDesc::N8_CONNECT */
+
+/* One connected component of a region of a hierarchy level, as vsg_render_level_components returns
+ * it. */
+typedef struct vsg_render_level_component {   /* 64 bytes, no padding */
+  int32_t id;                 /* region id at `level` */
+  int32_t component;          /* 0-based index among its region's components, reference order */
+  int32_t region_components;  /* how many components that region has */
+  int32_t first_interval, num_intervals;
+  int32_t area;
+  int32_t min_x, min_y, max_x, max_y;
+  float size, mean_x, mean_y, moment_xx, moment_xy, moment_yy;
+} vsg_render_level_component;
+
+/* The connected components of every region of hierarchy level `level`: ConnectedComponents
+ * (segment_util/segmentation_util.cpp:1007-1101) applied to each region's rasterization, with
+ * RasterizationArea and ShapeMomentsFromRasterization of every component, computed on the device.
+ *
+ * Input is the id plane of vsg_render_id_image at `level`; decode, hierarchy rules, refusals and the
+ * handling of vector-only descs are those of vsg_render_level_regions, region ids have to be
+ * non-negative, and pixels without a region (-1) belong to no component.  A region's rasterization is
+ * the list vsg_render_level_regions returns: its maximal runs per row in (y, left_x) order.
+ * Two runs of one region are neighbours as in ScanIntervalsNeighbored: |dy| <= 1 and, for
+ * VSG_RENDER_CONNECT_N4, max(left_x) <= min(right_x); for VSG_RENDER_CONNECT_N8,
+ * max(left_x) - min(right_x) <= 1.  Maximal runs never touch within a row, so only runs of adjacent
+ * rows are neighbours, and the components are exactly the 4-connected (8-connected) components of
+ * the pixels of each id.  Any other connectedness is VSG_ERR_INVALID.
+ * Order is that of ConnectedComponents' second loop: a region's components are ordered by the first
+ * appearance of their intervals in the region's list, that is by their first pixel in row-major
+ * order, and a component keeps its intervals in list order.  Regions are ordered by ascending id.
+ * area, bounding box and moments are RasterizationArea and ShapeMomentsFromRasterization applied to
+ * the component's interval list in that order, f32 operation for operation, by the kernel that
+ * computes them for vsg_render_level_regions.
+ *
+ * components: ordered by (id, component).  intervals: int32 quadruples {y, left_x, right_x,
+ * region_id}, grouped by component in the order of the component list.  label_image: NULL, or W*H
+ * int32 that receive the index of each pixel's component in the component list, -1 where there is
+ * none.  All in mem_out memory.
+ * *num_components and *num_intervals are always set on VSG_OK and when a capacity is too small; in
+ * that case the call fails with VSG_ERR_INVALID and no output is touched, the label image included.
+ * components == NULL, intervals == NULL and label_image == NULL with both capacities 0 asks for the
+ * counts only (VSG_OK; needs the device).  A null handle, a null count pointer or a bad connectedness
+ * is VSG_ERR_INVALID and touches no device. */
+int vsg_render_level_components(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                                vsg_render_level_component* components, size_t capacity_components, size_t* num_components,
+                                int32_t* intervals, size_t capacity_intervals, size_t* num_intervals,
+                                int32_t* label_image, int mem_out);
+
+/* What the last vsg_render_level_components call of the handle did.  links: neighbour pairs found
+ * between adjacent rows (fewer than 2 * runs).  Device times are HIP events around the stages:
+ * k_level_runs; the radix sort, the scan and k_level_table of the runs; the union-find (k_comp_init,
+ * k_comp_link, k_comp_flatten); the radix sort by component, the scan, k_comp_table and
+ * k_comp_finish; the moments; the label image's clear and fill.  The time the stream idles while the
+ * host reads the number of components is in none of them.  The last two are not run, and
+ * largest_component_intervals is not known, in a count-only or refused call. */
+typedef struct vsg_render_component_stats {
+  int64_t runs, regions, components, links, largest_component_intervals;
+  float runs_us, sort_us, link_us, order_us, moments_us, label_us;
+  int launches;
+} vsg_render_component_stats;
+int vsg_render_last_component_stats(vsg_render* h, vsg_render_component_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

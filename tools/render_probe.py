@@ -25,6 +25,14 @@ The level leg: a dense-unit chunk result given a hierarchy by RegionSegmentation
 call the four stage times of vsg_render_level_stats, the launch count and the runs of the frame are
 recorded; in the same run vsg_render_id_image on the same desc and level is timed, which is what
 painting the plane the answer is read from costs.  No pass or fail threshold.
+
+    python tools/render_probe.py --level-components [--reps 30] [--out profiles/level_components.json]
+
+The component leg: the same descs and levels asked for their connected components
+(vsg_render_level_components, N4 and N8, lists and label image in device memory).  Per call the six
+stage times of vsg_render_component_stats, launches, runs, links and components are recorded; in the
+same run vsg_render_level_regions on the same desc and handle is timed with its four stage times: the
+yardstick.  No pass or fail threshold.
 """
 import argparse
 import json
@@ -53,11 +61,14 @@ def main():
     ap.add_argument("--vector", action="store_true", help="the vector leg instead (profiles/vector_raster.json)")
     ap.add_argument("--level-regions", action="store_true",
                     help="the level leg instead (profiles/level_regions.json)")
+    ap.add_argument("--level-components", action="store_true",
+                    help="the component leg instead (profiles/level_components.json)")
     args = ap.parse_args()
-    if args.level_regions and "--reps" not in sys.argv:
+    if (args.level_regions or args.level_components) and "--reps" not in sys.argv:
         args.reps = 30
     if args.out is None:
-        name = "level_regions.json" if args.level_regions else "vector_raster.json" if args.vector else "render_kernels.json"
+        name = ("level_components.json" if args.level_components else "level_regions.json" if args.level_regions
+                else "vector_raster.json" if args.vector else "render_kernels.json")
         args.out = os.path.join(ROOT, "profiles", name)
 
     import torch
@@ -70,6 +81,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.level_components:
+        return components_leg(args, result, dev)
     if args.level_regions:
         return level_leg(args, result, dev)
     for size in args.sizes.split(","):
@@ -192,11 +205,10 @@ def vector_leg(args, result, dev):
     print("wrote", args.out)
 
 
-def level_leg(args, result, dev):
-    import torch
+def level_descs(args):
+    """Per size: (size, W, H, a dense-unit desc that carries a hierarchy, its height)."""
     import synth
     import video_segment_amd as vsg
-    from video_segment_amd import render
     from test_proto_wire import build_schema
     Msg = build_schema()
     for size in args.sizes.split(","):
@@ -217,11 +229,18 @@ def level_leg(args, result, dev):
         reg.close()
         m = Msg()
         m.ParseFromString(segs[0])          # the chunk's first frame carries the hierarchy
-        height = len(m.hierarchy)
+        yield size, W, H, segs[0], len(m.hierarchy)
+
+
+def level_leg(args, result, dev):
+    import torch
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    for size, W, H, seg0, height in level_descs(args):
         r = vsg.SegmentationRenderer(W, H, has_video=False)
         ids = torch.empty((H, W), dtype=torch.int32, device=dev)
         for level in sorted({0, height // 2, max(height - 1, 0)}):
-            nr, ni = (len(a) for a in r.level_regions(segs[0], level))
+            nr, ni = (len(a) for a in r.level_regions(seg0, level))
             regions = torch.empty((nr, render.LEVEL_REGION_WORDS), dtype=torch.int32, device=dev)
             intervals = torch.empty((ni, 4), dtype=torch.int32, device=dev)
             keys = ["runs_us", "sort_us", "table_us", "moments_us", "call_ms", "id_image_call_ms", "id_image_fill_us",
@@ -229,10 +248,10 @@ def level_leg(args, result, dev):
             rows = {k: [] for k in keys}
             for it in range(args.warmup + args.reps):
                 t0 = time.perf_counter()
-                r.level_regions(segs[0], level, regions_out=regions, intervals_out=intervals)
+                r.level_regions(seg0, level, regions_out=regions, intervals_out=intervals)
                 st = dict(r.last_level_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
                 t0 = time.perf_counter()
-                r.id_image(segs[0], level, out=ids)
+                r.id_image(seg0, level, out=ids)
                 ist = r.last_stats()
                 st.update(id_image_call_ms=(time.perf_counter() - t0) * 1e3, id_image_fill_us=ist["fill_us"],
                           id_image_clear_us=ist["clear_us"])
@@ -248,6 +267,52 @@ def level_leg(args, result, dev):
             with open(args.out, "w") as f:
                 json.dump(result, f, indent=1)
                 f.write("\n")
+        r.close()
+    print("wrote", args.out)
+
+
+def components_leg(args, result, dev):
+    import torch
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    for size, W, H, seg, height in level_descs(args):
+        r = vsg.SegmentationRenderer(W, H, has_video=False)
+        labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+        for level in sorted({0, height // 2, max(height - 1, 0)}):
+            nr, ni = (len(a) for a in r.level_regions(seg, level))
+            regions = torch.empty((nr, render.LEVEL_REGION_WORDS), dtype=torch.int32, device=dev)
+            intervals = torch.empty((ni, 4), dtype=torch.int32, device=dev)
+            for name, connect in (("N4", render.N4), ("N8", render.N8)):
+                nc = len(r.level_components(seg, level, connect)[0])
+                comps = torch.empty((nc, render.LEVEL_COMPONENT_WORDS), dtype=torch.int32, device=dev)
+                stage_keys = ["runs_us", "sort_us", "link_us", "order_us", "moments_us", "label_us"]
+                region_keys = ["runs_us", "sort_us", "table_us", "moments_us"]
+                rows = {k: [] for k in stage_keys + ["call_ms", "level_regions_call_ms"]
+                        + ["level_regions_" + k for k in region_keys]}
+                for it in range(args.warmup + args.reps):
+                    t0 = time.perf_counter()
+                    r.level_components(seg, level, connect, components_out=comps, intervals_out=intervals,
+                                       labels_out=labels)
+                    st = dict(r.last_component_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
+                    t0 = time.perf_counter()
+                    r.level_regions(seg, level, regions_out=regions, intervals_out=intervals)
+                    st["level_regions_call_ms"] = (time.perf_counter() - t0) * 1e3
+                    lst = r.last_level_stats()
+                    st.update({"level_regions_" + k: lst[k] for k in region_keys})
+                    if it >= args.warmup:
+                        for k in rows:
+                            rows[k].append(st[k])
+                case = {"size": size, "level": level, "hierarchy_levels": height, "connectedness": name,
+                        "runs": st["runs"], "regions": st["regions"], "components": st["components"],
+                        "links": st["links"], "largest_component_intervals": st["largest_component_intervals"],
+                        "largest_region_intervals": lst["largest_region_intervals"], "launches": st["launches"],
+                        "level_regions_launches": lst["launches"]}
+                case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+                result["cases"].append(case)
+                print(json.dumps(case), flush=True)
+                with open(args.out, "w") as f:
+                    json.dump(result, f, indent=1)
+                    f.write("\n")
         r.close()
     print("wrote", args.out)
 

@@ -15,6 +15,11 @@
 // asks vsg_render_level_regions for that hierarchy level's regions of every frame and prints a line
 // level_regions=<sum over frames> level_intervals=<sum> level_fnv1a32=<hash of both lists' bytes>.
 //
+//   --level_components <level> [--components_n8]
+// asks vsg_render_level_components for the connected components (N4, or N8) of that level's regions of
+// every frame and prints a line
+// level_components=<sum> component_intervals=<sum> component_fnv1a32=<hash of both lists' bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -290,6 +295,66 @@ class LevelRegionsSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_components: the same for the connected components of a level's regions
+// (vsg_render_level_components), components first.
+class LevelComponentsSinkUnit : public VideoUnit {
+ public:
+  LevelComponentsSinkUnit(int level, bool n8, int device)
+      : level_(level), connect_(n8 ? VSG_RENDER_CONNECT_N8 : VSG_RENDER_CONNECT_N4), device_(device) {}
+  ~LevelComponentsSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t nc = 0, ni = 0;
+    VF_CHECK(vsg_render_level_components(render_, seg, desc.wire.size(), level_, connect_, nullptr, 0, &nc, nullptr,
+                                         0, &ni, nullptr, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    components_buf_.resize(nc);
+    intervals_buf_.resize(4 * ni);
+    VF_CHECK(vsg_render_level_components(render_, seg, desc.wire.size(), level_, connect_, components_buf_.data(), nc,
+                                         &nc, intervals_buf_.data(), ni, &ni, nullptr, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    Hash(components_buf_.data(), nc * sizeof(vsg_render_level_component));
+    Hash(intervals_buf_.data(), ni * 4 * sizeof(int32_t));
+    components_ += (long)nc;
+    intervals_ += (long)ni;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long components() const { return components_; }
+  long intervals() const { return intervals_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_component> components_buf_;
+  std::vector<int32_t> intervals_buf_;
+  long components_ = 0, intervals_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -380,6 +445,9 @@ struct Flags {
   double render_blend_alpha = 0.5;
   // vsg_render_level_regions at this level for every frame; < 0: off
   int level_regions = -1;
+  // vsg_render_level_components at this level for every frame; < 0: off.  N4, or N8 with --components_n8
+  int level_components = -1;
+  bool components_n8 = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -411,7 +479,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     }
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
-                                   "compute_flow", "remove_rasterization", "run_on_server", "help"};
+                                   "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
+                                   "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -456,6 +525,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "render_level") f->render_level = atof(v.c_str());
     else if (a == "render_blend_alpha") f->render_blend_alpha = atof(v.c_str());
     else if (a == "level_regions") f->level_regions = atoi(v.c_str());
+    else if (a == "level_components") f->level_components = atoi(v.c_str());
+    else if (a == "components_n8") f->components_n8 = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -656,6 +727,12 @@ int main(int argc, char** argv) {
     level_sink->AttachTo(input);
     input = level_sink.get();
   }
+  std::unique_ptr<LevelComponentsSinkUnit> components_sink;
+  if (FLAGS.level_components >= 0) {
+    components_sink.reset(new LevelComponentsSinkUnit(FLAGS.level_components, FLAGS.components_n8, FLAGS.device));
+    components_sink->AttachTo(input);
+    input = components_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -702,6 +779,10 @@ int main(int argc, char** argv) {
   if (level_sink) {
     std::printf("level_regions=%ld level_intervals=%ld level_fnv1a32=%08x\n", level_sink->regions(),
                 level_sink->intervals(), level_sink->hash());
+  }
+  if (components_sink) {
+    std::printf("level_components=%ld component_intervals=%ld component_fnv1a32=%08x\n", components_sink->components(),
+                components_sink->intervals(), components_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

@@ -53,6 +53,16 @@ class VsgRenderLevelStats(_capi.Structure):
     ]
 
 
+class VsgRenderComponentStats(_capi.Structure):
+    _fields_ = [
+        ("runs", C.c_int64), ("regions", C.c_int64), ("components", C.c_int64), ("links", C.c_int64),
+        ("largest_component_intervals", C.c_int64),
+        ("runs_us", C.c_float), ("sort_us", C.c_float), ("link_us", C.c_float), ("order_us", C.c_float),
+        ("moments_us", C.c_float), ("label_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -63,6 +73,21 @@ LEVEL_REGION_DTYPE = np.dtype([
 assert LEVEL_REGION_DTYPE.itemsize == 56
 LEVEL_REGION_WORDS = 14
 
+# vsg_render_level_component: 64 bytes, no padding
+LEVEL_COMPONENT_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("region_components", np.int32),
+    ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
+    ("min_x", np.int32), ("min_y", np.int32), ("max_x", np.int32), ("max_y", np.int32),
+    ("size", np.float32), ("mean_x", np.float32), ("mean_y", np.float32),
+    ("moment_xx", np.float32), ("moment_xy", np.float32), ("moment_yy", np.float32),
+])
+assert LEVEL_COMPONENT_DTYPE.itemsize == 64
+LEVEL_COMPONENT_WORDS = 16
+
+# VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
+N4 = 1
+N8 = 2
+
 
 # Every symbol include/vsg_render.h declares.
 EXPORTED_SYMBOLS = [
@@ -70,6 +95,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_frame", "vsg_render_id_image", "vsg_render_level", "vsg_render_default_stride",
     "vsg_render_last_stats", "vsg_render_color", "vsg_render_rasterize", "vsg_render_last_vector_stats",
     "vsg_render_level_regions", "vsg_render_last_level_stats",
+    "vsg_render_level_components", "vsg_render_last_component_stats",
 ]
 
 
@@ -107,6 +133,10 @@ def lib():
     L.vsg_render_level_regions.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t),
                                            vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_level_stats.argtypes = [vp, C.POINTER(VsgRenderLevelStats)]
+    L.vsg_render_level_components.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t,
+                                              C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp,
+                                              C.c_int]
+    L.vsg_render_last_component_stats.argtypes = [vp, C.POINTER(VsgRenderComponentStats)]
     _handle = L
     return L
 
@@ -257,6 +287,72 @@ class SegmentationRenderer(_capi.Handle):
         """vsg_render_last_level_stats of the last level_regions call, as a dict."""
         s = VsgRenderLevelStats()
         check(lib().vsg_render_last_level_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def level_components(self, seg_bytes, level=0, connectedness=N4, label_image=False, components_out=None,
+                         intervals_out=None, labels_out=None):
+        """The connected components (N4 or N8) of every region of hierarchy level `level`, in the
+        reference's ConnectedComponents order: (components, intervals), or (components, intervals,
+        labels) with label_image=True or a labels_out.  components: a LEVEL_COMPONENT_DTYPE array ordered
+        by (id, component); intervals: (n, 4) int32 {y, left_x, right_x, region id} grouped by component
+        in that order; labels: H x W int32, the index of each pixel's component in `components`, -1
+        where there is none.  Without outputs the counts are asked for first and the arrays are
+        allocated exactly.  components_out / intervals_out (both or neither) and labels_out: buffers to
+        fill instead, all numpy (a LEVEL_COMPONENT_DTYPE array, a (capacity, 4) int32 array, an H x W
+        int32 array) or all torch CUDA tensors ((capacity, 16) int32 with the float fields as bit views,
+        (capacity, 4) int32, H x W int32); the filled parts are returned."""
+        seg_bytes = bytes(seg_bytes)
+        nc, ni = C.c_size_t(), C.c_size_t()
+        if (components_out is None) != (intervals_out is None):
+            raise ValueError("pass both list outputs or neither")
+        if components_out is None:
+            if labels_out is not None and _capi.is_torch(labels_out):
+                raise ValueError("a torch labels_out needs torch components_out and intervals_out")
+            check(lib().vsg_render_level_components(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                    None, 0, C.byref(nc), None, 0, C.byref(ni), None, VSG_MEM_HOST))
+            components_out = np.empty(nc.value, LEVEL_COMPONENT_DTYPE)
+            intervals_out = np.empty((ni.value, 4), np.int32)
+        torch_out = _capi.is_torch(components_out)
+        if torch_out != _capi.is_torch(intervals_out):
+            raise ValueError("both list outputs have to be numpy arrays or both torch tensors")
+        if torch_out:
+            if (components_out.dim() != 2 or components_out.shape[1] != LEVEL_COMPONENT_WORDS
+                    or str(components_out.dtype) != "torch.int32"):
+                raise ValueError("components_out has to be (capacity, %d) int32" % LEVEL_COMPONENT_WORDS)
+        elif components_out.dtype != LEVEL_COMPONENT_DTYPE or components_out.ndim != 1:
+            raise ValueError("components_out has to be a one-dimensional LEVEL_COMPONENT_DTYPE array")
+        if (len(intervals_out.shape) != 2 or intervals_out.shape[1] != 4
+                or str(intervals_out.dtype).replace("torch.", "") != "int32"):
+            raise ValueError("intervals_out has to be (capacity, 4) int32")
+        pc, mem = _capi.contiguous_ptr(components_out)
+        pi, mem_i = _capi.contiguous_ptr(intervals_out)
+        if mem != mem_i:
+            raise ValueError("all outputs have to be in the same kind of memory")
+        pl = None
+        if labels_out is None and label_image:
+            if torch_out:
+                import torch
+                labels_out = torch.empty((self.H, self.W), dtype=torch.int32, device=components_out.device)
+            else:
+                labels_out = np.empty((self.H, self.W), np.int32)
+        if labels_out is not None:
+            if (tuple(labels_out.shape) != (self.H, self.W)
+                    or str(labels_out.dtype).replace("torch.", "") != "int32"):
+                raise ValueError("labels_out has to be %d x %d int32" % (self.H, self.W))
+            pl, mem_l = _capi.contiguous_ptr(labels_out)
+            if mem_l != mem:
+                raise ValueError("all outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_components(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                pc, components_out.shape[0], C.byref(nc), pi, intervals_out.shape[0],
+                                                C.byref(ni), pl, mem))
+        if labels_out is None:
+            return components_out[:nc.value], intervals_out[:ni.value]
+        return components_out[:nc.value], intervals_out[:ni.value], labels_out
+
+    def last_component_stats(self):
+        """vsg_render_last_component_stats of the last level_components call, as a dict."""
+        s = VsgRenderComponentStats()
+        check(lib().vsg_render_last_component_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def last_vector_stats(self):

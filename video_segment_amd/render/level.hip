@@ -9,7 +9,7 @@
 //   k_level_table    one thread per sorted run: its interval {y, left_x, right_x, id}; a segment head
 //                    also writes its region's id and first interval
 //   k_level_moments  one wavefront per region: area, bounding box, and the reference's six f32 sums
-//                    in interval order
+//                    in interval order (also run per connected component, on the table of components.hip)
 //   k_level_copy     regions and intervals to the caller's device memory, if the regions fit
 //
 // The moments' arithmetic is the reference's, operation for operation; every operation is rounded on
@@ -137,18 +137,23 @@ __device__ __forceinline__ float LaneValue(float v, int lane) {
 // after the other, in interval order, as ShapeMomentsFromRasterization's loop does
 // (segmentation_util.cpp:663-684).  The sums are wave-uniform.  Area and bounding box are integer
 // reductions.
+// The regions are the segments of any table of kWords int32 per entry whose word kFirst is the
+// entry's first interval (a region of the level, or a connected component of one): the twelve words
+// behind it are written, *count entries exist and *largest takes the most intervals of one.
+template <int kWords, int kFirst>
 __global__ __launch_bounds__(256) void k_level_moments(const int4* __restrict__ intervals, uint32_t n,
                                                        uint32_t capacity_regions, int32_t* __restrict__ regions,
-                                                       LevelStatus* __restrict__ status) {
+                                                       const uint32_t* __restrict__ count,
+                                                       uint32_t* __restrict__ largest) {
   const uint32_t r = (blockIdx.x * 256u + threadIdx.x) >> 6;
   const int lane = threadIdx.x & 63;
-  const uint32_t n_regions = status->regions;
+  const uint32_t n_regions = *count;
   if (r >= n_regions || r >= capacity_regions) return;
-  int32_t* out = regions + (size_t)r * kLevelRegionWords;
+  int32_t* out = regions + (size_t)r * kWords + (kFirst - 1);
   // one region per wavefront: both bounds are wave-uniform
   const uint32_t first = (uint32_t)__builtin_amdgcn_readfirstlane(out[1]);
   const bool has_next = r + 1 < n_regions && r + 1 < capacity_regions;
-  const uint32_t end = has_next ? (uint32_t)__builtin_amdgcn_readfirstlane(out[kLevelRegionWords + 1]) : n;
+  const uint32_t end = has_next ? (uint32_t)__builtin_amdgcn_readfirstlane(out[kWords + 1]) : n;
   if (first >= end || end > n) return;   // cannot happen; nothing outside the list is read
 
   float area_sum = 0.0f, mean_x = 0.0f, mean_y = 0.0f, moment_xx = 0.0f, moment_xy = 0.0f, moment_yy = 0.0f;
@@ -209,7 +214,7 @@ __global__ __launch_bounds__(256) void k_level_moments(const int4* __restrict__ 
     out[11] = __float_as_int(__fmul_rn(moment_xx, inv_area));
     out[12] = __float_as_int(__fmul_rn(moment_xy, inv_area));
     out[13] = __float_as_int(__fmul_rn(moment_yy, inv_area));
-    atomicMax(&status->largest, end - first);
+    atomicMax(largest, end - first);
   }
 }
 
@@ -272,8 +277,18 @@ void LaunchLevelMoments(const Interval* intervals, uint32_t n, uint32_t capacity
                         LevelStatus* status, hipStream_t stream) {
   if (n == 0 || capacity_regions == 0) return;
   const uint32_t blocks = (capacity_regions + 3) / 4;   // a wavefront per region; regions <= capacity_regions
-  hipLaunchKernelGGL(k_level_moments, dim3(blocks), dim3(256), 0, stream, reinterpret_cast<const int4*>(intervals), n,
-                     capacity_regions, regions, status);
+  hipLaunchKernelGGL((k_level_moments<kLevelRegionWords, 1>), dim3(blocks), dim3(256), 0, stream,
+                     reinterpret_cast<const int4*>(intervals), n, capacity_regions, regions, &status->regions,
+                     &status->largest);
+}
+
+void LaunchComponentMoments(const Interval* intervals, uint32_t n, uint32_t capacity_components,
+                            int32_t* components, CompStatus* status, hipStream_t stream) {
+  if (n == 0 || capacity_components == 0) return;
+  const uint32_t blocks = (capacity_components + 3) / 4;
+  hipLaunchKernelGGL((k_level_moments<kLevelComponentWords, 3>), dim3(blocks), dim3(256), 0, stream,
+                     reinterpret_cast<const int4*>(intervals), n, capacity_components, components,
+                     &status->components, &status->largest);
 }
 
 void LaunchLevelCopy(const int32_t* regions, const Interval* intervals, uint32_t n, uint32_t capacity_regions,

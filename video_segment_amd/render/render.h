@@ -1,5 +1,5 @@
-// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip), called by
-// render_capi.cpp.
+// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip),
+// called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
 
@@ -110,6 +110,52 @@ void LaunchLevelMoments(const Interval* intervals, uint32_t n, uint32_t capacity
 // capacity_regions.
 void LaunchLevelCopy(const int32_t* regions, const Interval* intervals, uint32_t n, uint32_t capacity_regions,
                      int32_t* regions_out, int32_t* intervals_out, const LevelStatus* status, hipStream_t stream);
+
+// ---- level components (components.hip): the connected components of every region of a level ---------
+
+constexpr int kLevelComponentWords = 16;   // vsg_render_level_component as int32 words
+
+enum CompFlag {
+  COMP_FLAG_BOUND = 1,     // a find or hook loop ran out of its bound, or an index was out of range
+  COMP_FLAG_DROPPED = 2,   // a component or a region had no slot
+};
+
+// Written by the component kernels; read by the host once the table is made and at the end of a call.
+struct CompStatus {
+  unsigned long long links;   // neighbour pairs found between adjacent rows
+  uint32_t components;
+  uint32_t largest;           // most intervals of one component
+  uint32_t flags, pad;
+};
+
+// Union-find over the n sorted runs of LevelSort (keys, right ends): runs of one id in adjacent rows
+// are united when left_a <= right_b + slack and left_b <= right_a + slack (slack 0: N4, 1: N8).
+// Leaves label[i] = the smallest run index of i's component and index[i] = i.  parent, label and index
+// have n entries each.
+void LaunchCompLink(const unsigned long long* keys_sorted, const uint32_t* rights_sorted, uint32_t n, int width,
+                    int slack, uint32_t* parent, uint32_t* label, uint32_t* index, CompStatus* status,
+                    hipStream_t stream);
+// Work space of CompSort and CompRank (the larger of the two).
+size_t CompTempBytes(int64_t n, int end_bit);
+// The library radix sort (stable) of the (label, index) pairs on bits [0, end_bit) of the label.
+hipError_t CompSort(void* temp, size_t temp_bytes, const uint32_t* label, uint32_t* label_sorted,
+                    const uint32_t* index, uint32_t* order, int64_t n, int end_bit, hipStream_t stream);
+// comp_rank[k] = number of distinct labels among ordered runs [0, k].
+hipError_t CompRank(void* temp, size_t temp_bytes, const uint32_t* label_sorted, uint32_t* comp_rank, int64_t n,
+                    hipStream_t stream);
+// n ordered runs -> the ordered interval list, the same list with the component's index as its value
+// (`fill`, may be null), and id, component, region_components and first_interval of every component;
+// status->components.  region_rank and intervals are LevelRank's and LaunchLevelTable's, level_status
+// holds the number of regions.  `components` has room for capacity_components entries of
+// kLevelComponentWords words, region_first for capacity_regions words.
+void LaunchCompTable(const uint32_t* label_sorted, const uint32_t* order, const uint32_t* comp_rank,
+                     const uint32_t* region_rank, const Interval* intervals, uint32_t n,
+                     uint32_t capacity_components, uint32_t capacity_regions, Interval* ordered, Interval* fill,
+                     int32_t* components, uint32_t* region_first, const LevelStatus* level_status,
+                     CompStatus* status, hipStream_t stream);
+// The remaining fields of every component, by the kernel of LaunchLevelMoments; status->largest.
+void LaunchComponentMoments(const Interval* intervals, uint32_t n, uint32_t capacity_components,
+                            int32_t* components, CompStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -17,6 +17,7 @@
 
 namespace {
 
+using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
 using vsg_render_impl::VecLine;
@@ -25,6 +26,8 @@ using vsg_render_impl::VecStatus;
 enum Stage { STAGE_CLEAR = 0, STAGE_FILL, STAGE_COMPOSE, STAGE_COUNT };
 enum VecStage { VEC_WALK = 0, VEC_SORT, VEC_PAIRS, VEC_COUNT };
 enum LevelStage { LVL_RUNS = 0, LVL_SORT, LVL_TABLE, LVL_MOMENTS, LVL_COUNT };
+// CMP_WAIT: the stream idles while the host reads the number of components; reported with no stage
+enum CompStage { CMP_LINK = 0, CMP_ORDER, CMP_MOMENTS, CMP_LABEL, CMP_WAIT, CMP_COUNT };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -322,7 +325,8 @@ struct vsg_render {
   vsg_render_options opt;
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
-  StageClock clock, vclock, lclock;   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages
+  // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
+  StageClock clock, vclock, lclock, cclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -341,10 +345,16 @@ struct vsg_render {
   // level regions: unsorted runs (keys, right ends), sorted runs with their ranks, the two lists,
   // the status words, and the pinned block the status and host outputs come back through
   Block d_runs, d_sorted, d_level_regions, d_level_intervals, d_level_status, h_level;
+  // level components: the union-find's parents, labels and indices with their sorted copies and the
+  // components' ranks; the component table; the ordered intervals; the same with component indices
+  // for the label fill; every region's first component; the label plane of a host output; the status
+  // words and the pinned block they come back through
+  Block d_comp_work, d_comp_table, d_comp_intervals, d_comp_fill, d_comp_first, d_labels, d_comp_status, h_comp;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
   vsg_render_level_stats lstats;
+  vsg_render_component_stats cstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -593,6 +603,108 @@ bool PaintIds(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint
   return vector;
 }
 
+// What the front half of the level calls leaves behind: n runs, unsorted (keys, rights) and, after
+// SortLevelRuns, sorted with their regions' ranks, as intervals, and with id and first interval of every
+// region in `regions`.
+struct LevelFront {
+  bool vector = false;
+  uint32_t n = 0, cap_runs = 0, cap_regions = 0;
+  int32_t max_id = 0;
+  unsigned long long* keys = nullptr;
+  uint32_t* rights = nullptr;
+  LevelStatus* status = nullptr;
+  unsigned long long* keys_sorted = nullptr;
+  uint32_t* rights_sorted = nullptr;
+  uint32_t* rank = nullptr;
+  int32_t* regions = nullptr;
+  Interval* intervals = nullptr;
+};
+
+// Paints the id plane as vsg_render_id_image does, finds its runs and waits for their number, which
+// sizes everything after it.  Fills the run fields of *ls.
+LevelFront PaintLevelRuns(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, vsg_render_level_stats* ls) {
+  using namespace vsg_render_impl;
+  const int W = h->W, H = h->H;
+  LevelFront f;
+  // ---- the id plane, as vsg_render_id_image paints it ----
+  h->d_ids.Reserve((size_t)W * H * sizeof(int32_t), &h->allocations);
+  int32_t max_id = 0;
+  f.vector = PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(), [&](int mapped) {
+    // -1 is the plane's "no region"; the sort key takes the id as an unsigned number
+    if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
+    max_id = std::max(max_id, mapped);
+    return (uint32_t)mapped;
+  });
+  f.max_id = max_id;
+
+  // ---- runs ----
+  // Intervals that do not overlap give at most one run each; every end of an interval that lies
+  // on another one can add a run.  The kernel drops what has no slot and says so.
+  const uint64_t painted = (uint64_t)h->stats.intervals;
+  const uint32_t cap_runs = (uint32_t)std::min<uint64_t>(2 * painted + 1, (uint64_t)W * H);
+  h->d_runs.Reserve((size_t)cap_runs * 12, &h->allocations);
+  h->d_level_status.Reserve(sizeof(LevelStatus), &h->allocations);
+  h->h_level.Reserve(2 * sizeof(LevelStatus), &h->allocations);
+  f.cap_runs = cap_runs;
+  f.keys = h->d_runs.As<unsigned long long>();
+  f.rights = reinterpret_cast<uint32_t*>(f.keys + cap_runs);
+  f.status = h->d_level_status.As<LevelStatus>();
+  LevelStatus* seen = h->h_level.As<LevelStatus>();   // [0] after the runs, [1] at the end
+  VSG_HIP(hipMemsetAsync(f.status, 0, sizeof(LevelStatus), h->stream));
+  h->lclock.Begin(h->stream);
+  LaunchLevelRuns(h->d_ids.As<int32_t>(), W, W, H, cap_runs, f.keys, f.rights, f.status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->lclock.Mark(LVL_RUNS);
+  VSG_HIP(hipMemcpyAsync(&seen[0], f.status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
+  ls->launches = 3;
+  VSG_HIP(hipStreamSynchronize(h->stream));   // the run count sizes everything below
+  {
+    float us[STAGE_COUNT], lus[LVL_COUNT];
+    h->clock.Read(us, STAGE_COUNT);
+    h->stats.clear_us = us[STAGE_CLEAR];
+    h->stats.fill_us = us[STAGE_FILL];
+    h->lclock.Read(lus, LVL_COUNT);
+    ls->runs_us = lus[LVL_RUNS];
+  }
+  if (f.vector) h->CheckVector();
+  if (seen[0].overflow || seen[0].runs > cap_runs) Throw(VSG_ERR_INTERNAL, "more runs than the intervals allow");
+  f.n = seen[0].runs;
+  ls->runs = f.n;
+  // every region has a run, and every id of the plane is one of the host's distinct mapped ids
+  f.cap_regions = (uint32_t)std::min<uint64_t>(f.n, (uint64_t)h->stats.distinct_ids);
+  return f;
+}
+
+// The n > 0 runs into (id, y, left_x) order, their regions' ranks, the interval list and the heads of
+// the region table; restarts lclock and leaves it after LVL_TABLE.
+void SortLevelRuns(vsg_render* h, LevelFront* f, vsg_render_level_stats* ls) {
+  using namespace vsg_render_impl;
+  const uint32_t n = f->n;
+  int id_bits = 1;
+  while (id_bits < 31 && (f->max_id >> id_bits)) ++id_bits;
+  const int end_bit = 32 + id_bits;
+  const size_t temp_bytes = std::max<size_t>(LevelTempBytes(n, end_bit), 16);
+  h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+  h->d_sorted.Reserve((size_t)n * 16, &h->allocations);
+  h->d_level_regions.Reserve((size_t)f->cap_regions * sizeof(vsg_render_level_region), &h->allocations);
+  h->d_level_intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+  f->keys_sorted = h->d_sorted.As<unsigned long long>();
+  f->rights_sorted = reinterpret_cast<uint32_t*>(f->keys_sorted + n);
+  f->rank = f->rights_sorted + n;
+  f->regions = h->d_level_regions.As<int32_t>();
+  f->intervals = h->d_level_intervals.As<Interval>();
+  h->lclock.Begin(h->stream);
+  VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, f->keys, f->keys_sorted, f->rights, f->rights_sorted, n, end_bit,
+                    h->stream));
+  h->lclock.Mark(LVL_SORT);
+  VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, f->keys_sorted, f->rank, n, h->stream));
+  LaunchLevelTable(f->keys_sorted, f->rights_sorted, f->rank, n, h->W, f->cap_regions, f->intervals, f->regions,
+                   f->status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->lclock.Mark(LVL_TABLE);
+  ls->launches += 3;   // the sort and the scan count as one each
+}
+
 }  // namespace
 
 extern "C" {
@@ -648,6 +760,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->clock.Create(STAGE_COUNT + 1);
     h->vclock.Create(VEC_COUNT + 1);
     h->lclock.Create(LVL_COUNT + 1);
+    h->cclock.Create(CMP_COUNT + 1);
+    h->h_comp.pinned = true;
+    std::memset(&h->cstats, 0, sizeof(h->cstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -803,80 +918,23 @@ int vsg_render_level_regions(vsg_render* h, const uint8_t* seg, size_t seg_len, 
     DeviceGuard guard(h->device);
     std::memset(&h->lstats, 0, sizeof(h->lstats));
 
-    // ---- the id plane, as vsg_render_id_image paints it ----
-    h->d_ids.Reserve((size_t)W * H * sizeof(int32_t), &h->allocations);
-    int32_t max_id = 0;
-    const bool vector = PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(), [&](int mapped) {
-      // -1 is the plane's "no region"; the sort key takes the id as an unsigned number
-      if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
-      max_id = std::max(max_id, mapped);
-      return (uint32_t)mapped;
-    });
-
-    // ---- runs ----
-    // Intervals that do not overlap give at most one run each; every end of an interval that lies
-    // on another one can add a run.  The kernel drops what has no slot and says so.
-    const uint64_t painted = (uint64_t)h->stats.intervals;
-    const uint32_t cap_runs = (uint32_t)std::min<uint64_t>(2 * painted + 1, (uint64_t)W * H);
-    h->d_runs.Reserve((size_t)cap_runs * 12, &h->allocations);
-    h->d_level_status.Reserve(sizeof(LevelStatus), &h->allocations);
-    h->h_level.Reserve(2 * sizeof(LevelStatus), &h->allocations);
-    unsigned long long* keys = h->d_runs.As<unsigned long long>();
-    uint32_t* rights = reinterpret_cast<uint32_t*>(keys + cap_runs);
-    LevelStatus* status = h->d_level_status.As<LevelStatus>();
-    LevelStatus* seen = h->h_level.As<LevelStatus>();   // [0] after the runs, [1] at the end
-    VSG_HIP(hipMemsetAsync(status, 0, sizeof(LevelStatus), h->stream));
-    h->lclock.Begin(h->stream);
-    LaunchLevelRuns(h->d_ids.As<int32_t>(), W, W, H, cap_runs, keys, rights, status, h->stream);
-    VSG_HIP(hipGetLastError());
-    h->lclock.Mark(LVL_RUNS);
-    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
-    h->lstats.launches = 3;
-    VSG_HIP(hipStreamSynchronize(h->stream));   // the run count sizes everything below
-    {
-      float us[STAGE_COUNT], lus[LVL_COUNT];
-      h->clock.Read(us, STAGE_COUNT);
-      h->stats.clear_us = us[STAGE_CLEAR];
-      h->stats.fill_us = us[STAGE_FILL];
-      h->lclock.Read(lus, LVL_COUNT);
-      h->lstats.runs_us = lus[LVL_RUNS];
-    }
-    if (vector) h->CheckVector();
-    if (seen[0].overflow || seen[0].runs > cap_runs) Throw(VSG_ERR_INTERNAL, "more runs than the intervals allow");
-    const uint32_t n = seen[0].runs;
-    h->lstats.runs = n;
+    LevelFront f = PaintLevelRuns(h, seg, seg_len, level, &h->lstats);
+    const uint32_t n = f.n;
     *num_intervals = n;
 
     // ---- sort, table, moments, outputs ----
-    // every region has a run, and every id of the plane is one of the host's distinct mapped ids
-    const uint32_t cap_regions = (uint32_t)std::min<uint64_t>(n, (uint64_t)h->stats.distinct_ids);
+    const uint32_t cap_regions = f.cap_regions;
     const bool intervals_fit = n <= capacity_intervals;
     const bool deliver = !count_only && intervals_fit;
     const size_t region_bytes = (size_t)cap_regions * sizeof(vsg_render_level_region);
     const size_t interval_bytes = (size_t)n * sizeof(Interval);
     if (deliver && n && (!regions || !intervals)) Throw(VSG_ERR_INVALID, "an output is null");
     if (n) {
-      int id_bits = 1;
-      while (id_bits < 31 && (max_id >> id_bits)) ++id_bits;
-      const int end_bit = 32 + id_bits;
-      const size_t temp_bytes = std::max<size_t>(LevelTempBytes(n, end_bit), 16);
-      h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
-      h->d_sorted.Reserve((size_t)n * 16, &h->allocations);
-      h->d_level_regions.Reserve(region_bytes, &h->allocations);
-      h->d_level_intervals.Reserve(interval_bytes, &h->allocations);
-      unsigned long long* keys_sorted = h->d_sorted.As<unsigned long long>();
-      uint32_t* rights_sorted = reinterpret_cast<uint32_t*>(keys_sorted + n);
-      uint32_t* rank = rights_sorted + n;
-      int32_t* d_regions = h->d_level_regions.As<int32_t>();
-      Interval* d_intervals = h->d_level_intervals.As<Interval>();
-      h->lclock.Begin(h->stream);
-      VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, rights, rights_sorted, n, end_bit, h->stream));
-      h->lclock.Mark(LVL_SORT);
-      VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, keys_sorted, rank, n, h->stream));
-      LaunchLevelTable(keys_sorted, rights_sorted, rank, n, W, cap_regions, d_intervals, d_regions, status, h->stream);
-      VSG_HIP(hipGetLastError());
-      h->lclock.Mark(LVL_TABLE);
-      h->lstats.launches += 3;   // the sort and the scan count as one each
+      SortLevelRuns(h, &f, &h->lstats);
+      LevelStatus* status = f.status;
+      LevelStatus* seen = h->h_level.As<LevelStatus>();
+      int32_t* d_regions = f.regions;
+      Interval* d_intervals = f.intervals;
       if (!count_only) {
         LaunchLevelMoments(d_intervals, n, cap_regions, d_regions, status, h->stream);
         VSG_HIP(hipGetLastError());
@@ -934,6 +992,171 @@ int vsg_render_last_level_stats(vsg_render* h, vsg_render_level_stats* s) {
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->lstats;
+  });
+}
+
+int vsg_render_level_components(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                                vsg_render_level_component* components, size_t capacity_components,
+                                size_t* num_components, int32_t* intervals, size_t capacity_intervals,
+                                size_t* num_intervals, int32_t* label_image, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_level_component) == kLevelComponentWords * sizeof(int32_t), "moved as int32 words");
+    if (connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_components || !num_intervals) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_components = *num_intervals = 0;
+    CheckMem(mem_out, "outputs");
+    const bool count_only =
+        !components && !intervals && !label_image && capacity_components == 0 && capacity_intervals == 0;
+    const int W = h->W, H = h->H;
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+    DeviceGuard guard(h->device);
+    vsg_render_component_stats& cs = h->cstats;
+    std::memset(&cs, 0, sizeof(cs));
+    vsg_render_level_stats ls;   // of the shared front half; the last level_regions call's stay
+    std::memset(&ls, 0, sizeof(ls));
+
+    LevelFront f = PaintLevelRuns(h, seg, seg_len, level, &ls);
+    const uint32_t n = f.n;
+    *num_intervals = n;
+    cs.runs = n;
+    cs.runs_us = ls.runs_us;
+    if (!count_only && n && n <= capacity_intervals && (!components || !intervals)) {
+      Throw(VSG_ERR_INVALID, "an output is null");
+    }
+    h->d_comp_status.Reserve(sizeof(CompStatus), &h->allocations);
+    h->h_comp.Reserve(2 * sizeof(CompStatus) + sizeof(LevelStatus), &h->allocations);
+    CompStatus* status = h->d_comp_status.As<CompStatus>();
+    CompStatus* seen = h->h_comp.As<CompStatus>();   // [0] once the table is made, [1] at the end
+    LevelStatus* seen_level = reinterpret_cast<LevelStatus*>(seen + 2);
+    std::memset(seen, 0, 2 * sizeof(CompStatus) + sizeof(LevelStatus));
+    Interval* ordered = nullptr;
+    Interval* fill = nullptr;
+    int32_t* table = nullptr;
+    int launches = 0;
+    if (!n) h->cclock.Begin(h->stream);   // an empty frame still clears the label image
+    if (n) {
+      // ---- the runs sorted by (id, y, left_x), as vsg_render_level_regions has them ----
+      int label_bits = 1;
+      while (label_bits < 32 && ((uint64_t)(n - 1) >> label_bits)) ++label_bits;
+      const size_t temp_bytes = std::max<size_t>(CompTempBytes(n, label_bits), 16);
+      h->d_sort_temp.Reserve(temp_bytes, &h->allocations);   // before anything that uses the block is enqueued
+      SortLevelRuns(h, &f, &ls);
+
+      // ---- union-find, order, table ----
+      h->d_comp_work.Reserve((size_t)n * 6 * sizeof(uint32_t), &h->allocations);
+      h->d_comp_table.Reserve((size_t)n * sizeof(vsg_render_level_component), &h->allocations);
+      h->d_comp_intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+      h->d_comp_first.Reserve((size_t)f.cap_regions * sizeof(uint32_t), &h->allocations);
+      if (label_image) h->d_comp_fill.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+      uint32_t* parent = h->d_comp_work.As<uint32_t>();
+      uint32_t* label = parent + n;
+      uint32_t* index = label + n;
+      uint32_t* label_sorted = index + n;
+      uint32_t* order = label_sorted + n;
+      uint32_t* comp_rank = order + n;
+      ordered = h->d_comp_intervals.As<Interval>();
+      fill = label_image ? h->d_comp_fill.As<Interval>() : nullptr;
+      table = h->d_comp_table.As<int32_t>();
+      VSG_HIP(hipMemsetAsync(status, 0, sizeof(CompStatus), h->stream));
+      h->cclock.Begin(h->stream);
+      LaunchCompLink(f.keys_sorted, f.rights_sorted, n, W, connectedness == VSG_RENDER_CONNECT_N8 ? 1 : 0, parent,
+                     label, index, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      h->cclock.Mark(CMP_LINK);
+      VSG_HIP(CompSort(h->d_sort_temp.p, temp_bytes, label, label_sorted, index, order, n, label_bits, h->stream));
+      VSG_HIP(CompRank(h->d_sort_temp.p, temp_bytes, label_sorted, comp_rank, n, h->stream));
+      // a run has at most one component: n slots hold them all
+      LaunchCompTable(label_sorted, order, comp_rank, f.rank, f.intervals, n, n, f.cap_regions, ordered, fill, table,
+                      h->d_comp_first.As<uint32_t>(), f.status, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      h->cclock.Mark(CMP_ORDER);
+      VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(seen_level, f.status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
+      launches += 11;   // the clear, five kernels, two copies; the sorts and the scans count as one each
+      VSG_HIP(hipStreamSynchronize(h->stream));   // the number of components decides what is delivered
+      if (seen_level->regions == 0 || seen_level->regions > f.cap_regions) {
+        Throw(VSG_ERR_INTERNAL, "the plane has more regions than the desc has ids");
+      }
+      if (seen[0].flags & COMP_FLAG_BOUND) Throw(VSG_ERR_INTERNAL, "the union-find did not end within its bound");
+      if ((seen[0].flags & COMP_FLAG_DROPPED) || seen[0].components == 0 || seen[0].components > n) {
+        Throw(VSG_ERR_INTERNAL, "a component had no slot");
+      }
+    }
+    const uint32_t n_components = seen[0].components;
+    *num_components = n_components;
+    cs.regions = seen_level->regions;
+    cs.components = n_components;
+    cs.links = (int64_t)seen[0].links;
+    auto finish = [&] {
+      float us[CMP_COUNT], lus[LVL_COUNT];
+      h->cclock.Read(us, CMP_COUNT);
+      cs.link_us = us[CMP_LINK];
+      cs.order_us = us[CMP_ORDER];
+      cs.moments_us = us[CMP_MOMENTS];
+      cs.label_us = us[CMP_LABEL];
+      if (n) {
+        h->lclock.Read(lus, LVL_COUNT);
+        cs.sort_us = lus[LVL_SORT] + lus[LVL_TABLE];
+      }
+      cs.launches = ls.launches + launches;
+      h->stats.launches += cs.launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    if (count_only) return finish();
+    if (n > capacity_intervals || n_components > capacity_components) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_components) + " components and " +
+                                 std::to_string(n) + " intervals, the capacities are " +
+                                 std::to_string(capacity_components) + " and " + std::to_string(capacity_intervals));
+    }
+
+    // ---- moments, label image, outputs ----
+    if (n) h->cclock.Mark(CMP_WAIT);
+    const hipMemcpyKind kind = mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+    if (n) {
+      LaunchComponentMoments(ordered, n, n_components, table, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      h->cclock.Mark(CMP_MOMENTS);
+      ++launches;
+    }
+    if (label_image) {
+      const size_t bytes = (size_t)W * H * sizeof(int32_t);
+      uint32_t* plane = reinterpret_cast<uint32_t*>(label_image);   // device output: painted in place
+      if (mem_out == VSG_MEM_HOST) {
+        h->d_labels.Reserve(bytes, &h->allocations);
+        plane = h->d_labels.As<uint32_t>();
+      }
+      VSG_HIP(hipMemsetAsync(plane, 0xff, bytes, h->stream));   // -1: no component
+      LaunchFill(fill, n, plane, W, h->stream);
+      VSG_HIP(hipGetLastError());
+      h->cclock.Mark(CMP_LABEL);
+      launches += 1 + (n ? 1 : 0);
+      if (mem_out == VSG_MEM_HOST) {
+        VSG_HIP(hipMemcpyAsync(label_image, plane, bytes, hipMemcpyDeviceToHost, h->stream));
+        ++launches;
+      }
+    }
+    if (n) {
+      VSG_HIP(hipMemcpyAsync(components, table, (size_t)n_components * sizeof(vsg_render_level_component), kind,
+                             h->stream));
+      VSG_HIP(hipMemcpyAsync(intervals, ordered, (size_t)n * sizeof(Interval), kind, h->stream));
+      VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
+      launches += 3;
+    }
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    cs.largest_component_intervals = seen[1].largest;
+    finish();
+  });
+}
+
+int vsg_render_last_component_stats(vsg_render* h, vsg_render_component_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->cstats;
   });
 }
 
