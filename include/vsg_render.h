@@ -38,9 +38,10 @@
  * level with its merged rasterization, its area and its shape moments; the ellipse's axes and angle
  * (GetShapeDescriptorFromShapeMoments) and the drawing itself are left to the caller.  A region of a
  * level above 0 is usually several blobs in one frame; vsg_render_level_components returns the same
- * per connected component.  Boundary point lists (GetBoundary, segmentation/boundary.cpp) are not
- * offered either, with and without that call: it splits a region as GetBoundary's first step does
- * and traces nothing.
+ * per connected component, and vsg_render_level_boundaries the boundary point lists of either: the
+ * reference's GetBoundary (segment_util/segmentation_boundary.{h,cpp}), the N4 inner or outer boundary
+ * pixels of a rasterization in row-major order.  Contour tracing and vectorisation at a level
+ * (BoundaryComputation, segmentation/boundary.cpp) are not offered.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -267,6 +268,72 @@ typedef struct vsg_render_component_stats {
   int launches;
 } vsg_render_component_stats;
 int vsg_render_last_component_stats(vsg_render* h, vsg_render_component_stats* s);
+
+#define VSG_RENDER_BOUNDARY_INNER 0
+#define VSG_RENDER_BOUNDARY_OUTER 1
+
+/* One boundary, as vsg_render_level_boundaries returns it. */
+typedef struct vsg_render_level_boundary {   /* 16 bytes, no padding */
+  int32_t id;           /* region id at `level` */
+  int32_t component;    /* index among its region's components; -1 with connectedness 0 */
+  int32_t first_point, num_points;
+} vsg_render_level_boundary;
+
+/* The N4 boundary pixels of every region of hierarchy level `level`, or of every connected component
+ * of its regions: GetBoundary (segment_util/segmentation_boundary.cpp:78-179) applied to each of their
+ * rasterizations, computed on the device.
+ *
+ * Let P be an int32 plane of W x H, -1 where nothing covers the pixel; positions outside the frame
+ * count as -1.  A group g >= 0 is a value of P.
+ *   inner(g): the positions (x, y) with P = g and at least one of the four neighbours != g.  The frame
+ *     edge therefore always bounds a region.  This is the reference's result exactly.
+ *   outer(g): the positions (x, y) of [-1, W] x [-1, H] with P != g and at least one of the four
+ *     neighbours = g.  Positions outside the frame and uncovered pixels are included, a pixel of another
+ *     group is an outer point of g, and a position is an outer point of up to four groups; it is listed
+ *     once per group, however many of its neighbours belong to that group.
+ * Within a group the points are ordered by y, then by x: the order of the reference's loops.
+ * connectedness 0: P is the id plane of vsg_render_id_image at `level`; one boundary per region,
+ * regions in ascending id, record k belonging to record k of vsg_render_level_regions.
+ * VSG_RENDER_CONNECT_N4 / _N8: P is the label image of vsg_render_level_components with that
+ * connectedness; one boundary per component in the component list's order, record k belonging to
+ * record k of that call (which is made internally: vsg_render_last_component_stats then describes it).
+ * Every group has at least one inner and at least one outer point, so the lists align one to one.
+ *
+ * Two things differ from the reference's outer mode, on purpose:
+ *  1. The reference reports every outer point with x one too large: its row pointers start at
+ *     min_range - shift while its x starts at min_range (segmentation_boundary.cpp:148-154), so
+ *     reference_x = x + 1 throughout, y being right.  This call returns the true position x.
+ *  2. The reference's outer mode reads one byte before the first row of the caller's buffer (the left
+ *     neighbour of position -1 of its first row) and, with a buffer of the advertised size
+ *     3 * (frame_width + 2), one byte past the last row.  This call treats those positions as not in
+ *     the region, which is what the reference computes whenever the bytes it happens to read are zero.
+ *
+ * boundaries: one record per group.  points: int32 pairs {x, y}, grouped by boundary in list order;
+ * x is in [-1, W] and y in [-1, H] for outer points.  Both in mem_out memory.
+ * Decode, hierarchy rules, refusals, the non-negative ids and the handling of vector-only descs are
+ * those of vsg_render_level_regions.
+ * *num_boundaries and *num_points are always set on VSG_OK and when a capacity is too small; in that
+ * case the call fails with VSG_ERR_INVALID and neither output is touched.  boundaries == NULL and
+ * points == NULL with both capacities 0 asks for the counts only (VSG_OK; needs the device).  A null
+ * handle, a null count pointer, a connectedness other than 0, VSG_RENDER_CONNECT_N4 and
+ * VSG_RENDER_CONNECT_N8 or a `which` other than the two above is VSG_ERR_INVALID and touches no
+ * device. */
+int vsg_render_level_boundaries(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                                int which, vsg_render_level_boundary* boundaries, size_t capacity_boundaries,
+                                size_t* num_boundaries, int32_t* points, size_t capacity_points,
+                                size_t* num_points, int mem_out);
+
+/* What the last vsg_render_level_boundaries call of the handle did.  Device times are HIP events
+ * around the stages: making the plane (the id plane's clear and fill; with a connectedness, also every
+ * stage of the internal vsg_render_level_components call up to its label image); the count pass of
+ * k_bound_classify; its emit pass; the radix sort; the scan, k_bound_table and k_bound_finish.  The
+ * last three are not run, and boundaries and largest_boundary_points are 0, when there is no point. */
+typedef struct vsg_render_boundary_stats {
+  int64_t points, boundaries, largest_boundary_points;
+  float plane_us, count_us, emit_us, sort_us, table_us;
+  int launches;
+} vsg_render_boundary_stats;
+int vsg_render_last_boundary_stats(vsg_render* h, vsg_render_boundary_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -33,6 +33,15 @@ The component leg: the same descs and levels asked for their connected component
 stage times of vsg_render_component_stats, launches, runs, links and components are recorded; in the
 same run vsg_render_level_regions on the same desc and handle is timed with its four stage times: the
 yardstick.  No pass or fail threshold.
+
+    python tools/render_probe.py --level-boundaries [--reps 30] [--out profiles/level_boundaries.json]
+
+The boundary leg: the same descs and levels asked for their boundary point lists
+(vsg_render_level_boundaries, outputs in device memory): of the regions (connectedness 0) and of their N4
+components, inner and outer.  Per call the five stage times of vsg_render_boundary_stats, launches, points
+and boundaries are recorded; in the same run vsg_render_level_components (N4, lists and label image in
+device memory) on the same desc and handle is timed with its six stage times: the yardstick.  No pass or
+fail threshold.
 """
 import argparse
 import json
@@ -63,11 +72,14 @@ def main():
                     help="the level leg instead (profiles/level_regions.json)")
     ap.add_argument("--level-components", action="store_true",
                     help="the component leg instead (profiles/level_components.json)")
+    ap.add_argument("--level-boundaries", action="store_true",
+                    help="the boundary leg instead (profiles/level_boundaries.json)")
     args = ap.parse_args()
-    if (args.level_regions or args.level_components) and "--reps" not in sys.argv:
+    if (args.level_regions or args.level_components or args.level_boundaries) and "--reps" not in sys.argv:
         args.reps = 30
     if args.out is None:
-        name = ("level_components.json" if args.level_components else "level_regions.json" if args.level_regions
+        name = ("level_boundaries.json" if args.level_boundaries else
+                "level_components.json" if args.level_components else "level_regions.json" if args.level_regions
                 else "vector_raster.json" if args.vector else "render_kernels.json")
         args.out = os.path.join(ROOT, "profiles", name)
 
@@ -81,6 +93,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.level_boundaries:
+        return boundaries_leg(args, result, dev)
     if args.level_components:
         return components_leg(args, result, dev)
     if args.level_regions:
@@ -313,6 +327,54 @@ def components_leg(args, result, dev):
                 with open(args.out, "w") as f:
                     json.dump(result, f, indent=1)
                     f.write("\n")
+        r.close()
+    print("wrote", args.out)
+
+
+def boundaries_leg(args, result, dev):
+    import torch
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    for size, W, H, seg, height in level_descs(args):
+        r = vsg.SegmentationRenderer(W, H, has_video=False)
+        labels = torch.empty((H, W), dtype=torch.int32, device=dev)
+        for level in sorted({0, height // 2, max(height - 1, 0)}):
+            nc, ni = (len(a) for a in r.level_components(seg, level, render.N4))
+            comps = torch.empty((nc, render.LEVEL_COMPONENT_WORDS), dtype=torch.int32, device=dev)
+            intervals = torch.empty((ni, 4), dtype=torch.int32, device=dev)
+            for mode, connect in (("regions", 0), ("components_N4", render.N4)):
+                for which, outer in (("inner", False), ("outer", True)):
+                    nb, npts = (len(a) for a in r.level_boundaries(seg, level, connect, outer))
+                    records = torch.empty((nb, render.LEVEL_BOUNDARY_WORDS), dtype=torch.int32, device=dev)
+                    points = torch.empty((npts, 2), dtype=torch.int32, device=dev)
+                    stage_keys = ["plane_us", "count_us", "emit_us", "sort_us", "table_us"]
+                    comp_keys = ["runs_us", "sort_us", "link_us", "order_us", "moments_us", "label_us"]
+                    rows = {k: [] for k in stage_keys + ["call_ms", "level_components_call_ms"]
+                            + ["level_components_" + k for k in comp_keys]}
+                    for it in range(args.warmup + args.reps):
+                        t0 = time.perf_counter()
+                        r.level_boundaries(seg, level, connect, outer, boundaries_out=records, points_out=points)
+                        st = dict(r.last_boundary_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
+                        t0 = time.perf_counter()
+                        r.level_components(seg, level, render.N4, components_out=comps, intervals_out=intervals,
+                                           labels_out=labels)
+                        st["level_components_call_ms"] = (time.perf_counter() - t0) * 1e3
+                        cst = r.last_component_stats()
+                        st.update({"level_components_" + k: cst[k] for k in comp_keys})
+                        if it >= args.warmup:
+                            for k in rows:
+                                rows[k].append(st[k])
+                    case = {"size": size, "level": level, "hierarchy_levels": height, "mode": mode, "which": which,
+                            "points": st["points"], "boundaries": st["boundaries"],
+                            "largest_boundary_points": st["largest_boundary_points"], "launches": st["launches"],
+                            "runs": cst["runs"], "components": cst["components"],
+                            "level_components_launches": cst["launches"]}
+                    case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+                    result["cases"].append(case)
+                    print(json.dumps(case), flush=True)
+                    with open(args.out, "w") as f:
+                        json.dump(result, f, indent=1)
+                        f.write("\n")
         r.close()
     print("wrote", args.out)
 

@@ -20,6 +20,11 @@
 // every frame and prints a line
 // level_components=<sum> component_intervals=<sum> component_fnv1a32=<hash of both lists' bytes>.
 //
+//   --level_boundaries <level> [--boundaries_outer] [--boundaries_components [--components_n8]]
+// asks vsg_render_level_boundaries for the inner (or outer) N4 boundary points of that level's regions,
+// or of their connected components (N4, or N8), of every frame and prints a line
+// level_boundaries=<sum> boundary_points=<sum> boundary_fnv1a32=<hash of both lists' bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -355,6 +360,67 @@ class LevelComponentsSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_boundaries: the same for the boundary point lists of a level's regions or of their connected
+// components (vsg_render_level_boundaries), records first.
+class LevelBoundariesSinkUnit : public VideoUnit {
+ public:
+  LevelBoundariesSinkUnit(int level, int connectedness, bool outer, int device)
+      : level_(level), connect_(connectedness),
+        which_(outer ? VSG_RENDER_BOUNDARY_OUTER : VSG_RENDER_BOUNDARY_INNER), device_(device) {}
+  ~LevelBoundariesSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t nb = 0, np = 0;
+    VF_CHECK(vsg_render_level_boundaries(render_, seg, desc.wire.size(), level_, connect_, which_, nullptr, 0, &nb,
+                                         nullptr, 0, &np, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    records_buf_.resize(nb);
+    points_buf_.resize(2 * np);
+    VF_CHECK(vsg_render_level_boundaries(render_, seg, desc.wire.size(), level_, connect_, which_, records_buf_.data(),
+                                         nb, &nb, points_buf_.data(), np, &np, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    Hash(records_buf_.data(), nb * sizeof(vsg_render_level_boundary));
+    Hash(points_buf_.data(), np * 2 * sizeof(int32_t));
+    boundaries_ += (long)nb;
+    points_ += (long)np;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long boundaries() const { return boundaries_; }
+  long points() const { return points_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, which_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_boundary> records_buf_;
+  std::vector<int32_t> points_buf_;
+  long boundaries_ = 0, points_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -448,6 +514,11 @@ struct Flags {
   // vsg_render_level_components at this level for every frame; < 0: off.  N4, or N8 with --components_n8
   int level_components = -1;
   bool components_n8 = false;
+  // vsg_render_level_boundaries at this level for every frame; < 0: off.  Inner points of the regions, or
+  // outer points with --boundaries_outer, of the components (N4, or N8 with --components_n8) with
+  // --boundaries_components
+  int level_boundaries = -1;
+  bool boundaries_outer = false, boundaries_components = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -480,7 +551,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
-                                   "help"};
+                                   "boundaries_outer", "boundaries_components", "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -527,6 +598,9 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_regions") f->level_regions = atoi(v.c_str());
     else if (a == "level_components") f->level_components = atoi(v.c_str());
     else if (a == "components_n8") f->components_n8 = bv;
+    else if (a == "level_boundaries") f->level_boundaries = atoi(v.c_str());
+    else if (a == "boundaries_outer") f->boundaries_outer = bv;
+    else if (a == "boundaries_components") f->boundaries_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -733,6 +807,16 @@ int main(int argc, char** argv) {
     components_sink->AttachTo(input);
     input = components_sink.get();
   }
+  std::unique_ptr<LevelBoundariesSinkUnit> boundaries_sink;
+  if (FLAGS.level_boundaries >= 0) {
+    const int connectedness = !FLAGS.boundaries_components ? 0
+                              : FLAGS.components_n8        ? VSG_RENDER_CONNECT_N8
+                                                           : VSG_RENDER_CONNECT_N4;
+    boundaries_sink.reset(
+        new LevelBoundariesSinkUnit(FLAGS.level_boundaries, connectedness, FLAGS.boundaries_outer, FLAGS.device));
+    boundaries_sink->AttachTo(input);
+    input = boundaries_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -783,6 +867,10 @@ int main(int argc, char** argv) {
   if (components_sink) {
     std::printf("level_components=%ld component_intervals=%ld component_fnv1a32=%08x\n", components_sink->components(),
                 components_sink->intervals(), components_sink->hash());
+  }
+  if (boundaries_sink) {
+    std::printf("level_boundaries=%ld boundary_points=%ld boundary_fnv1a32=%08x\n", boundaries_sink->boundaries(),
+                boundaries_sink->points(), boundaries_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

@@ -63,6 +63,15 @@ class VsgRenderComponentStats(_capi.Structure):
     ]
 
 
+class VsgRenderBoundaryStats(_capi.Structure):
+    _fields_ = [
+        ("points", C.c_int64), ("boundaries", C.c_int64), ("largest_boundary_points", C.c_int64),
+        ("plane_us", C.c_float), ("count_us", C.c_float), ("emit_us", C.c_float), ("sort_us", C.c_float),
+        ("table_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -84,6 +93,17 @@ LEVEL_COMPONENT_DTYPE = np.dtype([
 assert LEVEL_COMPONENT_DTYPE.itemsize == 64
 LEVEL_COMPONENT_WORDS = 16
 
+# vsg_render_level_boundary: 16 bytes, no padding
+LEVEL_BOUNDARY_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("first_point", np.int32), ("num_points", np.int32),
+])
+assert LEVEL_BOUNDARY_DTYPE.itemsize == 16
+LEVEL_BOUNDARY_WORDS = 4
+
+# VSG_RENDER_BOUNDARY_INNER / _OUTER
+BOUNDARY_INNER = 0
+BOUNDARY_OUTER = 1
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -96,6 +116,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_last_stats", "vsg_render_color", "vsg_render_rasterize", "vsg_render_last_vector_stats",
     "vsg_render_level_regions", "vsg_render_last_level_stats",
     "vsg_render_level_components", "vsg_render_last_component_stats",
+    "vsg_render_level_boundaries", "vsg_render_last_boundary_stats",
 ]
 
 
@@ -137,6 +158,9 @@ def lib():
                                               C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp,
                                               C.c_int]
     L.vsg_render_last_component_stats.argtypes = [vp, C.POINTER(VsgRenderComponentStats)]
+    L.vsg_render_level_boundaries.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                              C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_boundary_stats.argtypes = [vp, C.POINTER(VsgRenderBoundaryStats)]
     _handle = L
     return L
 
@@ -353,6 +377,54 @@ class SegmentationRenderer(_capi.Handle):
         """vsg_render_last_component_stats of the last level_components call, as a dict."""
         s = VsgRenderComponentStats()
         check(lib().vsg_render_last_component_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def level_boundaries(self, seg_bytes, level=0, connectedness=0, outer=False, boundaries_out=None,
+                         points_out=None):
+        """The N4 boundary pixels (the reference's GetBoundary) of every region of hierarchy level `level`
+        (connectedness 0) or of every connected component of its regions (N4 or N8): (records, points).
+        records: a LEVEL_BOUNDARY_DTYPE array, record k belonging to record k of level_regions
+        (level_components); points: (n, 2) int32 {x, y}, grouped by boundary in that order, within a boundary
+        by y, then x.  outer=False: the pixels of a group with a 4-neighbour outside it; True: the positions
+        of [-1, W] x [-1, H] outside a group with a 4-neighbour in it, at their true x (the reference
+        reports x + 1).  Without outputs the counts are asked for first and both arrays are allocated
+        exactly.  boundaries_out / points_out: buffers to fill instead, both numpy (a LEVEL_BOUNDARY_DTYPE
+        array and a (capacity, 2) int32 array) or both torch CUDA tensors ((capacity, 4) int32 and
+        (capacity, 2) int32); the filled parts of them are returned."""
+        seg_bytes = bytes(seg_bytes)
+        which = BOUNDARY_OUTER if outer else BOUNDARY_INNER
+        nb, npts = C.c_size_t(), C.c_size_t()
+        if (boundaries_out is None) != (points_out is None):
+            raise ValueError("pass both outputs or neither")
+        if boundaries_out is None:
+            check(lib().vsg_render_level_boundaries(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                    which, None, 0, C.byref(nb), None, 0, C.byref(npts), VSG_MEM_HOST))
+            boundaries_out = np.empty(nb.value, LEVEL_BOUNDARY_DTYPE)
+            points_out = np.empty((npts.value, 2), np.int32)
+        if _capi.is_torch(boundaries_out) != _capi.is_torch(points_out):
+            raise ValueError("both outputs have to be numpy arrays or both torch tensors")
+        if _capi.is_torch(boundaries_out):
+            if (boundaries_out.dim() != 2 or boundaries_out.shape[1] != LEVEL_BOUNDARY_WORDS
+                    or str(boundaries_out.dtype) != "torch.int32"):
+                raise ValueError("boundaries_out has to be (capacity, %d) int32" % LEVEL_BOUNDARY_WORDS)
+        elif boundaries_out.dtype != LEVEL_BOUNDARY_DTYPE or boundaries_out.ndim != 1:
+            raise ValueError("boundaries_out has to be a one-dimensional LEVEL_BOUNDARY_DTYPE array")
+        if (len(points_out.shape) != 2 or points_out.shape[1] != 2
+                or str(points_out.dtype).replace("torch.", "") != "int32"):
+            raise ValueError("points_out has to be (capacity, 2) int32")
+        pb, mem = _capi.contiguous_ptr(boundaries_out)
+        pp, mem_p = _capi.contiguous_ptr(points_out)
+        if mem != mem_p:
+            raise ValueError("both outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_boundaries(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                which, pb, boundaries_out.shape[0], C.byref(nb), pp,
+                                                points_out.shape[0], C.byref(npts), mem))
+        return boundaries_out[:nb.value], points_out[:npts.value]
+
+    def last_boundary_stats(self):
+        """vsg_render_last_boundary_stats of the last level_boundaries call, as a dict."""
+        s = VsgRenderBoundaryStats()
+        check(lib().vsg_render_last_boundary_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def last_vector_stats(self):

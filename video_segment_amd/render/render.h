@@ -1,4 +1,5 @@
-// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip),
+// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
+// boundaries.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -156,6 +157,48 @@ void LaunchCompTable(const uint32_t* label_sorted, const uint32_t* order, const 
 // The remaining fields of every component, by the kernel of LaunchLevelMoments; status->largest.
 void LaunchComponentMoments(const Interval* intervals, uint32_t n, uint32_t capacity_components,
                             int32_t* components, CompStatus* status, hipStream_t stream);
+
+// ---- level boundaries (boundaries.hip): the N4 boundary pixels of every group of an int32 plane -----
+
+constexpr int kLevelBoundaryWords = 4;   // vsg_render_level_boundary as int32 words
+
+enum BoundFlag {
+  BOUND_FLAG_OVERFLOW = 1,   // a key had no slot: the emit pass found more keys than the count pass
+  BOUND_FLAG_RANGE = 2,      // a sorted key, a rank or a record was out of range
+};
+
+// Written by the boundary kernels; read by the host after the count pass and at the end of a call.
+struct BoundStatus {
+  unsigned long long points;   // keys the count pass found
+  uint32_t emitted;            // slots the emit pass reserved
+  uint32_t boundaries;         // distinct groups among the keys
+  uint32_t largest;            // most points of one boundary
+  uint32_t flags;
+};
+
+// The boundary keys of the H x W plane (row pitch W; -1 and everything outside the frame: no group),
+// group << 32 | (y + 1) * (W + 2) + (x + 1).  outer false: the pixels of a group with a 4-neighbour
+// outside it; true: the positions of [-1, W] x [-1, H] outside a group with a 4-neighbour in it, once
+// per group.  emit false: status->points += their number, keys is not looked at.  emit true: the keys,
+// in no particular order, status->emitted of them; a slot at or beyond `capacity` is not written and
+// raises BOUND_FLAG_OVERFLOW.
+void LaunchBoundClassify(const int32_t* plane, int width, int height, bool outer, bool emit, uint32_t capacity,
+                         unsigned long long* keys, BoundStatus* status, hipStream_t stream);
+// Work space of BoundSort and of LevelRank on the sorted keys (the larger of the two).
+size_t BoundTempBytes(int64_t n, int end_bit);
+// The library radix sort on bits [0, end_bit) of the keys.
+hipError_t BoundSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                     int64_t n, int end_bit, hipStream_t stream);
+// n sorted keys with LevelRank's ranks -> n points {x, y} and the records {id, component, first_point,
+// num_points}; status->boundaries and status->largest.  comp_table: null (id = group, component = -1),
+// or the table of LaunchCompTable the groups index.  `records` has room for capacity_records entries.
+void LaunchBoundTable(const unsigned long long* keys_sorted, const uint32_t* rank, uint32_t n, int width, int height,
+                      uint32_t max_group, uint32_t capacity_records, const int32_t* comp_table, int32_t* points,
+                      int32_t* records, BoundStatus* status, hipStream_t stream);
+// Copies status->boundaries records and n points, or nothing when there are more records than
+// capacity_records or a flag is up.
+void LaunchBoundCopy(const int32_t* records, const int32_t* points, uint32_t n, uint32_t capacity_records,
+                     int32_t* records_out, int32_t* points_out, const BoundStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -17,6 +17,7 @@
 
 namespace {
 
+using vsg_render_impl::BoundStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
@@ -28,6 +29,7 @@ enum VecStage { VEC_WALK = 0, VEC_SORT, VEC_PAIRS, VEC_COUNT };
 enum LevelStage { LVL_RUNS = 0, LVL_SORT, LVL_TABLE, LVL_MOMENTS, LVL_COUNT };
 // CMP_WAIT: the stream idles while the host reads the number of components; reported with no stage
 enum CompStage { CMP_LINK = 0, CMP_ORDER, CMP_MOMENTS, CMP_LABEL, CMP_WAIT, CMP_COUNT };
+enum BoundStage { BND_COUNT = 0, BND_EMIT, BND_SORT, BND_TABLE, BND_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -326,7 +328,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock;
+  StageClock clock, vclock, lclock, cclock, bclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -350,11 +352,15 @@ struct vsg_render {
   // for the label fill; every region's first component; the label plane of a host output; the status
   // words and the pinned block they come back through
   Block d_comp_work, d_comp_table, d_comp_intervals, d_comp_fill, d_comp_first, d_labels, d_comp_status, h_comp;
+  // level boundaries: unsorted and sorted keys; their groups' ranks; the points; the records; the
+  // status words and the pinned block the status and host outputs come back through
+  Block d_bound_keys, d_bound_rank, d_bound_points, d_bound_records, d_bound_status, h_bound;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
   vsg_render_level_stats lstats;
   vsg_render_component_stats cstats;
+  vsg_render_boundary_stats bstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -620,6 +626,19 @@ struct LevelFront {
   Interval* intervals = nullptr;
 };
 
+// The id plane of the level calls in h->d_ids, as vsg_render_id_image paints it, with their rule for
+// ids; *max_id receives the largest id.  Returns whether the desc was vector-only; the rest as PaintIds.
+bool PaintLevelPlane(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int32_t* max_id) {
+  h->d_ids.Reserve((size_t)h->W * h->H * sizeof(int32_t), &h->allocations);
+  *max_id = 0;
+  return PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(), [&](int mapped) {
+    // -1 is the plane's "no region"; the sort key takes the id as an unsigned number
+    if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
+    *max_id = std::max(*max_id, mapped);
+    return (uint32_t)mapped;
+  });
+}
+
 // Paints the id plane as vsg_render_id_image does, finds its runs and waits for their number, which
 // sizes everything after it.  Fills the run fields of *ls.
 LevelFront PaintLevelRuns(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, vsg_render_level_stats* ls) {
@@ -627,15 +646,7 @@ LevelFront PaintLevelRuns(vsg_render* h, const uint8_t* seg, size_t seg_len, int
   const int W = h->W, H = h->H;
   LevelFront f;
   // ---- the id plane, as vsg_render_id_image paints it ----
-  h->d_ids.Reserve((size_t)W * H * sizeof(int32_t), &h->allocations);
-  int32_t max_id = 0;
-  f.vector = PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(), [&](int mapped) {
-    // -1 is the plane's "no region"; the sort key takes the id as an unsigned number
-    if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
-    max_id = std::max(max_id, mapped);
-    return (uint32_t)mapped;
-  });
-  f.max_id = max_id;
+  f.vector = PaintLevelPlane(h, seg, seg_len, level, &f.max_id);
 
   // ---- runs ----
   // Intervals that do not overlap give at most one run each; every end of an interval that lies
@@ -705,6 +716,163 @@ void SortLevelRuns(vsg_render* h, LevelFront* f, vsg_render_level_stats* ls) {
   ls->launches += 3;   // the sort and the scan count as one each
 }
 
+// vsg_render_level_components behind its argument checks.  labels_only: the call is made for
+// vsg_render_level_boundaries, which needs the label image in h->d_labels and id and component of every
+// entry of h->d_comp_table and nothing else: no output is looked at, no capacity is checked, the moments
+// are not computed and nothing is delivered but the two counts.
+void LevelComponents(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                     vsg_render_level_component* components, size_t capacity_components, size_t* num_components,
+                     int32_t* intervals, size_t capacity_intervals, size_t* num_intervals, int32_t* label_image,
+                     int mem_out, bool labels_only) {
+  using namespace vsg_render_impl;
+  CheckMem(mem_out, "outputs");
+  const bool count_only = !labels_only && !components && !intervals && !label_image && capacity_components == 0 &&
+                          capacity_intervals == 0;
+  const bool paint_labels = labels_only || label_image;
+  const int W = h->W, H = h->H;
+  if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+  DeviceGuard guard(h->device);
+  vsg_render_component_stats& cs = h->cstats;
+  std::memset(&cs, 0, sizeof(cs));
+  vsg_render_level_stats ls;   // of the shared front half; the last level_regions call's stay
+  std::memset(&ls, 0, sizeof(ls));
+
+  LevelFront f = PaintLevelRuns(h, seg, seg_len, level, &ls);
+  const uint32_t n = f.n;
+  *num_intervals = n;
+  cs.runs = n;
+  cs.runs_us = ls.runs_us;
+  if (!count_only && !labels_only && n && n <= capacity_intervals && (!components || !intervals)) {
+    Throw(VSG_ERR_INVALID, "an output is null");
+  }
+  h->d_comp_status.Reserve(sizeof(CompStatus), &h->allocations);
+  h->h_comp.Reserve(2 * sizeof(CompStatus) + sizeof(LevelStatus), &h->allocations);
+  CompStatus* status = h->d_comp_status.As<CompStatus>();
+  CompStatus* seen = h->h_comp.As<CompStatus>();   // [0] once the table is made, [1] at the end
+  LevelStatus* seen_level = reinterpret_cast<LevelStatus*>(seen + 2);
+  std::memset(seen, 0, 2 * sizeof(CompStatus) + sizeof(LevelStatus));
+  Interval* ordered = nullptr;
+  Interval* fill = nullptr;
+  int32_t* table = nullptr;
+  int launches = 0;
+  if (!n) h->cclock.Begin(h->stream);   // an empty frame still clears the label image
+  if (n) {
+    // ---- the runs sorted by (id, y, left_x), as vsg_render_level_regions has them ----
+    int label_bits = 1;
+    while (label_bits < 32 && ((uint64_t)(n - 1) >> label_bits)) ++label_bits;
+    const size_t temp_bytes = std::max<size_t>(CompTempBytes(n, label_bits), 16);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);   // before anything that uses the block is enqueued
+    SortLevelRuns(h, &f, &ls);
+
+    // ---- union-find, order, table ----
+    h->d_comp_work.Reserve((size_t)n * 6 * sizeof(uint32_t), &h->allocations);
+    h->d_comp_table.Reserve((size_t)n * sizeof(vsg_render_level_component), &h->allocations);
+    h->d_comp_intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+    h->d_comp_first.Reserve((size_t)f.cap_regions * sizeof(uint32_t), &h->allocations);
+    if (paint_labels) h->d_comp_fill.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+    uint32_t* parent = h->d_comp_work.As<uint32_t>();
+    uint32_t* label = parent + n;
+    uint32_t* index = label + n;
+    uint32_t* label_sorted = index + n;
+    uint32_t* order = label_sorted + n;
+    uint32_t* comp_rank = order + n;
+    ordered = h->d_comp_intervals.As<Interval>();
+    fill = paint_labels ? h->d_comp_fill.As<Interval>() : nullptr;
+    table = h->d_comp_table.As<int32_t>();
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(CompStatus), h->stream));
+    h->cclock.Begin(h->stream);
+    LaunchCompLink(f.keys_sorted, f.rights_sorted, n, W, connectedness == VSG_RENDER_CONNECT_N8 ? 1 : 0, parent,
+                   label, index, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->cclock.Mark(CMP_LINK);
+    VSG_HIP(CompSort(h->d_sort_temp.p, temp_bytes, label, label_sorted, index, order, n, label_bits, h->stream));
+    VSG_HIP(CompRank(h->d_sort_temp.p, temp_bytes, label_sorted, comp_rank, n, h->stream));
+    // a run has at most one component: n slots hold them all
+    LaunchCompTable(label_sorted, order, comp_rank, f.rank, f.intervals, n, n, f.cap_regions, ordered, fill, table,
+                    h->d_comp_first.As<uint32_t>(), f.status, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->cclock.Mark(CMP_ORDER);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
+    VSG_HIP(hipMemcpyAsync(seen_level, f.status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
+    launches += 11;   // the clear, five kernels, two copies; the sorts and the scans count as one each
+    VSG_HIP(hipStreamSynchronize(h->stream));   // the number of components decides what is delivered
+    if (seen_level->regions == 0 || seen_level->regions > f.cap_regions) {
+      Throw(VSG_ERR_INTERNAL, "the plane has more regions than the desc has ids");
+    }
+    if (seen[0].flags & COMP_FLAG_BOUND) Throw(VSG_ERR_INTERNAL, "the union-find did not end within its bound");
+    if ((seen[0].flags & COMP_FLAG_DROPPED) || seen[0].components == 0 || seen[0].components > n) {
+      Throw(VSG_ERR_INTERNAL, "a component had no slot");
+    }
+  }
+  const uint32_t n_components = seen[0].components;
+  *num_components = n_components;
+  cs.regions = seen_level->regions;
+  cs.components = n_components;
+  cs.links = (int64_t)seen[0].links;
+  auto finish = [&] {
+    float us[CMP_COUNT], lus[LVL_COUNT];
+    h->cclock.Read(us, CMP_COUNT);
+    cs.link_us = us[CMP_LINK];
+    cs.order_us = us[CMP_ORDER];
+    cs.moments_us = us[CMP_MOMENTS];
+    cs.label_us = us[CMP_LABEL];
+    if (n) {
+      h->lclock.Read(lus, LVL_COUNT);
+      cs.sort_us = lus[LVL_SORT] + lus[LVL_TABLE];
+    }
+    cs.launches = ls.launches + launches;
+    h->stats.launches += cs.launches;
+    h->stats.device_allocations = h->allocations;
+  };
+  if (count_only) {
+    finish();
+    return;
+  }
+  if (!labels_only && (n > capacity_intervals || n_components > capacity_components)) {
+    finish();
+    Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_components) + " components and " +
+                               std::to_string(n) + " intervals, the capacities are " +
+                               std::to_string(capacity_components) + " and " + std::to_string(capacity_intervals));
+  }
+
+  // ---- moments, label image, outputs ----
+  if (n) h->cclock.Mark(CMP_WAIT);
+  const hipMemcpyKind kind = mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
+  if (n && !labels_only) {
+    LaunchComponentMoments(ordered, n, n_components, table, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->cclock.Mark(CMP_MOMENTS);
+    ++launches;
+  }
+  if (paint_labels) {
+    const size_t bytes = (size_t)W * H * sizeof(int32_t);
+    uint32_t* plane = reinterpret_cast<uint32_t*>(label_image);   // device output: painted in place
+    if (labels_only || mem_out == VSG_MEM_HOST) {
+      h->d_labels.Reserve(bytes, &h->allocations);
+      plane = h->d_labels.As<uint32_t>();
+    }
+    VSG_HIP(hipMemsetAsync(plane, 0xff, bytes, h->stream));   // -1: no component
+    LaunchFill(fill, n, plane, W, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->cclock.Mark(CMP_LABEL);
+    launches += 1 + (n ? 1 : 0);
+    if (!labels_only && mem_out == VSG_MEM_HOST) {
+      VSG_HIP(hipMemcpyAsync(label_image, plane, bytes, hipMemcpyDeviceToHost, h->stream));
+      ++launches;
+    }
+  }
+  if (n && !labels_only) {
+    VSG_HIP(hipMemcpyAsync(components, table, (size_t)n_components * sizeof(vsg_render_level_component), kind,
+                           h->stream));
+    VSG_HIP(hipMemcpyAsync(intervals, ordered, (size_t)n * sizeof(Interval), kind, h->stream));
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
+    launches += 3;
+  }
+  VSG_HIP(hipStreamSynchronize(h->stream));
+  cs.largest_component_intervals = seen[1].largest;
+  finish();
+}
+
 }  // namespace
 
 extern "C" {
@@ -763,6 +931,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->cclock.Create(CMP_COUNT + 1);
     h->h_comp.pinned = true;
     std::memset(&h->cstats, 0, sizeof(h->cstats));
+    h->bclock.Create(BND_STAGES + 1);
+    h->h_bound.pinned = true;
+    std::memset(&h->bstats, 0, sizeof(h->bstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -1008,148 +1179,8 @@ int vsg_render_level_components(vsg_render* h, const uint8_t* seg, size_t seg_le
     if (!h) Throw(VSG_ERR_INVALID, "handle is null");
     if (!num_components || !num_intervals) Throw(VSG_ERR_INVALID, "a count pointer is null");
     *num_components = *num_intervals = 0;
-    CheckMem(mem_out, "outputs");
-    const bool count_only =
-        !components && !intervals && !label_image && capacity_components == 0 && capacity_intervals == 0;
-    const int W = h->W, H = h->H;
-    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
-    DeviceGuard guard(h->device);
-    vsg_render_component_stats& cs = h->cstats;
-    std::memset(&cs, 0, sizeof(cs));
-    vsg_render_level_stats ls;   // of the shared front half; the last level_regions call's stay
-    std::memset(&ls, 0, sizeof(ls));
-
-    LevelFront f = PaintLevelRuns(h, seg, seg_len, level, &ls);
-    const uint32_t n = f.n;
-    *num_intervals = n;
-    cs.runs = n;
-    cs.runs_us = ls.runs_us;
-    if (!count_only && n && n <= capacity_intervals && (!components || !intervals)) {
-      Throw(VSG_ERR_INVALID, "an output is null");
-    }
-    h->d_comp_status.Reserve(sizeof(CompStatus), &h->allocations);
-    h->h_comp.Reserve(2 * sizeof(CompStatus) + sizeof(LevelStatus), &h->allocations);
-    CompStatus* status = h->d_comp_status.As<CompStatus>();
-    CompStatus* seen = h->h_comp.As<CompStatus>();   // [0] once the table is made, [1] at the end
-    LevelStatus* seen_level = reinterpret_cast<LevelStatus*>(seen + 2);
-    std::memset(seen, 0, 2 * sizeof(CompStatus) + sizeof(LevelStatus));
-    Interval* ordered = nullptr;
-    Interval* fill = nullptr;
-    int32_t* table = nullptr;
-    int launches = 0;
-    if (!n) h->cclock.Begin(h->stream);   // an empty frame still clears the label image
-    if (n) {
-      // ---- the runs sorted by (id, y, left_x), as vsg_render_level_regions has them ----
-      int label_bits = 1;
-      while (label_bits < 32 && ((uint64_t)(n - 1) >> label_bits)) ++label_bits;
-      const size_t temp_bytes = std::max<size_t>(CompTempBytes(n, label_bits), 16);
-      h->d_sort_temp.Reserve(temp_bytes, &h->allocations);   // before anything that uses the block is enqueued
-      SortLevelRuns(h, &f, &ls);
-
-      // ---- union-find, order, table ----
-      h->d_comp_work.Reserve((size_t)n * 6 * sizeof(uint32_t), &h->allocations);
-      h->d_comp_table.Reserve((size_t)n * sizeof(vsg_render_level_component), &h->allocations);
-      h->d_comp_intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
-      h->d_comp_first.Reserve((size_t)f.cap_regions * sizeof(uint32_t), &h->allocations);
-      if (label_image) h->d_comp_fill.Reserve((size_t)n * sizeof(Interval), &h->allocations);
-      uint32_t* parent = h->d_comp_work.As<uint32_t>();
-      uint32_t* label = parent + n;
-      uint32_t* index = label + n;
-      uint32_t* label_sorted = index + n;
-      uint32_t* order = label_sorted + n;
-      uint32_t* comp_rank = order + n;
-      ordered = h->d_comp_intervals.As<Interval>();
-      fill = label_image ? h->d_comp_fill.As<Interval>() : nullptr;
-      table = h->d_comp_table.As<int32_t>();
-      VSG_HIP(hipMemsetAsync(status, 0, sizeof(CompStatus), h->stream));
-      h->cclock.Begin(h->stream);
-      LaunchCompLink(f.keys_sorted, f.rights_sorted, n, W, connectedness == VSG_RENDER_CONNECT_N8 ? 1 : 0, parent,
-                     label, index, status, h->stream);
-      VSG_HIP(hipGetLastError());
-      h->cclock.Mark(CMP_LINK);
-      VSG_HIP(CompSort(h->d_sort_temp.p, temp_bytes, label, label_sorted, index, order, n, label_bits, h->stream));
-      VSG_HIP(CompRank(h->d_sort_temp.p, temp_bytes, label_sorted, comp_rank, n, h->stream));
-      // a run has at most one component: n slots hold them all
-      LaunchCompTable(label_sorted, order, comp_rank, f.rank, f.intervals, n, n, f.cap_regions, ordered, fill, table,
-                      h->d_comp_first.As<uint32_t>(), f.status, status, h->stream);
-      VSG_HIP(hipGetLastError());
-      h->cclock.Mark(CMP_ORDER);
-      VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
-      VSG_HIP(hipMemcpyAsync(seen_level, f.status, sizeof(LevelStatus), hipMemcpyDeviceToHost, h->stream));
-      launches += 11;   // the clear, five kernels, two copies; the sorts and the scans count as one each
-      VSG_HIP(hipStreamSynchronize(h->stream));   // the number of components decides what is delivered
-      if (seen_level->regions == 0 || seen_level->regions > f.cap_regions) {
-        Throw(VSG_ERR_INTERNAL, "the plane has more regions than the desc has ids");
-      }
-      if (seen[0].flags & COMP_FLAG_BOUND) Throw(VSG_ERR_INTERNAL, "the union-find did not end within its bound");
-      if ((seen[0].flags & COMP_FLAG_DROPPED) || seen[0].components == 0 || seen[0].components > n) {
-        Throw(VSG_ERR_INTERNAL, "a component had no slot");
-      }
-    }
-    const uint32_t n_components = seen[0].components;
-    *num_components = n_components;
-    cs.regions = seen_level->regions;
-    cs.components = n_components;
-    cs.links = (int64_t)seen[0].links;
-    auto finish = [&] {
-      float us[CMP_COUNT], lus[LVL_COUNT];
-      h->cclock.Read(us, CMP_COUNT);
-      cs.link_us = us[CMP_LINK];
-      cs.order_us = us[CMP_ORDER];
-      cs.moments_us = us[CMP_MOMENTS];
-      cs.label_us = us[CMP_LABEL];
-      if (n) {
-        h->lclock.Read(lus, LVL_COUNT);
-        cs.sort_us = lus[LVL_SORT] + lus[LVL_TABLE];
-      }
-      cs.launches = ls.launches + launches;
-      h->stats.launches += cs.launches;
-      h->stats.device_allocations = h->allocations;
-    };
-    if (count_only) return finish();
-    if (n > capacity_intervals || n_components > capacity_components) {
-      finish();
-      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_components) + " components and " +
-                                 std::to_string(n) + " intervals, the capacities are " +
-                                 std::to_string(capacity_components) + " and " + std::to_string(capacity_intervals));
-    }
-
-    // ---- moments, label image, outputs ----
-    if (n) h->cclock.Mark(CMP_WAIT);
-    const hipMemcpyKind kind = mem_out == VSG_MEM_HOST ? hipMemcpyDeviceToHost : hipMemcpyDeviceToDevice;
-    if (n) {
-      LaunchComponentMoments(ordered, n, n_components, table, status, h->stream);
-      VSG_HIP(hipGetLastError());
-      h->cclock.Mark(CMP_MOMENTS);
-      ++launches;
-    }
-    if (label_image) {
-      const size_t bytes = (size_t)W * H * sizeof(int32_t);
-      uint32_t* plane = reinterpret_cast<uint32_t*>(label_image);   // device output: painted in place
-      if (mem_out == VSG_MEM_HOST) {
-        h->d_labels.Reserve(bytes, &h->allocations);
-        plane = h->d_labels.As<uint32_t>();
-      }
-      VSG_HIP(hipMemsetAsync(plane, 0xff, bytes, h->stream));   // -1: no component
-      LaunchFill(fill, n, plane, W, h->stream);
-      VSG_HIP(hipGetLastError());
-      h->cclock.Mark(CMP_LABEL);
-      launches += 1 + (n ? 1 : 0);
-      if (mem_out == VSG_MEM_HOST) {
-        VSG_HIP(hipMemcpyAsync(label_image, plane, bytes, hipMemcpyDeviceToHost, h->stream));
-        ++launches;
-      }
-    }
-    if (n) {
-      VSG_HIP(hipMemcpyAsync(components, table, (size_t)n_components * sizeof(vsg_render_level_component), kind,
-                             h->stream));
-      VSG_HIP(hipMemcpyAsync(intervals, ordered, (size_t)n * sizeof(Interval), kind, h->stream));
-      VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(CompStatus), hipMemcpyDeviceToHost, h->stream));
-      launches += 3;
-    }
-    VSG_HIP(hipStreamSynchronize(h->stream));
-    cs.largest_component_intervals = seen[1].largest;
-    finish();
+    LevelComponents(h, seg, seg_len, level, connectedness, components, capacity_components, num_components, intervals,
+                    capacity_intervals, num_intervals, label_image, mem_out, false);
   });
 }
 
@@ -1157,6 +1188,191 @@ int vsg_render_last_component_stats(vsg_render* h, vsg_render_component_stats* s
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->cstats;
+  });
+}
+
+int vsg_render_level_boundaries(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                                int which, vsg_render_level_boundary* boundaries, size_t capacity_boundaries,
+                                size_t* num_boundaries, int32_t* points, size_t capacity_points, size_t* num_points,
+                                int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_level_boundary) == kLevelBoundaryWords * sizeof(int32_t), "moved as int32 words");
+    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    if (which != VSG_RENDER_BOUNDARY_INNER && which != VSG_RENDER_BOUNDARY_OUTER) {
+      Throw(VSG_ERR_INVALID, "which is neither VSG_RENDER_BOUNDARY_INNER nor VSG_RENDER_BOUNDARY_OUTER");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_boundaries || !num_points) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_boundaries = *num_points = 0;
+    CheckMem(mem_out, "outputs");
+    const bool count_only = !boundaries && !points && capacity_boundaries == 0 && capacity_points == 0;
+    const bool outer = which == VSG_RENDER_BOUNDARY_OUTER;
+    const int W = h->W, H = h->H;
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+    DeviceGuard guard(h->device);
+    vsg_render_boundary_stats& bs = h->bstats;
+    std::memset(&bs, 0, sizeof(bs));
+
+    // ---- the plane: the level's ids, or the indices of its regions' components ----
+    const int32_t* plane = nullptr;
+    const int32_t* comp_table = nullptr;
+    uint32_t max_group = 0;
+    uint64_t groups_bound = 0;   // no more groups than this
+    bool vector = false;
+    if (connectedness == 0) {
+      int32_t max_id = 0;
+      vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
+      plane = h->d_ids.As<int32_t>();
+      max_group = (uint32_t)max_id;
+      groups_bound = (uint64_t)h->stats.distinct_ids;
+      bs.launches = h->stats.launches;
+    } else {
+      size_t n_components = 0, n_intervals = 0;
+      LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
+                      nullptr, VSG_MEM_DEVICE, true);
+      plane = h->d_labels.As<int32_t>();
+      comp_table = h->d_comp_table.As<int32_t>();
+      max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
+      groups_bound = n_components;
+      const vsg_render_component_stats& cs = h->cstats;
+      bs.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                    cs.label_us;
+      bs.launches = h->stats.launches;
+    }
+
+    // ---- count: the number of points sizes everything below ----
+    h->d_bound_status.Reserve(sizeof(BoundStatus), &h->allocations);
+    h->h_bound.Reserve(2 * sizeof(BoundStatus), &h->allocations);
+    BoundStatus* status = h->d_bound_status.As<BoundStatus>();
+    BoundStatus* seen = h->h_bound.As<BoundStatus>();   // [0] after the count, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(BoundStatus));
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(BoundStatus), h->stream));
+    h->bclock.Begin(h->stream);
+    LaunchBoundClassify(plane, W, H, outer, false, 0, nullptr, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->bclock.Mark(BND_COUNT);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(BoundStatus), hipMemcpyDeviceToHost, h->stream));
+    int launches = 3;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[BND_STAGES];
+      h->bclock.Read(us, BND_STAGES);
+      bs.count_us = us[BND_COUNT];
+    }
+    if (connectedness == 0) {
+      float us[STAGE_COUNT];
+      h->clock.Read(us, STAGE_COUNT);
+      h->stats.clear_us = us[STAGE_CLEAR];
+      h->stats.fill_us = us[STAGE_FILL];
+      bs.plane_us = us[STAGE_CLEAR] + us[STAGE_FILL];
+      if (vector) h->CheckVector();
+    }
+    auto finish = [&] {
+      bs.launches += launches;
+      h->stats.launches += launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    if (seen[0].points > 0x7fffffffull) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the level has more than 2^31 - 1 boundary points");
+    }
+    const uint32_t n = (uint32_t)seen[0].points;
+    *num_points = n;
+    bs.points = n;
+    if (n == 0) return finish();   // no group at all: both lists are empty
+
+    // ---- emit, sort, table ----
+    const uint32_t cap_records = (uint32_t)std::min<uint64_t>(groups_bound, n);   // every group has a point
+    if (cap_records == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
+    const bool points_fit = n <= capacity_points;
+    const bool deliver = !count_only && points_fit;
+    if (deliver && (!boundaries || !points)) Throw(VSG_ERR_INVALID, "an output is null");
+    int group_bits = 1;
+    while (group_bits < 32 && (max_group >> group_bits)) ++group_bits;
+    const int end_bit = 32 + group_bits;
+    const size_t temp_bytes = std::max<size_t>(BoundTempBytes(n, end_bit), 16);
+    const size_t record_bytes = (size_t)cap_records * sizeof(vsg_render_level_boundary);
+    const size_t point_bytes = (size_t)n * 2 * sizeof(int32_t);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    h->d_bound_keys.Reserve((size_t)n * 2 * sizeof(unsigned long long), &h->allocations);
+    h->d_bound_rank.Reserve((size_t)n * sizeof(uint32_t), &h->allocations);
+    h->d_bound_points.Reserve(point_bytes, &h->allocations);
+    h->d_bound_records.Reserve(record_bytes, &h->allocations);
+    unsigned long long* keys = h->d_bound_keys.As<unsigned long long>();
+    unsigned long long* keys_sorted = keys + n;
+    uint32_t* rank = h->d_bound_rank.As<uint32_t>();
+    int32_t* d_points = h->d_bound_points.As<int32_t>();
+    int32_t* d_records = h->d_bound_records.As<int32_t>();
+    h->bclock.Begin(h->stream);
+    LaunchBoundClassify(plane, W, H, outer, true, n, keys, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->bclock.Mark(BND_EMIT);
+    VSG_HIP(BoundSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
+    h->bclock.Mark(BND_SORT);
+    VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, keys_sorted, rank, n, h->stream));
+    LaunchBoundTable(keys_sorted, rank, n, W, H, max_group, cap_records, comp_table, d_points, d_records, status,
+                     h->stream);
+    VSG_HIP(hipGetLastError());
+    h->bclock.Mark(BND_TABLE);
+    launches += 5;   // emit, the sort and the scan counted as one each, table, finish
+    if (deliver && mem_out == VSG_MEM_DEVICE) {
+      // the number of boundaries is on the device: the copy decides there whether they fit
+      LaunchBoundCopy(d_records, d_points, n, (uint32_t)std::min<size_t>(capacity_boundaries, cap_records),
+                      reinterpret_cast<int32_t*>(boundaries), points, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      ++launches;
+    } else if (deliver) {
+      // through the pinned block; handed to the caller once the number of boundaries is known
+      h->h_bound.Reserve(2 * sizeof(BoundStatus) + record_bytes + point_bytes, &h->allocations);
+      seen = h->h_bound.As<BoundStatus>();
+      char* stage = reinterpret_cast<char*>(seen + 2);
+      VSG_HIP(hipMemcpyAsync(stage, d_records, record_bytes, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(stage + record_bytes, d_points, point_bytes, hipMemcpyDeviceToHost, h->stream));
+      launches += 2;
+    }
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(BoundStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[BND_STAGES];
+      h->bclock.Read(us, BND_STAGES);
+      bs.emit_us = us[BND_EMIT];
+      bs.sort_us = us[BND_SORT];
+      bs.table_us = us[BND_TABLE];
+    }
+    finish();
+    if ((seen[1].flags & BOUND_FLAG_OVERFLOW) || seen[1].emitted != n) {
+      Throw(VSG_ERR_INTERNAL, "the emit pass found other boundary points than the count pass");
+    }
+    if ((seen[1].flags & BOUND_FLAG_RANGE) || seen[1].boundaries == 0 || seen[1].boundaries > cap_records ||
+        (comp_table && seen[1].boundaries != groups_bound)) {
+      Throw(VSG_ERR_INTERNAL, "a sorted boundary key or a boundary record is out of range");
+    }
+    const size_t n_boundaries = seen[1].boundaries;
+    *num_boundaries = n_boundaries;
+    bs.boundaries = (int64_t)n_boundaries;
+    bs.largest_boundary_points = seen[1].largest;
+    if (count_only) return;
+    if (!points_fit || n_boundaries > capacity_boundaries) {
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_boundaries) + " boundaries and " + std::to_string(n) +
+                                 " points, the capacities are " + std::to_string(capacity_boundaries) + " and " +
+                                 std::to_string(capacity_points));
+    }
+    if (mem_out == VSG_MEM_HOST) {
+      const char* stage = reinterpret_cast<const char*>(h->h_bound.As<BoundStatus>() + 2);
+      std::memcpy(boundaries, stage, n_boundaries * sizeof(vsg_render_level_boundary));
+      std::memcpy(points, stage + record_bytes, point_bytes);
+    }
+  });
+}
+
+int vsg_render_last_boundary_stats(vsg_render* h, vsg_render_boundary_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->bstats;
   });
 }
 
