@@ -41,7 +41,9 @@
  * per connected component, and vsg_render_level_boundaries the boundary point lists of either: the
  * reference's GetBoundary (segment_util/segmentation_boundary.{h,cpp}), the N4 inner or outer boundary
  * pixels of a rasterization in row-major order.  Contour tracing and vectorisation at a level
- * (BoundaryComputation, segmentation/boundary.cpp) are not offered.
+ * (BoundaryComputation, segmentation/boundary.cpp) are not offered.  Which regions or components of a
+ * level touch in a frame, and along how many pixel sides, is what vsg_render_level_adjacency returns;
+ * the reference has no per-frame counterpart (CompoundRegion.neighbor_id covers a chunk in 3-D).
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -334,6 +336,84 @@ typedef struct vsg_render_boundary_stats {
   int launches;
 } vsg_render_boundary_stats;
 int vsg_render_last_boundary_stats(vsg_render* h, vsg_render_boundary_stats* s);
+
+#define VSG_RENDER_ADJACENT_N4 1   /* pixel sides only */
+#define VSG_RENDER_ADJACENT_N8 2   /* pixel sides and diagonal contacts */
+
+/* One node of the adjacency graph, as vsg_render_level_adjacency returns it. */
+typedef struct vsg_render_level_node {   /* 28 bytes, no padding */
+  int32_t id;                /* region id at `level` */
+  int32_t component;         /* index among its region's components; -1 with connectedness 0 */
+  int32_t first_edge, num_edges;
+  int32_t border_frame;      /* pixel sides of the group on the frame edge */
+  int32_t border_uncovered;  /* pixel sides next to an uncovered (-1) pixel inside the frame */
+  int32_t border_shared;     /* pixel sides next to another group = sum of shared_n4 of its edges */
+} vsg_render_level_node;
+
+/* One directed edge of the adjacency graph. */
+typedef struct vsg_render_level_edge {   /* 16 bytes, no padding */
+  int32_t neighbour;         /* index of the neighbour in the node list */
+  int32_t neighbour_id;      /* its region id (equal to the node's own id for two components of one region) */
+  int32_t shared_n4;         /* pixel sides the two groups share */
+  int32_t shared_diagonal;   /* diagonal contacts; 0 with VSG_RENDER_ADJACENT_N4 */
+} vsg_render_level_edge;
+
+/* The region adjacency graph of hierarchy level `level`: which regions, or which connected components
+ * of its regions, touch which, and along how much border.  Computed on the device.
+ *
+ * The plane.  P is the plane of vsg_render_level_boundaries: the id plane of vsg_render_id_image at
+ * `level` for connectedness 0, or the label image of vsg_render_level_components for
+ * VSG_RENDER_CONNECT_N4 / _N8 (that call is made internally: vsg_render_last_component_stats then
+ * describes it).  Positions outside the frame are not pixels.  A group g >= 0 is a value of P.
+ *
+ * Sides.  Every pixel of g has four sides, each classified by what lies across it:
+ *   outside the frame:           the side counts to border_frame;
+ *   an in-frame pixel with -1:   the side counts to border_uncovered;
+ *   a pixel of another group b:  the side counts to border_shared of g and to shared_n4 of the edge g -> b;
+ *   a pixel of g:                the side counts to nothing.
+ * So border_frame + border_uncovered + border_shared is the group's perimeter in pixel sides.
+ *
+ * Diagonal contacts.  With VSG_RENDER_ADJACENT_N8, every pair of in-frame positions {(x, y), (x+1, y+1)}
+ * or {(x+1, y), (x, y+1)} with different non-negative values a, b adds 1 to shared_diagonal of a -> b and
+ * of b -> a; the other two pixels of that 2 x 2 block do not matter.  An edge exists when
+ * shared_n4 + shared_diagonal > 0.  With VSG_RENDER_ADJACENT_N4 only sides make edges, and
+ * shared_diagonal is 0.
+ *
+ * Nodes.  One node per group; every group has at least one bordering side, so no group is lost.  The
+ * order is that of the sibling calls: ascending id for connectedness 0, record k belonging to record k
+ * of vsg_render_level_regions; the component list's order otherwise, record k belonging to record k of
+ * vsg_render_level_components.
+ *
+ * Edges.  Grouped by node in node order, and within a node by ascending `neighbour`.  The graph is
+ * symmetric: a -> b is listed iff b -> a is, with equal counts.  Under N4 components two components of
+ * one region can touch diagonally; that is an edge with neighbour_id equal to the node's own id.
+ *
+ * Decode, hierarchy rules (the desc's own hierarchy replaces the kept one), refusals, the non-negative
+ * ids and the handling of vector-only descs are those of vsg_render_level_regions.
+ * *num_nodes and *num_edges are always set on VSG_OK and when a capacity is too small; in that case the
+ * call fails with VSG_ERR_INVALID and neither output is touched.  nodes == NULL and edges == NULL with
+ * both capacities 0 asks for the counts only (VSG_OK; needs the device).  A null handle, a null count
+ * pointer, a connectedness other than 0, VSG_RENDER_CONNECT_N4 and VSG_RENDER_CONNECT_N8 or a
+ * neighbourhood other than the two above is VSG_ERR_INVALID and touches no device.  A frame with no
+ * covered pixel returns zero nodes and zero edges.  Both lists in mem_out memory. */
+int vsg_render_level_adjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                               int neighbourhood, vsg_render_level_node* nodes, size_t capacity_nodes,
+                               size_t* num_nodes, vsg_render_level_edge* edges, size_t capacity_edges,
+                               size_t* num_edges, int mem_out);
+
+/* What the last vsg_render_level_adjacency call of the handle did.  sides: the sum over the nodes of
+ * the three border fields plus the sum over the edges of shared_diagonal, a property of the plane.
+ * keys: what the radix sort saw; equal to sides, since equal keys are not combined before the sort.
+ * Device times are HIP events around the stages: making the plane (as in vsg_render_boundary_stats);
+ * the count pass of k_adj_classify; its emit pass; the radix sort; the clears, the scan, k_adj_table,
+ * k_adj_finish and k_adj_resolve.  The last three are not run, and nodes, edges and largest_node_edges
+ * are 0, when there is no key. */
+typedef struct vsg_render_adjacency_stats {
+  int64_t sides, keys, nodes, edges, largest_node_edges;
+  float plane_us, count_us, emit_us, sort_us, table_us;
+  int launches;
+} vsg_render_adjacency_stats;
+int vsg_render_last_adjacency_stats(vsg_render* h, vsg_render_adjacency_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -42,6 +42,15 @@ components, inner and outer.  Per call the five stage times of vsg_render_bounda
 and boundaries are recorded; in the same run vsg_render_level_components (N4, lists and label image in
 device memory) on the same desc and handle is timed with its six stage times: the yardstick.  No pass or
 fail threshold.
+
+    python tools/render_probe.py --level-adjacency [--reps 30] [--out profiles/level_adjacency.json]
+
+The adjacency leg: the same descs and levels asked for their adjacency graph (vsg_render_level_adjacency,
+outputs in device memory): of the regions (connectedness 0) and of their N4 components, with pixel sides
+only (N4) and with diagonal contacts (N8).  Per call the five stage times of vsg_render_adjacency_stats,
+launches, sides, keys, nodes, edges and the largest degree are recorded; in the same run
+vsg_render_level_boundaries (inner, same connectedness, outputs in device memory) on the same desc and
+handle is timed: a point of comparison, nothing more.  No pass or fail threshold.
 """
 import argparse
 import json
@@ -74,11 +83,15 @@ def main():
                     help="the component leg instead (profiles/level_components.json)")
     ap.add_argument("--level-boundaries", action="store_true",
                     help="the boundary leg instead (profiles/level_boundaries.json)")
+    ap.add_argument("--level-adjacency", action="store_true",
+                    help="the adjacency leg instead (profiles/level_adjacency.json)")
     args = ap.parse_args()
-    if (args.level_regions or args.level_components or args.level_boundaries) and "--reps" not in sys.argv:
+    if ((args.level_regions or args.level_components or args.level_boundaries or args.level_adjacency)
+            and "--reps" not in sys.argv):
         args.reps = 30
     if args.out is None:
-        name = ("level_boundaries.json" if args.level_boundaries else
+        name = ("level_adjacency.json" if args.level_adjacency else
+                "level_boundaries.json" if args.level_boundaries else
                 "level_components.json" if args.level_components else "level_regions.json" if args.level_regions
                 else "vector_raster.json" if args.vector else "render_kernels.json")
         args.out = os.path.join(ROOT, "profiles", name)
@@ -93,6 +106,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.level_adjacency:
+        return adjacency_leg(args, result, dev)
     if args.level_boundaries:
         return boundaries_leg(args, result, dev)
     if args.level_components:
@@ -369,6 +384,47 @@ def boundaries_leg(args, result, dev):
                             "largest_boundary_points": st["largest_boundary_points"], "launches": st["launches"],
                             "runs": cst["runs"], "components": cst["components"],
                             "level_components_launches": cst["launches"]}
+                    case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+                    result["cases"].append(case)
+                    print(json.dumps(case), flush=True)
+                    with open(args.out, "w") as f:
+                        json.dump(result, f, indent=1)
+                        f.write("\n")
+        r.close()
+    print("wrote", args.out)
+
+
+def adjacency_leg(args, result, dev):
+    import torch
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    for size, W, H, seg, height in level_descs(args):
+        r = vsg.SegmentationRenderer(W, H, has_video=False)
+        for level in sorted({0, height // 2, max(height - 1, 0)}):
+            for mode, connect in (("regions", 0), ("components_N4", render.N4)):
+                nb, npts = (len(a) for a in r.level_boundaries(seg, level, connect, False))
+                records = torch.empty((nb, render.LEVEL_BOUNDARY_WORDS), dtype=torch.int32, device=dev)
+                points = torch.empty((npts, 2), dtype=torch.int32, device=dev)
+                for name, hood in (("N4", render.ADJACENT_N4), ("N8", render.ADJACENT_N8)):
+                    nn, ne = (len(a) for a in r.level_adjacency(seg, level, connect, hood))
+                    nodes = torch.empty((nn, render.LEVEL_NODE_WORDS), dtype=torch.int32, device=dev)
+                    edges = torch.empty((ne, render.LEVEL_EDGE_WORDS), dtype=torch.int32, device=dev)
+                    stage_keys = ["plane_us", "count_us", "emit_us", "sort_us", "table_us"]
+                    rows = {k: [] for k in stage_keys + ["call_ms", "level_boundaries_call_ms"]}
+                    for it in range(args.warmup + args.reps):
+                        t0 = time.perf_counter()
+                        r.level_adjacency(seg, level, connect, hood, nodes_out=nodes, edges_out=edges)
+                        st = dict(r.last_adjacency_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
+                        t0 = time.perf_counter()
+                        r.level_boundaries(seg, level, connect, False, boundaries_out=records, points_out=points)
+                        st["level_boundaries_call_ms"] = (time.perf_counter() - t0) * 1e3
+                        if it >= args.warmup:
+                            for k in rows:
+                                rows[k].append(st[k])
+                    case = {"size": size, "level": level, "hierarchy_levels": height, "mode": mode,
+                            "neighbourhood": name, "sides": st["sides"], "keys": st["keys"], "nodes": st["nodes"],
+                            "edges": st["edges"], "largest_node_edges": st["largest_node_edges"],
+                            "launches": st["launches"]}
                     case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
                     result["cases"].append(case)
                     print(json.dumps(case), flush=True)

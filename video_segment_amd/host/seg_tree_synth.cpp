@@ -25,6 +25,12 @@
 // or of their connected components (N4, or N8), of every frame and prints a line
 // level_boundaries=<sum> boundary_points=<sum> boundary_fnv1a32=<hash of both lists' bytes>.
 //
+//   --level_adjacency <level> [--adjacency_n8] [--adjacency_components [--components_n8]]
+// asks vsg_render_level_adjacency for the adjacency graph (pixel sides, or with --adjacency_n8 also
+// diagonal contacts) of that level's regions, or of their connected components (N4, or N8), of every
+// frame and prints a line
+// level_adjacency_nodes=<sum> adjacency_edges=<sum> adjacency_fnv1a32=<hash of both lists' bytes, nodes first>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -421,6 +427,70 @@ class LevelBoundariesSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_adjacency: the same for the adjacency graph of a level's regions or of their connected
+// components (vsg_render_level_adjacency), nodes first.
+class LevelAdjacencySinkUnit : public VideoUnit {
+ public:
+  LevelAdjacencySinkUnit(int level, int connectedness, bool n8, int device)
+      : level_(level), connect_(connectedness),
+        neighbourhood_(n8 ? VSG_RENDER_ADJACENT_N8 : VSG_RENDER_ADJACENT_N4), device_(device) {}
+  ~LevelAdjacencySinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t nn = 0, ne = 0;
+    VF_CHECK(vsg_render_level_adjacency(render_, seg, desc.wire.size(), level_, connect_, neighbourhood_, nullptr, 0,
+                                        &nn, nullptr, 0, &ne, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    nodes_buf_.resize(nn);
+    edges_buf_.resize(ne);
+    if (nn) {
+      VF_CHECK(vsg_render_level_adjacency(render_, seg, desc.wire.size(), level_, connect_, neighbourhood_,
+                                          nodes_buf_.data(), nn, &nn, edges_buf_.data(), ne, &ne,
+                                          VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+    }
+    Hash(nodes_buf_.data(), nn * sizeof(vsg_render_level_node));
+    Hash(edges_buf_.data(), ne * sizeof(vsg_render_level_edge));
+    nodes_ += (long)nn;
+    edges_ += (long)ne;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long nodes() const { return nodes_; }
+  long edges() const { return edges_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, neighbourhood_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_node> nodes_buf_;
+  std::vector<vsg_render_level_edge> edges_buf_;
+  long nodes_ = 0, edges_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -519,6 +589,11 @@ struct Flags {
   // --boundaries_components
   int level_boundaries = -1;
   bool boundaries_outer = false, boundaries_components = false;
+  // vsg_render_level_adjacency at this level for every frame; < 0: off.  Pixel sides of the regions, or
+  // with --adjacency_n8 also diagonal contacts, of the components (N4, or N8 with --components_n8) with
+  // --adjacency_components
+  int level_adjacency = -1;
+  bool adjacency_n8 = false, adjacency_components = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -551,7 +626,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     static const char* kBools[] = {"flow", "use_pipeline", "over_segment", "write_to_file", "save_flow",
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
-                                   "boundaries_outer", "boundaries_components", "help"};
+                                   "boundaries_outer", "boundaries_components", "adjacency_n8",
+                                   "adjacency_components", "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -601,6 +677,9 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_boundaries") f->level_boundaries = atoi(v.c_str());
     else if (a == "boundaries_outer") f->boundaries_outer = bv;
     else if (a == "boundaries_components") f->boundaries_components = bv;
+    else if (a == "level_adjacency") f->level_adjacency = atoi(v.c_str());
+    else if (a == "adjacency_n8") f->adjacency_n8 = bv;
+    else if (a == "adjacency_components") f->adjacency_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -817,6 +896,16 @@ int main(int argc, char** argv) {
     boundaries_sink->AttachTo(input);
     input = boundaries_sink.get();
   }
+  std::unique_ptr<LevelAdjacencySinkUnit> adjacency_sink;
+  if (FLAGS.level_adjacency >= 0) {
+    const int connectedness = !FLAGS.adjacency_components ? 0
+                              : FLAGS.components_n8       ? VSG_RENDER_CONNECT_N8
+                                                          : VSG_RENDER_CONNECT_N4;
+    adjacency_sink.reset(
+        new LevelAdjacencySinkUnit(FLAGS.level_adjacency, connectedness, FLAGS.adjacency_n8, FLAGS.device));
+    adjacency_sink->AttachTo(input);
+    input = adjacency_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -871,6 +960,10 @@ int main(int argc, char** argv) {
   if (boundaries_sink) {
     std::printf("level_boundaries=%ld boundary_points=%ld boundary_fnv1a32=%08x\n", boundaries_sink->boundaries(),
                 boundaries_sink->points(), boundaries_sink->hash());
+  }
+  if (adjacency_sink) {
+    std::printf("level_adjacency_nodes=%ld adjacency_edges=%ld adjacency_fnv1a32=%08x\n", adjacency_sink->nodes(),
+                adjacency_sink->edges(), adjacency_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

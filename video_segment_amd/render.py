@@ -72,6 +72,16 @@ class VsgRenderBoundaryStats(_capi.Structure):
     ]
 
 
+class VsgRenderAdjacencyStats(_capi.Structure):
+    _fields_ = [
+        ("sides", C.c_int64), ("keys", C.c_int64), ("nodes", C.c_int64), ("edges", C.c_int64),
+        ("largest_node_edges", C.c_int64),
+        ("plane_us", C.c_float), ("count_us", C.c_float), ("emit_us", C.c_float), ("sort_us", C.c_float),
+        ("table_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -104,6 +114,25 @@ LEVEL_BOUNDARY_WORDS = 4
 BOUNDARY_INNER = 0
 BOUNDARY_OUTER = 1
 
+# vsg_render_level_node: 28 bytes, no padding
+LEVEL_NODE_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("first_edge", np.int32), ("num_edges", np.int32),
+    ("border_frame", np.int32), ("border_uncovered", np.int32), ("border_shared", np.int32),
+])
+assert LEVEL_NODE_DTYPE.itemsize == 28
+LEVEL_NODE_WORDS = 7
+
+# vsg_render_level_edge: 16 bytes, no padding
+LEVEL_EDGE_DTYPE = np.dtype([
+    ("neighbour", np.int32), ("neighbour_id", np.int32), ("shared_n4", np.int32), ("shared_diagonal", np.int32),
+])
+assert LEVEL_EDGE_DTYPE.itemsize == 16
+LEVEL_EDGE_WORDS = 4
+
+# VSG_RENDER_ADJACENT_N4 / _N8
+ADJACENT_N4 = 1
+ADJACENT_N8 = 2
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -117,6 +146,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_regions", "vsg_render_last_level_stats",
     "vsg_render_level_components", "vsg_render_last_component_stats",
     "vsg_render_level_boundaries", "vsg_render_last_boundary_stats",
+    "vsg_render_level_adjacency", "vsg_render_last_adjacency_stats",
 ]
 
 
@@ -161,6 +191,9 @@ def lib():
     L.vsg_render_level_boundaries.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
                                               C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_boundary_stats.argtypes = [vp, C.POINTER(VsgRenderBoundaryStats)]
+    L.vsg_render_level_adjacency.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
+                                             C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_adjacency_stats.argtypes = [vp, C.POINTER(VsgRenderAdjacencyStats)]
     _handle = L
     return L
 
@@ -425,6 +458,57 @@ class SegmentationRenderer(_capi.Handle):
         """vsg_render_last_boundary_stats of the last level_boundaries call, as a dict."""
         s = VsgRenderBoundaryStats()
         check(lib().vsg_render_last_boundary_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def level_adjacency(self, seg_bytes, level=0, connectedness=0, neighbourhood=ADJACENT_N4, nodes_out=None,
+                        edges_out=None):
+        """The region adjacency graph of hierarchy level `level`: one node per region (connectedness 0) or per
+        connected component of its regions (N4 or N8), and one directed edge per pair of nodes that touch:
+        (nodes, edges).  nodes: a LEVEL_NODE_DTYPE array, record k belonging to record k of level_regions
+        (level_components), with the node's slice of `edges` and its perimeter split into sides on the frame
+        edge, next to uncovered pixels and next to other groups; edges: a LEVEL_EDGE_DTYPE array, grouped by
+        node, within a node by ascending neighbour, with the shared pixel sides and, for
+        neighbourhood=ADJACENT_N8, the diagonal contacts.  Without outputs the counts are asked for first
+        and both arrays are allocated exactly.  nodes_out / edges_out: buffers to fill instead, both numpy
+        (a LEVEL_NODE_DTYPE and a LEVEL_EDGE_DTYPE array) or both torch CUDA tensors ((capacity, 7) int32 and
+        (capacity, 4) int32); the filled parts of them are returned."""
+        seg_bytes = bytes(seg_bytes)
+        nn, ne = C.c_size_t(), C.c_size_t()
+        if (nodes_out is None) != (edges_out is None):
+            raise ValueError("pass both outputs or neither")
+        if nodes_out is None:
+            check(lib().vsg_render_level_adjacency(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                   int(neighbourhood), None, 0, C.byref(nn), None, 0, C.byref(ne),
+                                                   VSG_MEM_HOST))
+            nodes_out = np.empty(nn.value, LEVEL_NODE_DTYPE)
+            edges_out = np.empty(ne.value, LEVEL_EDGE_DTYPE)
+            if nn.value == 0:
+                return nodes_out, edges_out
+        if _capi.is_torch(nodes_out) != _capi.is_torch(edges_out):
+            raise ValueError("both outputs have to be numpy arrays or both torch tensors")
+        if _capi.is_torch(nodes_out):
+            if nodes_out.dim() != 2 or nodes_out.shape[1] != LEVEL_NODE_WORDS or str(nodes_out.dtype) != "torch.int32":
+                raise ValueError("nodes_out has to be (capacity, %d) int32" % LEVEL_NODE_WORDS)
+            if edges_out.dim() != 2 or edges_out.shape[1] != LEVEL_EDGE_WORDS or str(edges_out.dtype) != "torch.int32":
+                raise ValueError("edges_out has to be (capacity, %d) int32" % LEVEL_EDGE_WORDS)
+        else:
+            if nodes_out.dtype != LEVEL_NODE_DTYPE or nodes_out.ndim != 1:
+                raise ValueError("nodes_out has to be a one-dimensional LEVEL_NODE_DTYPE array")
+            if edges_out.dtype != LEVEL_EDGE_DTYPE or edges_out.ndim != 1:
+                raise ValueError("edges_out has to be a one-dimensional LEVEL_EDGE_DTYPE array")
+        pn, mem = _capi.contiguous_ptr(nodes_out)
+        pe, mem_e = _capi.contiguous_ptr(edges_out)
+        if mem != mem_e:
+            raise ValueError("both outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_adjacency(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                               int(neighbourhood), pn, nodes_out.shape[0], C.byref(nn), pe,
+                                               edges_out.shape[0], C.byref(ne), mem))
+        return nodes_out[:nn.value], edges_out[:ne.value]
+
+    def last_adjacency_stats(self):
+        """vsg_render_last_adjacency_stats of the last level_adjacency call, as a dict."""
+        s = VsgRenderAdjacencyStats()
+        check(lib().vsg_render_last_adjacency_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def last_vector_stats(self):

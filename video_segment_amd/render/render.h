@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip),
+// boundaries.hip, adjacency.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -199,6 +199,56 @@ void LaunchBoundTable(const unsigned long long* keys_sorted, const uint32_t* ran
 // capacity_records or a flag is up.
 void LaunchBoundCopy(const int32_t* records, const int32_t* points, uint32_t n, uint32_t capacity_records,
                      int32_t* records_out, int32_t* points_out, const BoundStatus* status, hipStream_t stream);
+
+// ---- level adjacency (adjacency.hip): the region adjacency graph of an int32 plane -------------------
+
+constexpr int kLevelNodeWords = 7;   // vsg_render_level_node as int32 words
+constexpr int kLevelEdgeWords = 4;   // vsg_render_level_edge as int32 words
+
+enum AdjFlag {
+  ADJ_FLAG_OVERFLOW = 1,   // a key had no slot: the emit pass found more keys than the count pass
+  ADJ_FLAG_RANGE = 2,      // a sorted key, a rank, a node or an edge was out of range
+};
+
+// Written by the adjacency kernels; read by the host after the count pass and at the end of a call.
+struct AdjStatus {
+  unsigned long long keys;   // keys the count pass found
+  uint32_t emitted;          // slots the emit pass reserved
+  uint32_t nodes;            // distinct groups among the keys
+  uint32_t edges;            // distinct (group, neighbouring group) among the keys
+  uint32_t largest;          // most edges of one node
+  uint32_t flags, pad;
+};
+
+// The adjacency keys of the H x W plane (row pitch W; negative: no group): for every covered position
+// one key group << (group_bits + 2) | other << 1 | kind per pixel side that does not lead to its own
+// group (kind 0; other = the group across, 1 << group_bits for the frame edge, 1 << group_bits | 1 for
+// an uncovered pixel) and, with `diagonal`, one per diagonal neighbour of another group (kind 1).  Every
+// group is below 1 << group_bits, group_bits in [1, 31].  emit false: status->keys += their number,
+// keys is not looked at.  emit true: the keys, in no particular order, status->emitted of them; a slot
+// at or beyond `capacity` is not written and raises ADJ_FLAG_OVERFLOW.
+void LaunchAdjClassify(const int32_t* plane, int width, int height, int group_bits, bool diagonal, bool emit,
+                       uint32_t capacity, unsigned long long* keys, AdjStatus* status, hipStream_t stream);
+// Work space of AdjSort and AdjRank (the larger of the two).
+size_t AdjTempBytes(int64_t n, int end_bit);
+// The library radix sort on bits [0, end_bit) of the keys; all of a key is below 2 * group_bits + 2.
+hipError_t AdjSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
+                   int64_t n, int end_bit, hipStream_t stream);
+// heads[i] = (distinct groups) << 32 | (distinct (group, other) with other a group) among sorted keys
+// [0, i]: LevelRank's scan with two counters in one sum.
+hipError_t AdjRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, int group_bits,
+                   unsigned long long* heads, int64_t n, hipStream_t stream);
+// n sorted keys with AdjRank's heads -> the nodes and the edges; status->nodes, ->edges and ->largest.
+// `nodes` (capacity_nodes entries) and `edges` (capacity_edges entries) have to be cleared to zero
+// before.  comp_table: null (id = group, component = -1, neighbour = the rank of the neighbour's id), or
+// the table of LaunchCompTable the groups index (neighbour = the group across).
+void LaunchAdjTable(const unsigned long long* keys_sorted, const unsigned long long* heads, uint32_t n, int group_bits,
+                    uint32_t max_group, uint32_t capacity_nodes, uint32_t capacity_edges, const int32_t* comp_table,
+                    int32_t* nodes, int32_t* edges, AdjStatus* status, hipStream_t stream);
+// Copies status->nodes nodes and status->edges edges, or nothing when either list is longer than its
+// capacity or a flag is up.
+void LaunchAdjCopy(const int32_t* nodes, const int32_t* edges, uint32_t capacity_nodes, uint32_t capacity_edges,
+                   int32_t* nodes_out, int32_t* edges_out, const AdjStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -17,6 +17,7 @@
 
 namespace {
 
+using vsg_render_impl::AdjStatus;
 using vsg_render_impl::BoundStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
@@ -30,6 +31,7 @@ enum LevelStage { LVL_RUNS = 0, LVL_SORT, LVL_TABLE, LVL_MOMENTS, LVL_COUNT };
 // CMP_WAIT: the stream idles while the host reads the number of components; reported with no stage
 enum CompStage { CMP_LINK = 0, CMP_ORDER, CMP_MOMENTS, CMP_LABEL, CMP_WAIT, CMP_COUNT };
 enum BoundStage { BND_COUNT = 0, BND_EMIT, BND_SORT, BND_TABLE, BND_STAGES };
+enum AdjStage { ADJ_COUNT = 0, ADJ_EMIT, ADJ_SORT, ADJ_TABLE, ADJ_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -328,7 +330,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -355,12 +357,16 @@ struct vsg_render {
   // level boundaries: unsorted and sorted keys; their groups' ranks; the points; the records; the
   // status words and the pinned block the status and host outputs come back through
   Block d_bound_keys, d_bound_rank, d_bound_points, d_bound_records, d_bound_status, h_bound;
+  // level adjacency: unsorted and sorted keys; their node and edge heads' counts; the nodes; the edges;
+  // the status words and the pinned block the status and host outputs come back through
+  Block d_adj_keys, d_adj_heads, d_adj_nodes, d_adj_edges, d_adj_status, h_adj;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
   vsg_render_level_stats lstats;
   vsg_render_component_stats cstats;
   vsg_render_boundary_stats bstats;
+  vsg_render_adjacency_stats astats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -934,6 +940,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->bclock.Create(BND_STAGES + 1);
     h->h_bound.pinned = true;
     std::memset(&h->bstats, 0, sizeof(h->bstats));
+    h->aclock.Create(ADJ_STAGES + 1);
+    h->h_adj.pinned = true;
+    std::memset(&h->astats, 0, sizeof(h->astats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -1373,6 +1382,211 @@ int vsg_render_last_boundary_stats(vsg_render* h, vsg_render_boundary_stats* s) 
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->bstats;
+  });
+}
+
+int vsg_render_level_adjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                               int neighbourhood, vsg_render_level_node* nodes, size_t capacity_nodes,
+                               size_t* num_nodes, vsg_render_level_edge* edges, size_t capacity_edges,
+                               size_t* num_edges, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_level_node) == kLevelNodeWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_level_edge) == kLevelEdgeWords * sizeof(int32_t), "moved as int32 words");
+    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    if (neighbourhood != VSG_RENDER_ADJACENT_N4 && neighbourhood != VSG_RENDER_ADJACENT_N8) {
+      Throw(VSG_ERR_INVALID, "neighbourhood is neither VSG_RENDER_ADJACENT_N4 nor VSG_RENDER_ADJACENT_N8");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_nodes || !num_edges) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_nodes = *num_edges = 0;
+    CheckMem(mem_out, "outputs");
+    const bool count_only = !nodes && !edges && capacity_nodes == 0 && capacity_edges == 0;
+    const bool diagonal = neighbourhood == VSG_RENDER_ADJACENT_N8;
+    const int W = h->W, H = h->H;
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+    DeviceGuard guard(h->device);
+    vsg_render_adjacency_stats& as = h->astats;
+    std::memset(&as, 0, sizeof(as));
+
+    // ---- the plane: the level's ids, or the indices of its regions' components ----
+    const int32_t* plane = nullptr;
+    const int32_t* comp_table = nullptr;
+    uint32_t max_group = 0;
+    uint64_t groups_bound = 0;   // no more groups than this
+    bool vector = false;
+    if (connectedness == 0) {
+      int32_t max_id = 0;
+      vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
+      plane = h->d_ids.As<int32_t>();
+      max_group = (uint32_t)max_id;
+      groups_bound = (uint64_t)h->stats.distinct_ids;
+      as.launches = h->stats.launches;
+    } else {
+      size_t n_components = 0, n_intervals = 0;
+      LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
+                      nullptr, VSG_MEM_DEVICE, true);
+      plane = h->d_labels.As<int32_t>();
+      comp_table = h->d_comp_table.As<int32_t>();
+      max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
+      groups_bound = n_components;
+      const vsg_render_component_stats& cs = h->cstats;
+      as.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                    cs.label_us;
+      as.launches = h->stats.launches;
+    }
+    int group_bits = 1;
+    while (group_bits < 31 && (max_group >> group_bits)) ++group_bits;
+
+    // ---- count: the number of keys sizes everything below ----
+    h->d_adj_status.Reserve(sizeof(AdjStatus), &h->allocations);
+    h->h_adj.Reserve(2 * sizeof(AdjStatus), &h->allocations);
+    AdjStatus* status = h->d_adj_status.As<AdjStatus>();
+    AdjStatus* seen = h->h_adj.As<AdjStatus>();   // [0] after the count, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(AdjStatus));
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(AdjStatus), h->stream));
+    h->aclock.Begin(h->stream);
+    LaunchAdjClassify(plane, W, H, group_bits, diagonal, false, 0, nullptr, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->aclock.Mark(ADJ_COUNT);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
+    int launches = 3;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[ADJ_STAGES];
+      h->aclock.Read(us, ADJ_STAGES);
+      as.count_us = us[ADJ_COUNT];
+    }
+    if (connectedness == 0) {
+      float us[STAGE_COUNT];
+      h->clock.Read(us, STAGE_COUNT);
+      h->stats.clear_us = us[STAGE_CLEAR];
+      h->stats.fill_us = us[STAGE_FILL];
+      as.plane_us = us[STAGE_CLEAR] + us[STAGE_FILL];
+      if (vector) h->CheckVector();
+    }
+    auto finish = [&] {
+      as.launches += launches;
+      h->stats.launches += launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    if (seen[0].keys > 0x7fffffffull) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the level has more than 2^31 - 1 bordering sides and diagonal contacts");
+    }
+    const uint32_t n = (uint32_t)seen[0].keys;
+    as.sides = as.keys = n;
+    if (n == 0) return finish();   // no covered pixel: both lists are empty
+
+    // ---- emit, sort, table ----
+    const uint32_t cap_nodes = (uint32_t)std::min<uint64_t>(groups_bound, n);   // every group has a key
+    if (cap_nodes == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
+    const uint32_t cap_edges = n;                                               // every edge has a key
+    const int end_bit = 2 * group_bits + 2;
+    const size_t temp_bytes = std::max<size_t>(AdjTempBytes(n, end_bit), 16);
+    const size_t node_bytes = (size_t)cap_nodes * sizeof(vsg_render_level_node);
+    const size_t edge_bytes = (size_t)cap_edges * sizeof(vsg_render_level_edge);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    h->d_adj_keys.Reserve((size_t)n * 2 * sizeof(unsigned long long), &h->allocations);
+    h->d_adj_heads.Reserve((size_t)n * sizeof(unsigned long long), &h->allocations);
+    h->d_adj_nodes.Reserve(node_bytes, &h->allocations);
+    h->d_adj_edges.Reserve(edge_bytes, &h->allocations);
+    unsigned long long* keys = h->d_adj_keys.As<unsigned long long>();
+    unsigned long long* keys_sorted = keys + n;
+    unsigned long long* heads = h->d_adj_heads.As<unsigned long long>();
+    int32_t* d_nodes = h->d_adj_nodes.As<int32_t>();
+    int32_t* d_edges = h->d_adj_edges.As<int32_t>();
+    h->aclock.Begin(h->stream);
+    LaunchAdjClassify(plane, W, H, group_bits, diagonal, true, n, keys, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->aclock.Mark(ADJ_EMIT);
+    VSG_HIP(AdjSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
+    h->aclock.Mark(ADJ_SORT);
+    VSG_HIP(hipMemsetAsync(d_nodes, 0, node_bytes, h->stream));   // the counts are summed into them
+    VSG_HIP(hipMemsetAsync(d_edges, 0, edge_bytes, h->stream));
+    VSG_HIP(AdjRank(h->d_sort_temp.p, temp_bytes, keys_sorted, group_bits, heads, n, h->stream));
+    LaunchAdjTable(keys_sorted, heads, n, group_bits, max_group, cap_nodes, cap_edges, comp_table, d_nodes, d_edges,
+                   status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->aclock.Mark(ADJ_TABLE);
+    // emit, the sort and the scan counted as one each, two clears, table, finish, resolve
+    launches += 7 + (comp_table ? 0 : 1);
+    const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && nodes && edges;
+    if (to_device) {
+      // the lengths of both lists are on the device: the copy decides there whether they fit
+      LaunchAdjCopy(d_nodes, d_edges, (uint32_t)std::min<size_t>(capacity_nodes, cap_nodes),
+                    (uint32_t)std::min<size_t>(capacity_edges, cap_edges), reinterpret_cast<int32_t*>(nodes),
+                    reinterpret_cast<int32_t*>(edges), status, h->stream);
+      VSG_HIP(hipGetLastError());
+      ++launches;
+    }
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[ADJ_STAGES];
+      h->aclock.Read(us, ADJ_STAGES);
+      as.emit_us = us[ADJ_EMIT];
+      as.sort_us = us[ADJ_SORT];
+      as.table_us = us[ADJ_TABLE];
+    }
+    if ((seen[1].flags & ADJ_FLAG_OVERFLOW) || seen[1].emitted != n) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "the emit pass found other adjacency keys than the count pass");
+    }
+    if ((seen[1].flags & ADJ_FLAG_RANGE) || seen[1].nodes == 0 || seen[1].nodes > cap_nodes ||
+        seen[1].edges > cap_edges || (comp_table && seen[1].nodes != groups_bound)) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "a sorted adjacency key, a node or an edge is out of range");
+    }
+    const size_t n_nodes = seen[1].nodes, n_edges = seen[1].edges;
+    *num_nodes = n_nodes;
+    *num_edges = n_edges;
+    as.nodes = (int64_t)n_nodes;
+    as.edges = (int64_t)n_edges;
+    as.largest_node_edges = seen[1].largest;
+    if (count_only) return finish();
+    if (n_nodes > capacity_nodes || n_edges > capacity_edges) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_nodes) + " nodes and " + std::to_string(n_edges) +
+                                 " edges, the capacities are " + std::to_string(capacity_nodes) + " and " +
+                                 std::to_string(capacity_edges));
+    }
+    if (!nodes || (n_edges && !edges)) {
+      finish();
+      Throw(VSG_ERR_INVALID, "an output is null");
+    }
+    if (mem_out == VSG_MEM_HOST) {
+      // through the pinned block, now that the lengths are known
+      const size_t nb = n_nodes * sizeof(vsg_render_level_node), eb = n_edges * sizeof(vsg_render_level_edge);
+      h->h_adj.Reserve(2 * sizeof(AdjStatus) + nb + eb, &h->allocations);
+      char* stage = reinterpret_cast<char*>(h->h_adj.As<AdjStatus>() + 2);
+      VSG_HIP(hipMemcpyAsync(stage, d_nodes, nb, hipMemcpyDeviceToHost, h->stream));
+      ++launches;
+      if (eb) {
+        VSG_HIP(hipMemcpyAsync(stage + nb, d_edges, eb, hipMemcpyDeviceToHost, h->stream));
+        ++launches;
+      }
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      std::memcpy(nodes, stage, nb);
+      if (eb) std::memcpy(edges, stage + nb, eb);
+    } else if (!to_device) {
+      // edges was null with no edge to deliver: the copy kernel was not launched
+      VSG_HIP(hipMemcpyAsync(nodes, d_nodes, n_nodes * sizeof(vsg_render_level_node), hipMemcpyDeviceToDevice,
+                             h->stream));
+      ++launches;
+      VSG_HIP(hipStreamSynchronize(h->stream));
+    }
+    finish();
+  });
+}
+
+int vsg_render_last_adjacency_stats(vsg_render* h, vsg_render_adjacency_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->astats;
   });
 }
 
