@@ -167,7 +167,10 @@ int vsg_vectorize_id_image(const int32_t* ids, int width, int height, const uint
                            size_t* len);
 
 /* ---- seam 2: DenseSegmentation ------------------------------------------------------------ */
-/* DenseSegmentation::DenseSegmentation(options, frame_width, frame_height), cpp:50-106. */
+/* DenseSegmentation::DenseSegmentation(options, frame_width, frame_height), cpp:50-106.
+ * Frame sizes: width in [2, 10224], height in [1, 65535]; anything else fails here with
+ * VSG_ERR_INVALID.  (10224 px is the widest row whose four i32 copies -- 16 bytes per pixel -- fit
+ * the 160 KiB of LDS of one gfx950 workgroup in the read-out's N4 sweep.) */
 int vsg_stream_create(const vsg_options* o, int width, int height, vsg_stream** out);
 void vsg_stream_destroy(vsg_stream* s);
 /* int DenseSegmentation::ProcessFrame(flush, features, flow, results), cpp:108-162.
@@ -294,7 +297,9 @@ int vsg_bgr_to_lab(const uint8_t* bgr, size_t stride, int width, int height, uin
 
 /* ---- seam 3: DenseSegGraphInterface ------------------------------------------------------- */
 /* CreateDenseSegGraph(frame_width, frame_height, max_frames) + InitializeGraph(),
- * dense_seg_graph_interface.h:46-48,112; l1 selects DistanceColorL1 (dense_segmentation.cpp:247-251). */
+ * dense_seg_graph_interface.h:46-48,112; l1 selects DistanceColorL1 (dense_segmentation.cpp:247-251).
+ * Frame sizes as for vsg_stream_create: width in [2, 10224], height in [1, 65535], else
+ * VSG_ERR_INVALID; max_frames in [1, 4095]. */
 int vsg_graph_create(int width, int height, int max_frames, int l1, int device, vsg_graph** out);
 void vsg_graph_destroy(vsg_graph* g);
 /* PreprocessFeatures + AddNodesAndSpatialEdges[Constrained] on a BGR24 frame

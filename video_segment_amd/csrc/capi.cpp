@@ -256,13 +256,22 @@ int vsg_vectorize_id_image(const int32_t* ids, int width, int height, const uint
   });
 }
 
+// The frame sizes a stream or a graph is created for (include/vsg.h).  Checked before anything is
+// allocated or launched: a wider row does not fit the LDS of the read-out's N4 sweep.
+static void RequireFrameSize(int width, int height) {
+  VSG_REQUIRE(width >= 2 && width <= vsg::kMaxFrameWidth && height >= 1 && height <= vsg::kMaxFrameHeight,
+              VSG_ERR_INVALID,
+              "unsupported frame size " + std::to_string(width) + "x" + std::to_string(height) +
+                  ": width has to be in [2, " + std::to_string(vsg::kMaxFrameWidth) +
+                  "], height in [1, " + std::to_string(vsg::kMaxFrameHeight) + "]");
+}
+
 // ---- stream ------------------------------------------------------------------------------
 int vsg_stream_create(const vsg_options* o, int width, int height, vsg_stream** out) {
   return Guard([&] {
     VSG_REQUIRE(o && out, VSG_ERR_INVALID, "null argument");
+    RequireFrameSize(width, height);
     RequireDevice(o->device);
-    VSG_REQUIRE(width >= 2 && height >= 1 && width <= 65535 && height <= 65535, VSG_ERR_INVALID,
-                "unsupported frame size");
     std::unique_ptr<vsg_stream> s(new vsg_stream);
     s->device = ResolveDevice(o->device);
     DeviceGuard dg(s->device);
@@ -710,9 +719,8 @@ int vsg_debug_sort_pairs(const uint32_t* keys, const uint32_t* values, int n, in
 int vsg_graph_create(int width, int height, int max_frames, int l1, int device, vsg_graph** out) {
   return Guard([&] {
     VSG_REQUIRE(out, VSG_ERR_INVALID, "null argument");
+    RequireFrameSize(width, height);
     RequireDevice(device);
-    VSG_REQUIRE(width >= 2 && height >= 1 && width <= 65535 && height <= 65535, VSG_ERR_INVALID,
-                "unsupported frame size");
     std::unique_ptr<vsg_graph> g(new vsg_graph);
     g->device = ResolveDevice(device);
     DeviceGuard dg(g->device);

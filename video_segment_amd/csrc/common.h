@@ -157,6 +157,13 @@ constexpr int kNumBuckets = 2048;          // segmentation_graph.h ctor: 2K buck
 constexpr int kBucketSlots = kNumBuckets + 2;   // 0..2047 real, 2048 virtual, 2049 end sentinel
 constexpr uint16_t kInvalidKey = 0x0FFF;   // sorts after every real bucket (12 sort bits)
 
+// Widest and tallest accepted frame.  The N4 sweep of the read-out (k_enforce_n4) keeps four i32
+// rows of a slice in LDS: 16 W bytes next to the 256 bytes of its workgroup reduction, in the
+// 160 KiB a gfx950 workgroup can have -- (163840 - 256) / 16 = 10224.  The height is bounded by the
+// 16 bits an interval's row has in IntervalArrays::ty.
+constexpr int kMaxFrameWidth = 10224;
+constexpr int kMaxFrameHeight = 65535;
+
 }  // namespace vsg
 
 #endif  // VSG_COMMON_H_

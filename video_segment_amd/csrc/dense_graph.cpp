@@ -45,7 +45,7 @@ void H2D(T* dst, const T* src, size_t n, hipStream_t s) {
 DenseGraphHip::DenseGraphHip(int W, int H, int max_frames, bool l1, hipStream_t stream)
     : W_(W), H_(H), capacity_frames_(max_frames), max_frames_(max_frames), l1_(l1),
       stream_(stream), wh_((size_t)W * H) {
-  VSG_REQUIRE(W >= 2 && H >= 1 && W <= 65535 && H <= 65535, -1, "unsupported frame size");
+  VSG_REQUIRE(W >= 2 && H >= 1 && W <= kMaxFrameWidth && H <= kMaxFrameHeight, -1, "unsupported frame size");
   VSG_REQUIRE(max_frames >= 1 && max_frames < 4096, -1, "unsupported number of frames");
   const size_t N = wh_ * (size_t)max_frames;
   VSG_REQUIRE(N * 9 < (size_t)0xFFFFFFFFu, -1, "graph too large for 32-bit edge positions");

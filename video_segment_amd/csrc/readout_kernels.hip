@@ -6,6 +6,8 @@
 //   EnforceN4Connectivity                    dense_segmentation_graph.h:1303-1337
 //   run-length rasterisation                 dense_segmentation_graph.h:533-559
 //   DetermineNeighborIdsImpl (edge walk)     segmentation_graph.h:466-496
+#include <atomic>
+
 #include "device_graph.h"
 
 namespace vsg {
@@ -47,6 +49,8 @@ void LaunchFlatten(NodeArrays nodes, size_t n, int32_t* label_uf, hipStream_t s)
 // on the rows below a rewritten one; everything else it skips without touching the image (the
 // sweep over all 1079 row pairs of a 1080p slice was 2.2 ms per chunk, one workgroup per slice).
 constexpr int kN4Threads = 1024;
+constexpr int kMaxAttrDevices = 64;
+constexpr size_t kLdsPerWorkgroup = 160 * 1024;   // gfx950
 
 __global__ __launch_bounds__(256) void k_n4_row_flags(const int32_t* __restrict__ label_img, int W, int H,
                                                        const int32_t* __restrict__ frames,
@@ -137,6 +141,22 @@ __global__ __launch_bounds__(kN4Threads) void k_enforce_n4(int32_t* __restrict__
 void LaunchEnforceN4(int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
                      int32_t* row_flags /* [num_frames * H], zeroed */, int32_t* adjust, hipStream_t s) {
   if (num_frames <= 0 || H < 2) return;
+  VSG_REQUIRE(W <= kMaxFrameWidth, -1, "frame too wide for the N4 sweep");
+  // Rows wider than 4096 px need more than the 64 KiB of dynamic LDS a kernel gets unasked.  The
+  // attribute belongs to the (function, device) pair, as in LaunchBilateral.
+  static std::atomic<bool> attr_set[kMaxAttrDevices];
+  int dev = 0;
+  VSG_HIP(hipGetDevice(&dev));
+  if (dev < 0 || dev >= kMaxAttrDevices || !attr_set[dev].load(std::memory_order_acquire)) {
+    hipFuncAttributes fa;
+    VSG_HIP(hipFuncGetAttributes(&fa, reinterpret_cast<const void*>(k_enforce_n4)));
+    const size_t widest = (size_t)4 * kMaxFrameWidth * sizeof(int32_t);
+    VSG_REQUIRE(fa.sharedSizeBytes + widest <= kLdsPerWorkgroup, -4,
+                "k_enforce_n4: static LDS leaves no room for a row of kMaxFrameWidth");
+    VSG_HIP(hipFuncSetAttribute(reinterpret_cast<const void*>(k_enforce_n4),
+                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)widest));
+    if (dev >= 0 && dev < kMaxAttrDevices) attr_set[dev].store(true, std::memory_order_release);
+  }
   hipLaunchKernelGGL(k_n4_row_flags, dim3(H - 1, num_frames), dim3(256), 0, s, label_img, W, H, frames_dev,
                      row_flags);
   hipLaunchKernelGGL(k_enforce_n4, dim3(num_frames), dim3(kN4Threads),
