@@ -43,7 +43,10 @@
  * pixels of a rasterization in row-major order.  Contour tracing and vectorisation at a level
  * (BoundaryComputation, segmentation/boundary.cpp) are not offered.  Which regions or components of a
  * level touch in a frame, and along how many pixel sides, is what vsg_render_level_adjacency returns;
- * the reference has no per-frame counterpart (CompoundRegion.neighbor_id covers a chunk in 3-D).
+ * the reference has no per-frame counterpart (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
+ * against ground truth and correspondence between frames are not offered either, but the table they are
+ * all functions of is: vsg_render_level_overlap relates a level to a ground-truth label image or to the id
+ * image of another frame.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -414,6 +417,94 @@ typedef struct vsg_render_adjacency_stats {
   int launches;
 } vsg_render_adjacency_stats;
 int vsg_render_last_adjacency_stats(vsg_render* h, vsg_render_adjacency_stats* s);
+
+/* One row of the overlap table, as vsg_render_level_overlap returns it: a group of the level. */
+typedef struct vsg_render_overlap_row {    /* 32 bytes, no padding */
+  int32_t id;            /* region id at `level` */
+  int32_t component;     /* index among its region's components; -1 with connectedness 0 */
+  int32_t first_pair, num_pairs;
+  int32_t area;          /* pixels of the group */
+  int32_t unlabelled;    /* of those, pixels where the other plane is negative */
+  int32_t best_label;    /* label with the largest count; ties: the smallest label; -1 when num_pairs == 0 */
+  int32_t best_count;    /* its count; 0 when num_pairs == 0 */
+} vsg_render_overlap_row;
+
+/* One column of the overlap table: a label of the other plane. */
+typedef struct vsg_render_overlap_col {    /* 24 bytes, no padding */
+  int32_t label;         /* a non-negative value of the other plane */
+  int32_t area;          /* pixels of the frame with that label */
+  int32_t uncovered;     /* of those, pixels where P is -1 */
+  int32_t num_pairs;     /* groups it overlaps */
+  int32_t best_row;      /* index in the row list of the group with the largest count; ties: the smallest
+                            index; -1 when num_pairs == 0 */
+  int32_t best_count;
+} vsg_render_overlap_col;
+
+/* One non-empty cell of the overlap table. */
+typedef struct vsg_render_overlap_pair {   /* 16 bytes, no padding */
+  int32_t row, col;      /* indices into the two lists */
+  int32_t label;         /* cols[col].label */
+  int32_t count;         /* pixels with P = the row's group and other = label; > 0 */
+} vsg_render_overlap_pair;
+
+/* The overlap (contingency) table of hierarchy level `level` and a plane of labels: for every (group of
+ * the level, label of the other plane) the number of pixels where both hold, with the marginals of either
+ * side.  Every score of a segmentation against ground truth (undersegmentation error, achievable
+ * segmentation accuracy, the Rand-type scores) and the correspondence of a level between two frames are
+ * functions of it.  Computed on the device, in integers throughout.
+ *
+ * The planes.  P is the plane of vsg_render_level_boundaries: the id plane of vsg_render_id_image at
+ * `level` for connectedness 0, or the label image of vsg_render_level_components for
+ * VSG_RENDER_CONNECT_N4 / _N8 (that call is made internally: vsg_render_last_component_stats then
+ * describes it).  B is `other`: H rows of other_pitch int32 in mem_other memory, host or device,
+ * independent of mem_out; other_pitch 0 means W, and only the first W values of a row are read.  Every
+ * int32 is a legal value of B, and every negative value means "no label" (ground-truth void): no label
+ * value is refused.  B is read only; it may be memory that an earlier vsg_render_id_image or
+ * vsg_render_level_components of the same handle wrote.
+ *
+ * Rows.  One row per group of P, in the order of the sibling calls: record k belongs to record k of
+ * vsg_render_level_regions for connectedness 0, of vsg_render_level_components otherwise.  area is the
+ * pixels of the group, unlabelled those of them with B < 0, so area - unlabelled is the sum of the counts
+ * of its pairs.
+ *
+ * Cols.  One column per distinct non-negative value of B inside the frame, ascending; values covered by no
+ * group are included.  area - uncovered is the sum of the counts of its pairs.
+ *
+ * Pairs.  One pair per (group, label) with at least one common pixel, grouped by row in row order and
+ * within a row by ascending label, which is ascending col.
+ *
+ * Decode, hierarchy rules (the desc's own hierarchy replaces the kept one), level refusals, the
+ * non-negative ids and the handling of vector-only descs are those of vsg_render_level_regions.
+ * *num_rows, *num_cols and *num_pairs are always set on VSG_OK and when a capacity is too small; in that
+ * case the call fails with VSG_ERR_INVALID and no output is touched.  All three outputs NULL with all three
+ * capacities 0 asks for the counts only (VSG_OK; needs the device).  A null handle, a null count pointer, a
+ * null `other`, a mem_other that is not one of the two memory kinds, an other_pitch that is neither 0 nor
+ * >= W, or a connectedness other than 0, VSG_RENDER_CONNECT_N4 and VSG_RENDER_CONNECT_N8 is
+ * VSG_ERR_INVALID and touches no device; all but the pitch, which is compared with the handle's width, are
+ * answered before the handle is dereferenced.  A frame with no covered pixel returns zero rows and zero
+ * pairs, and still every column.  A B without a label returns zero cols and zero pairs, and still every
+ * row.  All three lists in mem_out memory. */
+int vsg_render_level_overlap(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                             const int32_t* other, size_t other_pitch, int mem_other,
+                             vsg_render_overlap_row* rows, size_t capacity_rows, size_t* num_rows,
+                             vsg_render_overlap_col* cols, size_t capacity_cols, size_t* num_cols,
+                             vsg_render_overlap_pair* pairs, size_t capacity_pairs, size_t* num_pairs,
+                             int mem_out);
+
+/* What the last vsg_render_level_overlap call of the handle did.  covered: pixels with P >= 0; labelled:
+ * pixels with B >= 0; both: the sum of all counts.  runs: what the radix sort saw, the maximal runs, per
+ * frame row, of constant (P, B) with at least one of the two non-negative; a run ends with its row.
+ * Device times are HIP events around the stages: making the plane (as in vsg_render_boundary_stats) and
+ * bringing a host B to the device; the count pass of k_overlap_runs with k_overlap_totals; its emit pass;
+ * the radix sort of the runs; everything after it (the scans, k_overlap_table, k_overlap_pairs,
+ * k_overlap_rows, the sort of the distinct keys by label, k_overlap_col_heads, k_overlap_cols).  The last
+ * three are not run, and rows, cols, pairs and largest_row_pairs are 0, when there is no run. */
+typedef struct vsg_render_overlap_stats {
+  int64_t covered, labelled, both, runs, rows, cols, pairs, largest_row_pairs;
+  float plane_us, count_us, emit_us, sort_us, table_us;
+  int launches;
+} vsg_render_overlap_stats;
+int vsg_render_last_overlap_stats(vsg_render* h, vsg_render_overlap_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

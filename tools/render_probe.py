@@ -51,6 +51,16 @@ only (N4) and with diagonal contacts (N8).  Per call the five stage times of vsg
 launches, sides, keys, nodes, edges and the largest degree are recorded; in the same run
 vsg_render_level_boundaries (inner, same connectedness, outputs in device memory) on the same desc and
 handle is timed: a point of comparison, nothing more.  No pass or fail threshold.
+
+    python tools/render_probe.py --level-overlap [--reps 30] [--out profiles/level_overlap.json]
+
+The overlap leg: the same descs at their lowest and top level asked for their overlap table
+(vsg_render_level_overlap, outputs in device memory) of the regions (connectedness 0) and of their N4
+components, with the same level's id image shifted right by 8 pixels, in device memory, as the other plane.
+Per call the five stage times of vsg_render_overlap_stats, launches, runs, rows, cols and pairs are recorded;
+in the same run vsg_render_level_adjacency (N4 sides, same connectedness, outputs in device memory) on the
+same desc and handle is timed: the yardstick, which makes the same plane, reads it twice and sorts.  No pass
+or fail threshold.
 """
 import argparse
 import json
@@ -85,12 +95,15 @@ def main():
                     help="the boundary leg instead (profiles/level_boundaries.json)")
     ap.add_argument("--level-adjacency", action="store_true",
                     help="the adjacency leg instead (profiles/level_adjacency.json)")
+    ap.add_argument("--level-overlap", action="store_true",
+                    help="the overlap leg instead (profiles/level_overlap.json)")
     args = ap.parse_args()
-    if ((args.level_regions or args.level_components or args.level_boundaries or args.level_adjacency)
-            and "--reps" not in sys.argv):
+    if ((args.level_regions or args.level_components or args.level_boundaries or args.level_adjacency
+         or args.level_overlap) and "--reps" not in sys.argv):
         args.reps = 30
     if args.out is None:
-        name = ("level_adjacency.json" if args.level_adjacency else
+        name = ("level_overlap.json" if args.level_overlap else
+                "level_adjacency.json" if args.level_adjacency else
                 "level_boundaries.json" if args.level_boundaries else
                 "level_components.json" if args.level_components else "level_regions.json" if args.level_regions
                 else "vector_raster.json" if args.vector else "render_kernels.json")
@@ -106,6 +119,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.level_overlap:
+        return overlap_leg(args, result, dev)
     if args.level_adjacency:
         return adjacency_leg(args, result, dev)
     if args.level_boundaries:
@@ -431,6 +446,55 @@ def adjacency_leg(args, result, dev):
                     with open(args.out, "w") as f:
                         json.dump(result, f, indent=1)
                         f.write("\n")
+        r.close()
+    print("wrote", args.out)
+
+
+def overlap_leg(args, result, dev):
+    import torch
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    shift = 8
+    for size, W, H, seg, height in level_descs(args):
+        r = vsg.SegmentationRenderer(W, H, has_video=False)
+        ids = torch.empty((H, W), dtype=torch.int32, device=dev)
+        for level in sorted({0, max(height - 1, 0)}):
+            r.id_image(seg, level, out=ids)
+            other = torch.full((H, W), -1, dtype=torch.int32, device=dev)
+            other[:, shift:] = ids[:, :W - shift]
+            for mode, connect in (("regions", 0), ("components_N4", render.N4)):
+                nn, ne = (len(a) for a in r.level_adjacency(seg, level, connect, render.ADJACENT_N4))
+                nodes = torch.empty((nn, render.LEVEL_NODE_WORDS), dtype=torch.int32, device=dev)
+                edges = torch.empty((ne, render.LEVEL_EDGE_WORDS), dtype=torch.int32, device=dev)
+                sizes = [len(a) for a in r.level_overlap(seg, level, other, connect)]
+                words = (render.OVERLAP_ROW_WORDS, render.OVERLAP_COL_WORDS, render.OVERLAP_PAIR_WORDS)
+                outs = [torch.empty((n, w), dtype=torch.int32, device=dev) for n, w in zip(sizes, words)]
+                stage_keys = ["plane_us", "count_us", "emit_us", "sort_us", "table_us"]
+                rows = {k: [] for k in stage_keys + ["call_ms", "level_adjacency_call_ms"]
+                        + ["level_adjacency_" + k for k in stage_keys]}
+                for it in range(args.warmup + args.reps):
+                    t0 = time.perf_counter()
+                    r.level_overlap(seg, level, other, connect, rows_out=outs[0], cols_out=outs[1], pairs_out=outs[2])
+                    st = dict(r.last_overlap_stats(), call_ms=(time.perf_counter() - t0) * 1e3)
+                    t0 = time.perf_counter()
+                    r.level_adjacency(seg, level, connect, render.ADJACENT_N4, nodes_out=nodes, edges_out=edges)
+                    st["level_adjacency_call_ms"] = (time.perf_counter() - t0) * 1e3
+                    ast = r.last_adjacency_stats()
+                    st.update({"level_adjacency_" + k: ast[k] for k in stage_keys})
+                    if it >= args.warmup:
+                        for k in rows:
+                            rows[k].append(st[k])
+                case = {"size": size, "level": level, "hierarchy_levels": height, "mode": mode, "shift": shift,
+                        "runs": st["runs"], "rows": st["rows"], "cols": st["cols"], "pairs": st["pairs"],
+                        "largest_row_pairs": st["largest_row_pairs"], "covered": st["covered"],
+                        "labelled": st["labelled"], "both": st["both"], "launches": st["launches"],
+                        "level_adjacency_keys": ast["keys"], "level_adjacency_launches": ast["launches"]}
+                case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+                result["cases"].append(case)
+                print(json.dumps(case), flush=True)
+                with open(args.out, "w") as f:
+                    json.dump(result, f, indent=1)
+                    f.write("\n")
         r.close()
     print("wrote", args.out)
 

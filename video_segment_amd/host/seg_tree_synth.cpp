@@ -31,6 +31,13 @@
 // frame and prints a line
 // level_adjacency_nodes=<sum> adjacency_edges=<sum> adjacency_fnv1a32=<hash of both lists' bytes, nodes first>.
 //
+//   --level_overlap <level> [--overlap_components [--components_n8]]
+// asks vsg_render_level_overlap, for every frame after the first, for the overlap table of that level's
+// regions, or of their connected components (N4, or N8), with the previous frame's id image at that level
+// (fetched with vsg_render_id_image into host memory) and prints a line
+// level_overlap_rows=<sum> overlap_cols=<sum> overlap_pairs=<sum> overlap_fnv1a32=<hash of the three lists'
+// bytes, rows, cols and pairs of every compared frame in that order>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -491,6 +498,84 @@ class LevelAdjacencySinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_overlap: the same for the overlap table of a level's regions, or of their connected components,
+// with the previous frame's id image at that level (vsg_render_level_overlap): rows, cols, pairs of every
+// frame after the first.
+class LevelOverlapSinkUnit : public VideoUnit {
+ public:
+  LevelOverlapSinkUnit(int level, int connectedness, int device)
+      : level_(level), connect_(connectedness), device_(device) {}
+  ~LevelOverlapSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    previous_.resize((size_t)s.frame_width() * s.frame_height());
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    if (have_previous_) {
+      size_t nr = 0, nc = 0, np = 0;
+      VF_CHECK(vsg_render_level_overlap(render_, seg, desc.wire.size(), level_, connect_, previous_.data(), 0,
+                                        VSG_MEM_HOST, nullptr, 0, &nr, nullptr, 0, &nc, nullptr, 0, &np,
+                                        VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+      rows_buf_.resize(nr);
+      cols_buf_.resize(nc);
+      pairs_buf_.resize(np);
+      if (nr || nc) {
+        VF_CHECK(vsg_render_level_overlap(render_, seg, desc.wire.size(), level_, connect_, previous_.data(), 0,
+                                          VSG_MEM_HOST, rows_buf_.data(), nr, &nr, cols_buf_.data(), nc, &nc,
+                                          pairs_buf_.data(), np, &np, VSG_MEM_HOST) == VSG_OK,
+                 vsg_render_last_error());
+      }
+      Hash(rows_buf_.data(), nr * sizeof(vsg_render_overlap_row));
+      Hash(cols_buf_.data(), nc * sizeof(vsg_render_overlap_col));
+      Hash(pairs_buf_.data(), np * sizeof(vsg_render_overlap_pair));
+      rows_ += (long)nr;
+      cols_ += (long)nc;
+      pairs_ += (long)np;
+    }
+    VF_CHECK(vsg_render_id_image(render_, seg, desc.wire.size(), level_, previous_.data(), VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    have_previous_ = true;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long rows() const { return rows_; }
+  long cols() const { return cols_; }
+  long pairs() const { return pairs_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  bool have_previous_ = false;
+  std::vector<int32_t> previous_;
+  std::vector<vsg_render_overlap_row> rows_buf_;
+  std::vector<vsg_render_overlap_col> cols_buf_;
+  std::vector<vsg_render_overlap_pair> pairs_buf_;
+  long rows_ = 0, cols_ = 0, pairs_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -594,6 +679,11 @@ struct Flags {
   // --adjacency_components
   int level_adjacency = -1;
   bool adjacency_n8 = false, adjacency_components = false;
+  // vsg_render_level_overlap at this level for every frame after the first, with the previous frame's id
+  // image at this level; < 0: off.  Of the regions, or of the components (N4, or N8 with --components_n8)
+  // with --overlap_components
+  int level_overlap = -1;
+  bool overlap_components = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -627,7 +717,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
-                                   "adjacency_components", "help"};
+                                   "adjacency_components", "overlap_components", "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -680,6 +770,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_adjacency") f->level_adjacency = atoi(v.c_str());
     else if (a == "adjacency_n8") f->adjacency_n8 = bv;
     else if (a == "adjacency_components") f->adjacency_components = bv;
+    else if (a == "level_overlap") f->level_overlap = atoi(v.c_str());
+    else if (a == "overlap_components") f->overlap_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -906,6 +998,15 @@ int main(int argc, char** argv) {
     adjacency_sink->AttachTo(input);
     input = adjacency_sink.get();
   }
+  std::unique_ptr<LevelOverlapSinkUnit> overlap_sink;
+  if (FLAGS.level_overlap >= 0) {
+    const int connectedness = !FLAGS.overlap_components ? 0
+                              : FLAGS.components_n8     ? VSG_RENDER_CONNECT_N8
+                                                        : VSG_RENDER_CONNECT_N4;
+    overlap_sink.reset(new LevelOverlapSinkUnit(FLAGS.level_overlap, connectedness, FLAGS.device));
+    overlap_sink->AttachTo(input);
+    input = overlap_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -964,6 +1065,10 @@ int main(int argc, char** argv) {
   if (adjacency_sink) {
     std::printf("level_adjacency_nodes=%ld adjacency_edges=%ld adjacency_fnv1a32=%08x\n", adjacency_sink->nodes(),
                 adjacency_sink->edges(), adjacency_sink->hash());
+  }
+  if (overlap_sink) {
+    std::printf("level_overlap_rows=%ld overlap_cols=%ld overlap_pairs=%ld overlap_fnv1a32=%08x\n",
+                overlap_sink->rows(), overlap_sink->cols(), overlap_sink->pairs(), overlap_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

@@ -82,6 +82,16 @@ class VsgRenderAdjacencyStats(_capi.Structure):
     ]
 
 
+class VsgRenderOverlapStats(_capi.Structure):
+    _fields_ = [
+        ("covered", C.c_int64), ("labelled", C.c_int64), ("both", C.c_int64), ("runs", C.c_int64),
+        ("rows", C.c_int64), ("cols", C.c_int64), ("pairs", C.c_int64), ("largest_row_pairs", C.c_int64),
+        ("plane_us", C.c_float), ("count_us", C.c_float), ("emit_us", C.c_float), ("sort_us", C.c_float),
+        ("table_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -133,6 +143,27 @@ LEVEL_EDGE_WORDS = 4
 ADJACENT_N4 = 1
 ADJACENT_N8 = 2
 
+# vsg_render_overlap_row: 32 bytes, no padding
+OVERLAP_ROW_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("first_pair", np.int32), ("num_pairs", np.int32),
+    ("area", np.int32), ("unlabelled", np.int32), ("best_label", np.int32), ("best_count", np.int32),
+])
+assert OVERLAP_ROW_DTYPE.itemsize == 32
+OVERLAP_ROW_WORDS = 8
+
+# vsg_render_overlap_col: 24 bytes, no padding
+OVERLAP_COL_DTYPE = np.dtype([
+    ("label", np.int32), ("area", np.int32), ("uncovered", np.int32), ("num_pairs", np.int32),
+    ("best_row", np.int32), ("best_count", np.int32),
+])
+assert OVERLAP_COL_DTYPE.itemsize == 24
+OVERLAP_COL_WORDS = 6
+
+# vsg_render_overlap_pair: 16 bytes, no padding
+OVERLAP_PAIR_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("label", np.int32), ("count", np.int32)])
+assert OVERLAP_PAIR_DTYPE.itemsize == 16
+OVERLAP_PAIR_WORDS = 4
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -147,6 +178,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_components", "vsg_render_last_component_stats",
     "vsg_render_level_boundaries", "vsg_render_last_boundary_stats",
     "vsg_render_level_adjacency", "vsg_render_last_adjacency_stats",
+    "vsg_render_level_overlap", "vsg_render_last_overlap_stats",
 ]
 
 
@@ -194,6 +226,10 @@ def lib():
     L.vsg_render_level_adjacency.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t,
                                              C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_adjacency_stats.argtypes = [vp, C.POINTER(VsgRenderAdjacencyStats)]
+    L.vsg_render_level_overlap.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int,
+                                           vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t,
+                                           C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_overlap_stats.argtypes = [vp, C.POINTER(VsgRenderOverlapStats)]
     _handle = L
     return L
 
@@ -511,6 +547,80 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_adjacency_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def _other_ptr(self, other):
+        """(pointer, row pitch in int32, mem kind) of the H x W int32 plane `other`: a numpy array or a torch
+        tensor whose rows are contiguous and may be further apart than W values."""
+        if tuple(other.shape) != (self.H, self.W) or str(other.dtype).replace("torch.", "") != "int32":
+            raise ValueError("other has to be %d x %d int32" % (self.H, self.W))
+        ptr, strides, mem = _capi._memory(other)
+        unit = 1 if _capi.is_torch(other) else 4        # torch strides count elements, numpy's bytes
+        if strides[1] != unit and self.W > 1:
+            raise ValueError("other: the values of a row have to be contiguous")
+        pitch = self.W
+        if self.H > 1:
+            if strides[0] % unit or strides[0] // unit < self.W:
+                raise ValueError("other: rows have to be at least W int32 apart")
+            pitch = strides[0] // unit
+        _capi._drain(other)
+        return C.c_void_p(ptr), pitch, mem
+
+    def level_overlap(self, seg_bytes, level=0, other=None, connectedness=0, rows_out=None, cols_out=None,
+                      pairs_out=None):
+        """The overlap (contingency) table of hierarchy level `level` and the label plane `other`: (rows, cols,
+        pairs).  other: an H x W int32 numpy array or torch CUDA tensor with contiguous rows (its row stride
+        becomes the pitch); a negative value is "no label".  rows: an OVERLAP_ROW_DTYPE array, record k
+        belonging to record k of level_regions (connectedness 0) or level_components (N4 or N8), with the
+        group's area, how much of it is unlabelled, its slice of `pairs` and the label it overlaps most;
+        cols: an OVERLAP_COL_DTYPE array, one per distinct label by ascending label, with the label's area,
+        how much of it no group covers and the row that overlaps it most; pairs: an OVERLAP_PAIR_DTYPE array,
+        one per (group, label) with a common pixel, grouped by row, within a row by ascending label.
+        Without outputs the counts are asked for first and the arrays are allocated exactly.  rows_out /
+        cols_out / pairs_out (all or none): buffers to fill instead, all numpy (arrays of the three dtypes) or
+        all torch CUDA tensors ((capacity, 8), (capacity, 6) and (capacity, 4) int32); the filled parts of
+        them are returned."""
+        if other is None:
+            raise ValueError("other is needed")
+        seg_bytes = bytes(seg_bytes)
+        po, pitch, mem_other = self._other_ptr(other)
+        nr, nc, npairs = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        outs = (rows_out, cols_out, pairs_out)
+        if any(o is None for o in outs) and not all(o is None for o in outs):
+            raise ValueError("pass all three outputs or none")
+        if rows_out is None:
+            check(lib().vsg_render_level_overlap(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                 po, pitch, mem_other, None, 0, C.byref(nr), None, 0, C.byref(nc),
+                                                 None, 0, C.byref(npairs), VSG_MEM_HOST))
+            rows_out = np.empty(nr.value, OVERLAP_ROW_DTYPE)
+            cols_out = np.empty(nc.value, OVERLAP_COL_DTYPE)
+            pairs_out = np.empty(npairs.value, OVERLAP_PAIR_DTYPE)
+            if nr.value == 0 and nc.value == 0:
+                return rows_out, cols_out, pairs_out
+        outs = (rows_out, cols_out, pairs_out)
+        if len({_capi.is_torch(o) for o in outs}) != 1:
+            raise ValueError("all outputs have to be numpy arrays or all torch tensors")
+        specs = (("rows_out", OVERLAP_ROW_DTYPE, OVERLAP_ROW_WORDS), ("cols_out", OVERLAP_COL_DTYPE, OVERLAP_COL_WORDS),
+                 ("pairs_out", OVERLAP_PAIR_DTYPE, OVERLAP_PAIR_WORDS))
+        for o, (name, dtype, words) in zip(outs, specs):
+            if _capi.is_torch(o):
+                if o.dim() != 2 or o.shape[1] != words or str(o.dtype) != "torch.int32":
+                    raise ValueError("%s has to be (capacity, %d) int32" % (name, words))
+            elif o.dtype != dtype or o.ndim != 1:
+                raise ValueError("%s has to be a one-dimensional array of its dtype" % name)
+        ptrs = [_capi.contiguous_ptr(o) for o in outs]
+        if len({mem for _, mem in ptrs}) != 1:
+            raise ValueError("all outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_overlap(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), po,
+                                             pitch, mem_other, ptrs[0][0], rows_out.shape[0], C.byref(nr),
+                                             ptrs[1][0], cols_out.shape[0], C.byref(nc), ptrs[2][0],
+                                             pairs_out.shape[0], C.byref(npairs), ptrs[0][1]))
+        return rows_out[:nr.value], cols_out[:nc.value], pairs_out[:npairs.value]
+
+    def last_overlap_stats(self):
+        """vsg_render_last_overlap_stats of the last level_overlap call, as a dict."""
+        s = VsgRenderOverlapStats()
+        check(lib().vsg_render_last_overlap_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""
         s = VsgRenderVectorStats()
@@ -522,3 +632,20 @@ class SegmentationRenderer(_capi.Handle):
         s = VsgRenderStats()
         check(lib().vsg_render_last_stats(self.h, C.byref(s)))
         return s.as_dict()
+
+
+def overlap_scores(rows, pairs):
+    """The two scores every evaluation of this algorithm reports, from the host arrays of level_overlap, with
+    N = the sum of pairs.count (the pixels both covered and labelled): a dict of the integers
+    n, asa_sum = the sum of rows.best_count and ue_sum = the sum over the pairs of
+    min(count, (row.area - row.unlabelled) - count), and the float64 quotients
+    asa (achievable segmentation accuracy) = asa_sum / n and
+    ue (undersegmentation error, Neubert-Protzel) = ue_sum / n; both None when n == 0.  Host numpy only."""
+    rows, pairs = np.asarray(rows), np.asarray(pairs)
+    count = pairs["count"].astype(np.int64)
+    n = int(count.sum())
+    asa_sum = int(rows["best_count"].astype(np.int64).sum())
+    inside = (rows["area"].astype(np.int64) - rows["unlabelled"])[pairs["row"]]
+    ue_sum = int(np.minimum(count, inside - count).sum())
+    return {"n": n, "asa_sum": asa_sum, "ue_sum": ue_sum,
+            "asa": asa_sum / n if n else None, "ue": ue_sum / n if n else None}

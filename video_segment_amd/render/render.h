@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip),
+// boundaries.hip, adjacency.hip, overlap.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -249,6 +249,77 @@ void LaunchAdjTable(const unsigned long long* keys_sorted, const unsigned long l
 // capacity or a flag is up.
 void LaunchAdjCopy(const int32_t* nodes, const int32_t* edges, uint32_t capacity_nodes, uint32_t capacity_edges,
                    int32_t* nodes_out, int32_t* edges_out, const AdjStatus* status, hipStream_t stream);
+
+// ---- level overlap (overlap.hip): the contingency table of an int32 plane and a plane of labels ------
+
+constexpr int kOverlapRowWords = 8;    // vsg_render_overlap_row as int32 words
+constexpr int kOverlapColWords = 6;    // vsg_render_overlap_col as int32 words
+constexpr int kOverlapPairWords = 4;   // vsg_render_overlap_pair as int32 words
+constexpr int kOverlapRowTotals = 5;   // words a frame row leaves for the count pass's totals
+
+enum OvlFlag {
+  OVL_FLAG_OVERFLOW = 1,   // a run had no slot: the emit pass found more runs than the count pass
+  OVL_FLAG_RANGE = 2,      // a sorted key, a rank, a row, a column or a pair was out of range
+};
+
+// Written by the overlap kernels; read by the host after the count pass and at the end of a call.
+struct OvlStatus {
+  uint32_t runs;        // runs the count pass found
+  uint32_t covered;     // pixels with P >= 0
+  uint32_t labelled;    // pixels with B >= 0
+  uint32_t both;        // pixels with both
+  uint32_t max_label;   // the largest value of B (0 without a label)
+  uint32_t emitted;     // slots the emit pass reserved
+  uint32_t distinct;    // distinct (group or none, label or none) among the runs
+  uint32_t rows, cols, pairs;
+  uint32_t largest;     // most pairs of one row
+  uint32_t flags;
+};
+
+// The runs of constant (P, B) of the two H x W planes (`plane`: row pitch W; `other`: row pitch
+// other_pitch; negative: none), a run ending with its frame row, those with both values negative left out.
+// emit false: status->runs = their number, ->covered, ->labelled and ->both = the pixels with P >= 0, with
+// B >= 0 and with both, ->max_label = the largest label, summed over row_totals (height x
+// kOverlapRowTotals words, every one written); keys and lengths are not looked at.  emit true:
+// keys[k] = code(P) << (label_bits + 1) | code(B) and lengths[k] of every run, in no particular order,
+// status->emitted of them; code(v) = v for v >= 0; "none" is 1 << group_bits for P and 1 << label_bits for
+// B, every group below the one and every label below the other, both bit counts in [1, 31].  A slot at or
+// beyond `capacity` is not written and raises OVL_FLAG_OVERFLOW.
+void LaunchOverlapRuns(const int32_t* plane, const int32_t* other, size_t other_pitch, int width, int height,
+                       int group_bits, int label_bits, bool emit, uint32_t capacity, unsigned long long* keys,
+                       uint32_t* lengths, uint32_t* row_totals, OvlStatus* status, hipStream_t stream);
+// Work space of OverlapRank and OverlapColRank (the larger); the sorts are LevelSort, see LevelTempBytes.
+size_t OverlapScanTempBytes(int64_t n);
+// Two scans over the n sorted runs: row_heads[i] = (distinct groups) << 32 | (distinct (group, label), both
+// real) and key_heads[i] = (distinct keys) << 32 | (sum of the lengths), each over [0, i].
+hipError_t OverlapRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted,
+                       const uint32_t* lengths_sorted, int group_bits, int label_bits, unsigned long long* row_heads,
+                       unsigned long long* key_heads, int64_t n, hipStream_t stream);
+// n sorted runs with OverlapRank's scans -> the list of distinct keys (key, start and rank: m, m + 1 and m
+// entries; m bounds their number), the rows (capacity_rows entries, cleared to zero before) and the pairs
+// (m entries) but for `col`, and the m (column key, index of the distinct key) operands of the column sort;
+// status->distinct, ->rows, ->pairs and ->largest.  comp_table: null (id = group, component = -1), or the
+// table of LaunchCompTable the groups index.
+void LaunchOverlapTable(const unsigned long long* keys_sorted, const uint32_t* lengths_sorted,
+                        const unsigned long long* row_heads, const unsigned long long* key_heads, uint32_t n,
+                        uint32_t m, int group_bits, int label_bits, uint32_t max_group, uint32_t capacity_rows,
+                        const int32_t* comp_table, unsigned long long* key, uint32_t* start, unsigned long long* rank,
+                        int32_t* rows, int32_t* pairs, unsigned long long* ckeys, uint32_t* cvals, OvlStatus* status,
+                        hipStream_t stream);
+// rank[j] = number of distinct labels among sorted column keys [0, j].
+hipError_t OverlapColRank(void* temp, size_t temp_bytes, const unsigned long long* ckeys_sorted, int group_bits,
+                          int label_bits, uint32_t* rank, int64_t m, hipStream_t stream);
+// m sorted column operands with their ranks -> the columns (m entries) and `col` of every pair;
+// status->cols.  `first` has m + 1 entries; start and rank are those of LaunchOverlapTable.
+void LaunchOverlapCols(const unsigned long long* ckeys_sorted, const uint32_t* cvals_sorted, const uint32_t* col_rank,
+                       const uint32_t* start, const unsigned long long* rank, uint32_t m, int group_bits,
+                       int label_bits, uint32_t* first, int32_t* cols, int32_t* pairs, OvlStatus* status,
+                       hipStream_t stream);
+// Copies status->rows rows, status->cols columns and status->pairs pairs, or nothing when a list is longer
+// than its capacity or a flag is up.
+void LaunchOverlapCopy(const int32_t* rows, const int32_t* cols, const int32_t* pairs, uint32_t capacity_rows,
+                       uint32_t capacity_cols, uint32_t capacity_pairs, int32_t* rows_out, int32_t* cols_out,
+                       int32_t* pairs_out, const OvlStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -22,6 +22,7 @@ using vsg_render_impl::BoundStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
+using vsg_render_impl::OvlStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
 
@@ -32,6 +33,7 @@ enum LevelStage { LVL_RUNS = 0, LVL_SORT, LVL_TABLE, LVL_MOMENTS, LVL_COUNT };
 enum CompStage { CMP_LINK = 0, CMP_ORDER, CMP_MOMENTS, CMP_LABEL, CMP_WAIT, CMP_COUNT };
 enum BoundStage { BND_COUNT = 0, BND_EMIT, BND_SORT, BND_TABLE, BND_STAGES };
 enum AdjStage { ADJ_COUNT = 0, ADJ_EMIT, ADJ_SORT, ADJ_TABLE, ADJ_STAGES };
+enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -330,7 +332,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -360,6 +362,14 @@ struct vsg_render {
   // level adjacency: unsorted and sorted keys; their node and edge heads' counts; the nodes; the edges;
   // the status words and the pinned block the status and host outputs come back through
   Block d_adj_keys, d_adj_heads, d_adj_nodes, d_adj_edges, d_adj_status, h_adj;
+  // level overlap: a host B on the device and the pinned block it goes through; the count pass's words of
+  // every frame row; unsorted and sorted runs
+  // (keys, lengths), the unsorted halves taken again for the column sort's operands; the two scans, taken
+  // again for the sorted column operands and their ranks; the distinct keys (key, rank, start) and the
+  // columns' first keys; rows, columns, pairs; the status words and the pinned block the status and host
+  // outputs come back through
+  Block d_other, h_other, d_ovl_totals, d_ovl_runs, d_ovl_heads, d_ovl_keys, d_ovl_rows, d_ovl_cols, d_ovl_pairs,
+      d_ovl_status, h_ovl;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
@@ -367,6 +377,7 @@ struct vsg_render {
   vsg_render_component_stats cstats;
   vsg_render_boundary_stats bstats;
   vsg_render_adjacency_stats astats;
+  vsg_render_overlap_stats ostats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -943,6 +954,10 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->aclock.Create(ADJ_STAGES + 1);
     h->h_adj.pinned = true;
     std::memset(&h->astats, 0, sizeof(h->astats));
+    h->oclock.Create(OVL_STAGES + 1);
+    h->h_other.pinned = true;
+    h->h_ovl.pinned = true;
+    std::memset(&h->ostats, 0, sizeof(h->ostats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -1587,6 +1602,273 @@ int vsg_render_last_adjacency_stats(vsg_render* h, vsg_render_adjacency_stats* s
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->astats;
+  });
+}
+
+int vsg_render_level_overlap(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                             const int32_t* other, size_t other_pitch, int mem_other,
+                             vsg_render_overlap_row* rows, size_t capacity_rows, size_t* num_rows,
+                             vsg_render_overlap_col* cols, size_t capacity_cols, size_t* num_cols,
+                             vsg_render_overlap_pair* pairs, size_t capacity_pairs, size_t* num_pairs,
+                             int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_overlap_row) == kOverlapRowWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_overlap_col) == kOverlapColWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_overlap_pair) == kOverlapPairWords * sizeof(int32_t), "moved as int32 words");
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_rows || !num_cols || !num_pairs) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_rows = *num_cols = *num_pairs = 0;
+    if (!other) Throw(VSG_ERR_INVALID, "other is null");
+    if (mem_other != VSG_MEM_HOST && mem_other != VSG_MEM_DEVICE) {
+      Throw(VSG_ERR_INVALID, "mem_other is neither VSG_MEM_HOST nor VSG_MEM_DEVICE");
+    }
+    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    CheckMem(mem_out, "outputs");
+    const int W = h->W, H = h->H;
+    if (other_pitch != 0 && other_pitch < (size_t)W) {
+      Throw(VSG_ERR_INVALID, "the pitch of other, " + std::to_string(other_pitch) + ", is below the width " +
+                                 std::to_string(W));
+    }
+    const size_t pitch = other_pitch ? other_pitch : (size_t)W;
+    const bool count_only =
+        !rows && !cols && !pairs && capacity_rows == 0 && capacity_cols == 0 && capacity_pairs == 0;
+    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+    DeviceGuard guard(h->device);
+    vsg_render_overlap_stats& os = h->ostats;
+    std::memset(&os, 0, sizeof(os));
+
+    // ---- P: the level's ids, or the indices of its regions' components ----
+    const int32_t* plane = nullptr;
+    const int32_t* comp_table = nullptr;
+    uint32_t max_group = 0;
+    uint64_t groups_bound = 0;   // no more groups than this
+    bool vector = false;
+    if (connectedness == 0) {
+      int32_t max_id = 0;
+      vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
+      plane = h->d_ids.As<int32_t>();
+      max_group = (uint32_t)max_id;
+      groups_bound = (uint64_t)h->stats.distinct_ids;
+      os.launches = h->stats.launches;
+    } else {
+      size_t n_components = 0, n_intervals = 0;
+      LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
+                      nullptr, VSG_MEM_DEVICE, true);
+      plane = h->d_labels.As<int32_t>();
+      comp_table = h->d_comp_table.As<int32_t>();
+      max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
+      groups_bound = n_components;
+      const vsg_render_component_stats& cs = h->cstats;
+      os.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                    cs.label_us;
+      os.launches = h->stats.launches;
+    }
+    int group_bits = 1;
+    while (group_bits < 31 && (max_group >> group_bits)) ++group_bits;
+
+    // ---- B: where it is, or through the pinned block to the device, rows packed ----
+    h->d_ovl_status.Reserve(sizeof(OvlStatus), &h->allocations);
+    h->h_ovl.Reserve(2 * sizeof(OvlStatus), &h->allocations);
+    h->d_ovl_totals.Reserve((size_t)H * kOverlapRowTotals * sizeof(uint32_t), &h->allocations);
+    OvlStatus* status = h->d_ovl_status.As<OvlStatus>();
+    OvlStatus* seen = h->h_ovl.As<OvlStatus>();   // [0] after the count, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(OvlStatus));
+    int launches = 0;
+    const int32_t* label_plane = other;
+    size_t label_pitch = pitch;
+    h->oclock.Begin(h->stream);
+    if (mem_other == VSG_MEM_HOST) {
+      const size_t bytes = (size_t)W * H * sizeof(int32_t);
+      h->h_other.Reserve(bytes, &h->allocations);
+      h->d_other.Reserve(bytes, &h->allocations);
+      for (int y = 0; y < H; ++y) {
+        std::memcpy(h->h_other.As<int32_t>() + (size_t)y * W, other + (size_t)y * pitch, (size_t)W * sizeof(int32_t));
+      }
+      VSG_HIP(hipMemcpyAsync(h->d_other.p, h->h_other.p, bytes, hipMemcpyHostToDevice, h->stream));
+      label_plane = h->d_other.As<int32_t>();
+      label_pitch = (size_t)W;
+      ++launches;
+    }
+    h->oclock.Mark(OVL_UPLOAD);
+
+    // ---- count: the number of runs sizes everything below ----
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(OvlStatus), h->stream));
+    LaunchOverlapRuns(plane, label_plane, label_pitch, W, H, 1, 1, false, 0, nullptr, nullptr,
+                      h->d_ovl_totals.As<uint32_t>(), status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->oclock.Mark(OVL_COUNT);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(OvlStatus), hipMemcpyDeviceToHost, h->stream));
+    launches += 4;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[OVL_STAGES];
+      h->oclock.Read(us, OVL_STAGES);
+      os.count_us = us[OVL_COUNT];
+      os.plane_us += us[OVL_UPLOAD];
+    }
+    if (connectedness == 0) {
+      float us[STAGE_COUNT];
+      h->clock.Read(us, STAGE_COUNT);
+      h->stats.clear_us = us[STAGE_CLEAR];
+      h->stats.fill_us = us[STAGE_FILL];
+      os.plane_us += us[STAGE_CLEAR] + us[STAGE_FILL];
+      if (vector) h->CheckVector();
+    }
+    auto finish = [&] {
+      os.launches += launches;
+      h->stats.launches += launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    os.covered = seen[0].covered;
+    os.labelled = seen[0].labelled;
+    os.both = seen[0].both;
+    os.runs = seen[0].runs;
+    if (seen[0].runs > 0x7fffffffu) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the two planes have more than 2^31 - 1 runs");
+    }
+    const uint32_t n = seen[0].runs;
+    if (n == 0) return finish();   // nothing covered and nothing labelled: all three lists are empty
+
+    // ---- emit, sort, table ----
+    const uint32_t max_label = seen[0].max_label;
+    int label_bits = 1;
+    while (label_bits < 31 && (max_label >> label_bits)) ++label_bits;
+    const int end_bit = group_bits + label_bits + 2;
+    // distinct keys: no more than runs, and no more than (groups or none) x (labels or none)
+    const uint32_t m = (uint32_t)std::min<uint64_t>(n, (groups_bound + 1) * ((uint64_t)max_label + 2));
+    const uint32_t cap_rows = (uint32_t)std::min<uint64_t>(groups_bound, n);   // every group has a run
+    if (seen[0].covered && cap_rows == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
+    const size_t temp_bytes = std::max<size_t>(std::max(LevelTempBytes(n, end_bit), OverlapScanTempBytes(n)), 16);
+    const size_t row_bytes = (size_t)cap_rows * sizeof(vsg_render_overlap_row);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    h->d_ovl_runs.Reserve((size_t)n * 2 * 12, &h->allocations);
+    h->d_ovl_heads.Reserve((size_t)n * 2 * sizeof(unsigned long long), &h->allocations);
+    h->d_ovl_keys.Reserve((size_t)m * 24 + 8, &h->allocations);
+    h->d_ovl_rows.Reserve(std::max<size_t>(row_bytes, 16), &h->allocations);
+    h->d_ovl_cols.Reserve((size_t)m * sizeof(vsg_render_overlap_col), &h->allocations);
+    h->d_ovl_pairs.Reserve((size_t)m * sizeof(vsg_render_overlap_pair), &h->allocations);
+    // runs: keys, sorted keys, lengths, sorted lengths
+    unsigned long long* keys = h->d_ovl_runs.As<unsigned long long>();
+    unsigned long long* keys_sorted = keys + n;
+    uint32_t* lengths = reinterpret_cast<uint32_t*>(keys + 2 * (size_t)n);
+    uint32_t* lengths_sorted = lengths + n;
+    unsigned long long* row_heads = h->d_ovl_heads.As<unsigned long long>();
+    unsigned long long* key_heads = row_heads + n;
+    // distinct keys: key, rank, start (m + 1), the columns' first keys (m + 1)
+    unsigned long long* dkey = h->d_ovl_keys.As<unsigned long long>();
+    unsigned long long* drank = dkey + m;
+    uint32_t* dstart = reinterpret_cast<uint32_t*>(dkey + 2 * (size_t)m);
+    uint32_t* cfirst = dstart + m + 1;
+    // the column sort: its operands where the unsorted runs were, its results and the labels' ranks where
+    // the scans were; m <= n, and both are read for the last time before they are written again
+    unsigned long long* ckeys = keys;
+    uint32_t* cvals = lengths;
+    unsigned long long* ckeys_sorted = row_heads;
+    uint32_t* cvals_sorted = reinterpret_cast<uint32_t*>(key_heads);
+    uint32_t* col_rank = cvals_sorted + n;
+    int32_t* d_rows = h->d_ovl_rows.As<int32_t>();
+    int32_t* d_cols = h->d_ovl_cols.As<int32_t>();
+    int32_t* d_pairs = h->d_ovl_pairs.As<int32_t>();
+    h->oclock.Begin(h->stream);
+    LaunchOverlapRuns(plane, label_plane, label_pitch, W, H, group_bits, label_bits, true, n, keys, lengths, nullptr,
+                      status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->oclock.Mark(OVL_EMIT);
+    VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, lengths, lengths_sorted, n, end_bit,
+                      h->stream));
+    h->oclock.Mark(OVL_SORT);
+    if (row_bytes) VSG_HIP(hipMemsetAsync(d_rows, 0, row_bytes, h->stream));   // `unlabelled` of a row without any
+    VSG_HIP(OverlapRank(h->d_sort_temp.p, temp_bytes, keys_sorted, lengths_sorted, group_bits, label_bits, row_heads,
+                        key_heads, n, h->stream));
+    LaunchOverlapTable(keys_sorted, lengths_sorted, row_heads, key_heads, n, m, group_bits, label_bits, max_group,
+                       cap_rows, comp_table, dkey, dstart, drank, d_rows, d_pairs, ckeys, cvals, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cvals, cvals_sorted, m, end_bit, h->stream));
+    VSG_HIP(OverlapColRank(h->d_sort_temp.p, temp_bytes, ckeys_sorted, group_bits, label_bits, col_rank, m,
+                           h->stream));
+    LaunchOverlapCols(ckeys_sorted, cvals_sorted, col_rank, dstart, drank, m, group_bits, label_bits, cfirst, d_cols,
+                      d_pairs, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->oclock.Mark(OVL_TABLE);
+    // emit, a clear, table, pairs, rows, column heads, columns; two sorts and three scans counted as one each
+    launches += 12;
+    const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE;
+    if (to_device) {
+      // the lengths of the lists are on the device: the copy decides there whether they fit
+      LaunchOverlapCopy(d_rows, d_cols, d_pairs, rows ? (uint32_t)std::min<size_t>(capacity_rows, cap_rows) : 0u,
+                        cols ? (uint32_t)std::min<size_t>(capacity_cols, m) : 0u,
+                        pairs ? (uint32_t)std::min<size_t>(capacity_pairs, m) : 0u, reinterpret_cast<int32_t*>(rows),
+                        reinterpret_cast<int32_t*>(cols), reinterpret_cast<int32_t*>(pairs), status, h->stream);
+      VSG_HIP(hipGetLastError());
+      ++launches;
+    }
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(OvlStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[OVL_STAGES];
+      h->oclock.Read(us, OVL_STAGES);
+      os.emit_us = us[OVL_EMIT];
+      os.sort_us = us[OVL_SORT];
+      os.table_us = us[OVL_TABLE];
+    }
+    if ((seen[1].flags & OVL_FLAG_OVERFLOW) || seen[1].emitted != n) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "the emit pass found other runs than the count pass");
+    }
+    if ((seen[1].flags & OVL_FLAG_RANGE) || seen[1].distinct == 0 || seen[1].distinct > m ||
+        seen[1].rows > cap_rows || seen[1].pairs > m || seen[1].cols > m ||
+        (comp_table && seen[1].rows != groups_bound)) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "a sorted overlap key, a row, a column or a pair is out of range");
+    }
+    const size_t n_rows = seen[1].rows, n_cols = seen[1].cols, n_pairs = seen[1].pairs;
+    *num_rows = n_rows;
+    *num_cols = n_cols;
+    *num_pairs = n_pairs;
+    os.rows = (int64_t)n_rows;
+    os.cols = (int64_t)n_cols;
+    os.pairs = (int64_t)n_pairs;
+    os.largest_row_pairs = seen[1].largest;
+    if (count_only) return finish();
+    if (n_rows > capacity_rows || n_cols > capacity_cols || n_pairs > capacity_pairs) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the table has " + std::to_string(n_rows) + " rows, " + std::to_string(n_cols) +
+                                 " columns and " + std::to_string(n_pairs) + " pairs, the capacities are " +
+                                 std::to_string(capacity_rows) + ", " + std::to_string(capacity_cols) + " and " +
+                                 std::to_string(capacity_pairs));
+    }
+    if ((n_rows && !rows) || (n_cols && !cols) || (n_pairs && !pairs)) {
+      finish();
+      Throw(VSG_ERR_INVALID, "an output is null");
+    }
+    if (mem_out == VSG_MEM_HOST) {
+      // through the pinned block, now that the lengths are known
+      const size_t rb = n_rows * sizeof(vsg_render_overlap_row), cb = n_cols * sizeof(vsg_render_overlap_col);
+      const size_t pb = n_pairs * sizeof(vsg_render_overlap_pair);
+      h->h_ovl.Reserve(2 * sizeof(OvlStatus) + rb + cb + pb, &h->allocations);
+      char* stage = reinterpret_cast<char*>(h->h_ovl.As<OvlStatus>() + 2);
+      if (rb) VSG_HIP(hipMemcpyAsync(stage, d_rows, rb, hipMemcpyDeviceToHost, h->stream));
+      if (cb) VSG_HIP(hipMemcpyAsync(stage + rb, d_cols, cb, hipMemcpyDeviceToHost, h->stream));
+      if (pb) VSG_HIP(hipMemcpyAsync(stage + rb + cb, d_pairs, pb, hipMemcpyDeviceToHost, h->stream));
+      launches += (rb ? 1 : 0) + (cb ? 1 : 0) + (pb ? 1 : 0);
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      if (rb) std::memcpy(rows, stage, rb);
+      if (cb) std::memcpy(cols, stage + rb, cb);
+      if (pb) std::memcpy(pairs, stage + rb + cb, pb);
+    }
+    finish();
+  });
+}
+
+int vsg_render_last_overlap_stats(vsg_render* h, vsg_render_overlap_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->ostats;
   });
 }
 
