@@ -46,7 +46,10 @@
  * the reference has no per-frame counterpart (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
  * against ground truth and correspondence between frames are not offered either, but the table they are
  * all functions of is: vsg_render_level_overlap relates a level to a ground-truth label image or to the id
- * image of another frame.
+ * image of another frame.  Boundary scores over a whole hierarchy are not offered; the ultrametric contour
+ * map they are functions of is: vsg_render_persistence_image, vsg_render_persistence_frame and
+ * vsg_render_persistence_graph return, for every pixel side and for every pair of touching level-0
+ * regions, the number of hierarchy levels at which the two sides are still different regions.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -505,6 +508,78 @@ typedef struct vsg_render_overlap_stats {
   int launches;
 } vsg_render_overlap_stats;
 int vsg_render_last_overlap_stats(vsg_render* h, vsg_render_overlap_stats* s);
+
+/* ---- Boundary persistence: the edges of all hierarchy levels in one pass ----
+ *
+ * Hierarchy.  The desc's own hierarchy when it carries one, else the handle's kept one.  A desc's own
+ * hierarchy replaces the kept one, exactly as in vsg_render_id_image.
+ * Height.  L = max(1, number of levels of that hierarchy).  L > 65535 is VSG_ERR_INVALID.
+ * Ancestors.  A_l(r) = GetParentId(r, 0, l) for l in [0, L), with A_0(r) = r.  The lookups and refusals
+ * are exactly those of vsg_render_id_image at level L - 1: an unsorted level or an id missing from a level
+ * is VSG_ERR_INVALID, and so is a negative region id, as in vsg_render_level_regions.  Only regions that
+ * paint at least one pixel (that have a scan interval or, in a vector-only desc, a polygon) are looked up.
+ * Persistence of two region ids.  pers(a, b) is the number of l in [0, L) with A_l(a) != A_l(b).  So
+ * pers(a, a) = 0, and pers(a, b) is in [1, L] for a != b.  "No region" (-1) against a region is L; -1
+ * against -1 is 0.  A_{l+1} is a function of A_l, so "differ at l" is monotone in l; the device finds the
+ * count by bisection over a table of ancestors.
+ * The persistence plane Q, W x H int32, with P0 the level-0 id image:
+ *   Q(x, y) = max( pers(P0(x,y), P0(x+1,y)) if x+1 < W,  pers(P0(x,y), P0(x,y+1)) if y+1 < H ),
+ * and 0 when neither neighbour exists.  This is the reference's edge rule (segmentation_render.h:159-182:
+ * right and below, in frame), as vsg_render_frame applies it.  Consequence: for every l in [0, L), Q > l
+ * holds exactly where vsg_render_id_image(level = l) differs from its in-frame right or below neighbour,
+ * -1 counting as a value; so Q > l is the set of pixels highlight_edges blackens at level l.
+ * The persistence picture, H rows of BGR24: every byte is (s * (L - Q) + L / 2) / L in unsigned integer
+ * arithmetic, s being the source frame's byte with has_video and 255 without.  Only the first 3 * W bytes
+ * of a row are written; out_stride 0 means vsg_render_default_stride.  blend_alpha, highlight_edges,
+ * hierarchy_level and concat_with_source are not looked at.  There are no floats in it.
+ * The persistence graph.  Nodes and edges are byte for byte those of
+ * vsg_render_level_adjacency(level 0, connectedness 0, neighbourhood).  persistence[e] = pers(the id of
+ * the node edge e belongs to, its neighbour_id) for every directed edge e; it is symmetric.  level_sides[l]
+ * for l in [0, L) is an int64: the number of unordered pairs of in-frame, side-adjacent pixels whose ids at
+ * level l are both >= 0 and differ.  Equivalently, level_sides[l] = 1/2 of the sum of shared_n4 over the
+ * edges with persistence > l, and 1/2 of the sum of border_shared over the nodes of
+ * vsg_render_level_adjacency at level l.  With VSG_RENDER_ADJACENT_N8, an edge that is diagonal-only
+ * (shared_n4 = 0) still gets its persistence.
+ *
+ * vsg_render_persistence_image writes Q (W * H int32, rows W apart) to out_int32 in mem_out memory and L to
+ * *num_levels.  vsg_render_persistence_frame writes the picture to `out` and L to *num_levels; bgr, stride
+ * and mem_in are those of vsg_render_frame: bgr is required with has_video and ignored without.
+ * vsg_render_persistence_graph runs the adjacency pipeline at level 0 internally
+ * (vsg_render_last_adjacency_stats then describes it), then one kernel over the edges and one small
+ * reduction.  The number of launches of each call does not depend on L.
+ *
+ * *num_nodes, *num_edges and *num_levels are always set on VSG_OK and when a capacity is too small (the
+ * persistence list has capacity_edges entries); in that case the call fails with VSG_ERR_INVALID and no
+ * output is touched.  All four outputs NULL with all three capacities 0 asks for the counts only (VSG_OK;
+ * needs the device).  A null handle, a null output of the image and frame calls, a null count pointer,
+ * an unknown memory kind or a neighbourhood other than VSG_RENDER_ADJACENT_N4 and
+ * VSG_RENDER_ADJACENT_N8 is VSG_ERR_INVALID, answered before the handle is dereferenced, and touches no
+ * device.  Vector-only descs are scan converted at the handle's size first.  Every call returns after its
+ * stream work has finished. */
+int vsg_render_persistence_image(vsg_render* h, const uint8_t* seg, size_t seg_len,
+                                 int32_t* out_int32, int* num_levels, int mem_out);
+int vsg_render_persistence_frame(vsg_render* h, const uint8_t* seg, size_t seg_len,
+                                 const uint8_t* bgr, size_t stride, int mem_in,
+                                 uint8_t* out, size_t out_stride, int mem_out, int* num_levels);
+int vsg_render_persistence_graph(vsg_render* h, const uint8_t* seg, size_t seg_len, int neighbourhood,
+                                 vsg_render_level_node* nodes, size_t capacity_nodes, size_t* num_nodes,
+                                 vsg_render_level_edge* edges, size_t capacity_edges, size_t* num_edges,
+                                 int32_t* persistence,            /* capacity_edges entries */
+                                 int64_t* level_sides, size_t capacity_levels, size_t* num_levels,
+                                 int mem_out);
+
+/* What the last persistence call of the handle did; fields that a call does not compute are 0.  levels: L.
+ * regions: the columns of the ancestor table, the distinct ids of the regions that paint.  edge_pixels and
+ * top_pixels (image and frame calls): pixels with Q > 0 and with Q == L.  nodes and edges (graph call).
+ * Device times are HIP events around the stages: plane_us, making the level-0 plane (clear and fill);
+ * persist_us, k_persist_plane, or k_persist_edges with k_persist_sides; compose_us, k_persist_compose;
+ * graph_us, the count, emit, sort and table stages of the internal adjacency call. */
+typedef struct vsg_render_persistence_stats {
+  int64_t levels, regions, edge_pixels /* Q > 0 */, top_pixels /* Q == L */, nodes, edges;
+  float plane_us, persist_us, compose_us, graph_us;
+  int launches;
+} vsg_render_persistence_stats;
+int vsg_render_last_persistence_stats(vsg_render* h, vsg_render_persistence_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

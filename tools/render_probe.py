@@ -61,6 +61,15 @@ Per call the five stage times of vsg_render_overlap_stats, launches, runs, rows,
 in the same run vsg_render_level_adjacency (N4 sides, same connectedness, outputs in device memory) on the
 same desc and handle is timed: the yardstick, which makes the same plane, reads it twice and sorts.  No pass
 or fail threshold.
+
+    python tools/render_probe.py --persistence [--reps 30] [--out profiles/persistence.json]
+
+The persistence leg: the same descs with their hierarchy cut to 1, 2, 5 and all of its levels, asked for the
+persistence plane (vsg_render_persistence_image, device memory), the picture (vsg_render_persistence_frame,
+source and picture in device memory) and the graph (vsg_render_persistence_graph, N4, device memory).  Per call
+the stage times of vsg_render_persistence_stats and launches are recorded; in the same run, on the same handle
+and desc, the yardstick for the same information: L calls of vsg_render_id_image, one per level, for the plane,
+and L calls of vsg_render_level_adjacency, one per level, for the graph.  No pass or fail threshold.
 """
 import argparse
 import json
@@ -97,12 +106,15 @@ def main():
                     help="the adjacency leg instead (profiles/level_adjacency.json)")
     ap.add_argument("--level-overlap", action="store_true",
                     help="the overlap leg instead (profiles/level_overlap.json)")
+    ap.add_argument("--persistence", action="store_true",
+                    help="the persistence leg instead (profiles/persistence.json)")
     args = ap.parse_args()
     if ((args.level_regions or args.level_components or args.level_boundaries or args.level_adjacency
-         or args.level_overlap) and "--reps" not in sys.argv):
+         or args.level_overlap or args.persistence) and "--reps" not in sys.argv):
         args.reps = 30
     if args.out is None:
-        name = ("level_overlap.json" if args.level_overlap else
+        name = ("persistence.json" if args.persistence else
+                "level_overlap.json" if args.level_overlap else
                 "level_adjacency.json" if args.level_adjacency else
                 "level_boundaries.json" if args.level_boundaries else
                 "level_components.json" if args.level_components else "level_regions.json" if args.level_regions
@@ -119,6 +131,8 @@ def main():
     result = {"device": torch.cuda.get_device_name(0), "reps": args.reps, "warmup": args.warmup, "cases": []}
     if args.vector:
         return vector_leg(args, result, dev)
+    if args.persistence:
+        return persistence_leg(args, result, dev)
     if args.level_overlap:
         return overlap_leg(args, result, dev)
     if args.level_adjacency:
@@ -496,6 +510,81 @@ def overlap_leg(args, result, dev):
                     json.dump(result, f, indent=1)
                     f.write("\n")
         r.close()
+    print("wrote", args.out)
+
+
+def persistence_leg(args, result, dev):
+    import torch
+    import synth
+    import video_segment_amd as vsg
+    from video_segment_amd import render
+    from test_proto_wire import build_schema
+    Msg = build_schema()
+    for size, W, H, seg, height in level_descs(args):
+        src = torch.from_numpy(synth.bench_frame(W, H, 0)).to(dev)
+        for L in sorted({1, 2, 5, height} & set(range(1, height + 1))):
+            m = Msg()
+            m.ParseFromString(seg)
+            del m.hierarchy[(L if L > 1 else 0):]       # the top level's parents are never looked up
+            cut = m.SerializeToString()
+            r = vsg.SegmentationRenderer(W, H)          # a handle of its own: no kept hierarchy from another height
+            plane = torch.empty((H, W), dtype=torch.int32, device=dev)
+            ids = torch.empty((H, W), dtype=torch.int32, device=dev)
+            picture = torch.empty((H, W, 3), dtype=torch.uint8, device=dev)
+            assert r.persistence_image(cut, out=plane)[1] == L
+            nn, ne = (len(a) for a in r.level_adjacency(cut, 0))
+            nodes = torch.empty((nn, render.LEVEL_NODE_WORDS), dtype=torch.int32, device=dev)
+            edges = torch.empty((ne, render.LEVEL_EDGE_WORDS), dtype=torch.int32, device=dev)
+            persistence = torch.empty((ne,), dtype=torch.int32, device=dev)
+            level_sides = torch.empty((L,), dtype=torch.int64, device=dev)
+            keys = ["image_call_ms", "image_plane_us", "image_persist_us", "frame_call_ms", "frame_plane_us",
+                    "frame_persist_us", "frame_compose_us", "graph_call_ms", "graph_plane_us", "graph_graph_us",
+                    "graph_persist_us", "id_image_per_level_call_ms", "level_adjacency_per_level_call_ms"]
+            rows = {k: [] for k in keys}
+            launches = {}
+            for it in range(args.warmup + args.reps):
+                st = {}
+                t0 = time.perf_counter()
+                r.persistence_image(cut, out=plane)
+                st["image_call_ms"] = (time.perf_counter() - t0) * 1e3
+                ps = r.last_persistence_stats()
+                st.update({"image_" + k: ps[k] for k in ("plane_us", "persist_us")})
+                launches["image"] = ps["launches"]
+                t0 = time.perf_counter()
+                r.persistence_frame(cut, src, out=picture)
+                st["frame_call_ms"] = (time.perf_counter() - t0) * 1e3
+                ps = r.last_persistence_stats()
+                st.update({"frame_" + k: ps[k] for k in ("plane_us", "persist_us", "compose_us")})
+                launches["frame"] = ps["launches"]
+                t0 = time.perf_counter()
+                r.persistence_graph(cut, render.ADJACENT_N4, nodes, edges, persistence, level_sides)
+                st["graph_call_ms"] = (time.perf_counter() - t0) * 1e3
+                ps = r.last_persistence_stats()
+                st.update({"graph_" + k: ps[k] for k in ("plane_us", "graph_us", "persist_us")})
+                launches["graph"] = ps["launches"]
+                # the yardsticks: one call per level
+                t0 = time.perf_counter()
+                for level in range(L):
+                    r.id_image(cut, level, out=ids)
+                st["id_image_per_level_call_ms"] = (time.perf_counter() - t0) * 1e3
+                t0 = time.perf_counter()
+                for level in range(L):
+                    r.level_adjacency(cut, level, 0, render.ADJACENT_N4, nodes_out=nodes, edges_out=edges)
+                st["level_adjacency_per_level_call_ms"] = (time.perf_counter() - t0) * 1e3
+                if it >= args.warmup:
+                    for k in rows:
+                        rows[k].append(st[k])
+            case = {"size": size, "hierarchy_levels": L, "regions": ps["regions"], "nodes": ps["nodes"],
+                    "edges": ps["edges"], "edge_pixels": int((plane > 0).sum()), "top_pixels": int((plane == L).sum()),
+                    "image_launches": launches["image"], "frame_launches": launches["frame"],
+                    "graph_launches": launches["graph"]}
+            case.update({k: dict(pct(v), unit=k.rsplit("_", 1)[1]) for k, v in rows.items()})
+            result["cases"].append(case)
+            print(json.dumps(case), flush=True)
+            with open(args.out, "w") as f:
+                json.dump(result, f, indent=1)
+                f.write("\n")
+            r.close()
     print("wrote", args.out)
 
 

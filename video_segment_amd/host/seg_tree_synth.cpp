@@ -38,6 +38,12 @@
 // level_overlap_rows=<sum> overlap_cols=<sum> overlap_pairs=<sum> overlap_fnv1a32=<hash of the three lists'
 // bytes, rows, cols and pairs of every compared frame in that order>.
 //
+//   --persistence [--adjacency_n8]
+// asks vsg_render_persistence_image and vsg_render_persistence_graph (pixel sides, or with --adjacency_n8 also
+// diagonal contacts) for the boundary persistence of every frame's hierarchy and prints a line
+// persistence_levels=<L of the last frame> persistence_edge_pixels=<sum> persistence_edges=<sum>
+// persistence_fnv1a32=<hash of every frame's plane, then persistence, then level_sides bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -498,6 +504,80 @@ class LevelAdjacencySinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --persistence: the boundary persistence of every frame's hierarchy: the plane of
+// vsg_render_persistence_image, then the edges' persistences and the levels' sides of
+// vsg_render_persistence_graph.
+class PersistenceSinkUnit : public VideoUnit {
+ public:
+  PersistenceSinkUnit(bool n8, int device)
+      : neighbourhood_(n8 ? VSG_RENDER_ADJACENT_N8 : VSG_RENDER_ADJACENT_N4), device_(device) {}
+  ~PersistenceSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    plane_.resize((size_t)s.frame_width() * s.frame_height());
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    VF_CHECK(vsg_render_persistence_image(render_, seg, desc.wire.size(), plane_.data(), &levels_, VSG_MEM_HOST) ==
+                 VSG_OK,
+             vsg_render_last_error());
+    vsg_render_persistence_stats st;
+    VF_CHECK(vsg_render_last_persistence_stats(render_, &st) == VSG_OK, vsg_render_last_error());
+    edge_pixels_ += (long)st.edge_pixels;
+    size_t nn = 0, ne = 0, nl = 0;
+    VF_CHECK(vsg_render_persistence_graph(render_, seg, desc.wire.size(), neighbourhood_, nullptr, 0, &nn, nullptr, 0,
+                                          &ne, nullptr, nullptr, 0, &nl, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    nodes_buf_.resize(std::max<size_t>(nn, 1));
+    edges_buf_.resize(std::max<size_t>(ne, 1));
+    persistence_.resize(std::max<size_t>(ne, 1));
+    sides_.resize(nl);
+    VF_CHECK(vsg_render_persistence_graph(render_, seg, desc.wire.size(), neighbourhood_, nodes_buf_.data(), nn, &nn,
+                                          edges_buf_.data(), ne, &ne, persistence_.data(), sides_.data(), nl, &nl,
+                                          VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    Hash(plane_.data(), plane_.size() * sizeof(int32_t));
+    Hash(persistence_.data(), ne * sizeof(int32_t));
+    Hash(sides_.data(), nl * sizeof(int64_t));
+    edges_ += (long)ne;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  int levels() const { return levels_; }
+  long edge_pixels() const { return edge_pixels_; }
+  long edges() const { return edges_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int neighbourhood_, device_, seg_idx_ = -1, levels_ = 0;
+  vsg_render* render_ = nullptr;
+  std::vector<int32_t> plane_, persistence_;
+  std::vector<int64_t> sides_;
+  std::vector<vsg_render_level_node> nodes_buf_;
+  std::vector<vsg_render_level_edge> edges_buf_;
+  long edge_pixels_ = 0, edges_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 // --level_overlap: the same for the overlap table of a level's regions, or of their connected components,
 // with the previous frame's id image at that level (vsg_render_level_overlap): rows, cols, pairs of every
 // frame after the first.
@@ -684,6 +764,9 @@ struct Flags {
   // with --overlap_components
   int level_overlap = -1;
   bool overlap_components = false;
+  // vsg_render_persistence_image and vsg_render_persistence_graph for every frame; the graph's
+  // neighbourhood is --adjacency_n8's
+  bool persistence = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -717,7 +800,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
-                                   "adjacency_components", "overlap_components", "help"};
+                                   "adjacency_components", "overlap_components", "persistence", "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -772,6 +855,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "adjacency_components") f->adjacency_components = bv;
     else if (a == "level_overlap") f->level_overlap = atoi(v.c_str());
     else if (a == "overlap_components") f->overlap_components = bv;
+    else if (a == "persistence") f->persistence = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -1007,6 +1091,12 @@ int main(int argc, char** argv) {
     overlap_sink->AttachTo(input);
     input = overlap_sink.get();
   }
+  std::unique_ptr<PersistenceSinkUnit> persistence_sink;
+  if (FLAGS.persistence) {
+    persistence_sink.reset(new PersistenceSinkUnit(FLAGS.adjacency_n8, FLAGS.device));
+    persistence_sink->AttachTo(input);
+    input = persistence_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -1069,6 +1159,11 @@ int main(int argc, char** argv) {
   if (overlap_sink) {
     std::printf("level_overlap_rows=%ld overlap_cols=%ld overlap_pairs=%ld overlap_fnv1a32=%08x\n",
                 overlap_sink->rows(), overlap_sink->cols(), overlap_sink->pairs(), overlap_sink->hash());
+  }
+  if (persistence_sink) {
+    std::printf("persistence_levels=%d persistence_edge_pixels=%ld persistence_edges=%ld persistence_fnv1a32=%08x\n",
+                persistence_sink->levels(), persistence_sink->edge_pixels(), persistence_sink->edges(),
+                persistence_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

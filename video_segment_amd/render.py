@@ -92,6 +92,15 @@ class VsgRenderOverlapStats(_capi.Structure):
     ]
 
 
+class VsgRenderPersistenceStats(_capi.Structure):
+    _fields_ = [
+        ("levels", C.c_int64), ("regions", C.c_int64), ("edge_pixels", C.c_int64), ("top_pixels", C.c_int64),
+        ("nodes", C.c_int64), ("edges", C.c_int64),
+        ("plane_us", C.c_float), ("persist_us", C.c_float), ("compose_us", C.c_float), ("graph_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -179,6 +188,8 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_boundaries", "vsg_render_last_boundary_stats",
     "vsg_render_level_adjacency", "vsg_render_last_adjacency_stats",
     "vsg_render_level_overlap", "vsg_render_last_overlap_stats",
+    "vsg_render_persistence_image", "vsg_render_persistence_frame", "vsg_render_persistence_graph",
+    "vsg_render_last_persistence_stats",
 ]
 
 
@@ -230,6 +241,13 @@ def lib():
                                            vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t,
                                            C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_overlap_stats.argtypes = [vp, C.POINTER(VsgRenderOverlapStats)]
+    L.vsg_render_persistence_image.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.POINTER(C.c_int), C.c_int]
+    L.vsg_render_persistence_frame.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, vp, C.c_size_t,
+                                               C.c_int, C.POINTER(C.c_int)]
+    L.vsg_render_persistence_graph.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t,
+                                               C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp,
+                                               C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_persistence_stats.argtypes = [vp, C.POINTER(VsgRenderPersistenceStats)]
     _handle = L
     return L
 
@@ -619,6 +637,101 @@ class SegmentationRenderer(_capi.Handle):
         """vsg_render_last_overlap_stats of the last level_overlap call, as a dict."""
         s = VsgRenderOverlapStats()
         check(lib().vsg_render_last_overlap_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def persistence_image(self, seg_bytes, out=None):
+        """The boundary persistence plane of the desc's hierarchy: (plane, levels).  plane: H x W int32, for
+        every pixel the number of hierarchy levels at which it still differs from its right or its below
+        neighbour (0: inside a level-0 region; levels: a boundary no level removes), so that plane > l is
+        the edge mask of level l; levels: the hierarchy's height L.  out: a contiguous int32 numpy array or
+        torch CUDA tensor to fill instead of a new numpy array."""
+        if out is None:
+            out = np.empty((self.H, self.W), np.int32)
+        if tuple(out.shape) != (self.H, self.W) or str(out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("out has to be %d x %d int32" % (self.H, self.W))
+        p, mem = _capi.contiguous_ptr(out)
+        seg_bytes = bytes(seg_bytes)
+        levels = C.c_int()
+        check(lib().vsg_render_persistence_image(self.h, seg_bytes, len(seg_bytes), p, C.byref(levels), mem))
+        return out, levels.value
+
+    def persistence_frame(self, seg_bytes, bgr=None, out=None):
+        """The persistence plane as a picture, H x W x 3 uint8: the source frame (white without has_video)
+        darkened by (L - Q) / L, so that a boundary is the darker the more levels it survives.  A numpy array,
+        or a torch CUDA tensor when bgr is one.  out: a caller's buffer instead, as in render()."""
+        p_bgr, stride, mem_in = None, 0, VSG_MEM_HOST
+        if self.opts.has_video:
+            if bgr is None:
+                raise ValueError("the renderer was created with has_video: pass the source frame")
+            p_bgr, stride, mem_in = _frame_ptr(bgr, self.H, self.W, "bgr")
+        if out is None:
+            if bgr is not None and self.opts.has_video and _capi.is_torch(bgr) and bgr.is_cuda:
+                import torch
+                out = torch.empty((self.H, self.W, 3), dtype=torch.uint8, device=bgr.device)
+            else:
+                out = np.empty((self.H, self.W, 3), np.uint8)
+        p_out, out_stride, mem_out = _frame_ptr(out, self.H, self.W, "out")
+        seg_bytes = bytes(seg_bytes)
+        levels = C.c_int()
+        check(lib().vsg_render_persistence_frame(self.h, seg_bytes, len(seg_bytes), p_bgr, stride, mem_in, p_out,
+                                                 out_stride, mem_out, C.byref(levels)))
+        return out
+
+    def persistence_graph(self, seg_bytes, neighbourhood=ADJACENT_N4, nodes_out=None, edges_out=None,
+                          persistence_out=None, level_sides_out=None):
+        """The level-0 adjacency graph with the level at which every pair of touching regions merges: (nodes,
+        edges, persistence, level_sides).  nodes, edges: those of level_adjacency(seg, 0, 0, neighbourhood);
+        persistence: int32 per directed edge, the number of levels at which its two regions differ (levels:
+        never merged); level_sides: int64 per level, the pixel sides between different regions of that level.
+        Without outputs the counts are asked for first and the arrays are allocated exactly.  The four outputs
+        (all or none): buffers to fill instead, all numpy (LEVEL_NODE_DTYPE, LEVEL_EDGE_DTYPE, int32 and int64
+        arrays) or all torch CUDA tensors ((capacity, 7) int32, (capacity, 4) int32, int32 with at least the
+        edges' capacity, int64); the filled parts of them are returned."""
+        seg_bytes = bytes(seg_bytes)
+        hood = int(neighbourhood)
+        nn, ne, nl = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        outs = (nodes_out, edges_out, persistence_out, level_sides_out)
+        if any(o is None for o in outs) and not all(o is None for o in outs):
+            raise ValueError("pass all four outputs or none")
+        if nodes_out is None:
+            check(lib().vsg_render_persistence_graph(self.h, seg_bytes, len(seg_bytes), hood, None, 0, C.byref(nn),
+                                                     None, 0, C.byref(ne), None, None, 0, C.byref(nl), VSG_MEM_HOST))
+            nodes_out = np.empty(nn.value, LEVEL_NODE_DTYPE)
+            edges_out = np.empty(ne.value, LEVEL_EDGE_DTYPE)
+            persistence_out = np.empty(ne.value, np.int32)
+            level_sides_out = np.empty(nl.value, np.int64)
+        outs = (nodes_out, edges_out, persistence_out, level_sides_out)
+        if len({_capi.is_torch(o) for o in outs}) != 1:
+            raise ValueError("all outputs have to be numpy arrays or all torch tensors")
+        if _capi.is_torch(nodes_out):
+            if nodes_out.dim() != 2 or nodes_out.shape[1] != LEVEL_NODE_WORDS or str(nodes_out.dtype) != "torch.int32":
+                raise ValueError("nodes_out has to be (capacity, %d) int32" % LEVEL_NODE_WORDS)
+            if edges_out.dim() != 2 or edges_out.shape[1] != LEVEL_EDGE_WORDS or str(edges_out.dtype) != "torch.int32":
+                raise ValueError("edges_out has to be (capacity, %d) int32" % LEVEL_EDGE_WORDS)
+        else:
+            if nodes_out.dtype != LEVEL_NODE_DTYPE or nodes_out.ndim != 1:
+                raise ValueError("nodes_out has to be a one-dimensional LEVEL_NODE_DTYPE array")
+            if edges_out.dtype != LEVEL_EDGE_DTYPE or edges_out.ndim != 1:
+                raise ValueError("edges_out has to be a one-dimensional LEVEL_EDGE_DTYPE array")
+        if len(persistence_out.shape) != 1 or str(persistence_out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("persistence_out has to be one-dimensional int32")
+        if len(level_sides_out.shape) != 1 or str(level_sides_out.dtype).replace("torch.", "") != "int64":
+            raise ValueError("level_sides_out has to be one-dimensional int64")
+        if persistence_out.shape[0] < edges_out.shape[0]:
+            raise ValueError("persistence_out has to hold as many entries as edges_out")
+        ptrs = [_capi.contiguous_ptr(o) for o in outs]
+        if len({mem for _, mem in ptrs}) != 1:
+            raise ValueError("all outputs have to be in the same kind of memory")
+        check(lib().vsg_render_persistence_graph(self.h, seg_bytes, len(seg_bytes), hood, ptrs[0][0],
+                                                 nodes_out.shape[0], C.byref(nn), ptrs[1][0], edges_out.shape[0],
+                                                 C.byref(ne), ptrs[2][0], ptrs[3][0], level_sides_out.shape[0],
+                                                 C.byref(nl), ptrs[0][1]))
+        return nodes_out[:nn.value], edges_out[:ne.value], persistence_out[:ne.value], level_sides_out[:nl.value]
+
+    def last_persistence_stats(self):
+        """vsg_render_last_persistence_stats of the last persistence call, as a dict."""
+        s = VsgRenderPersistenceStats()
+        check(lib().vsg_render_last_persistence_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def last_vector_stats(self):

@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -320,6 +320,41 @@ void LaunchOverlapCols(const unsigned long long* ckeys_sorted, const uint32_t* c
 void LaunchOverlapCopy(const int32_t* rows, const int32_t* cols, const int32_t* pairs, uint32_t capacity_rows,
                        uint32_t capacity_cols, uint32_t capacity_pairs, int32_t* rows_out, int32_t* cols_out,
                        int32_t* pairs_out, const OvlStatus* status, hipStream_t stream);
+
+// ---- boundary persistence (persistence.hip): all hierarchy levels' edges from the level-0 plane --------
+
+enum PersFlag {
+  PERS_FLAG_RANGE = 1,   // a region number, a node or an edge was out of range
+};
+
+// Written by the persistence kernels; read by the host at the end of a call.
+struct PersStatus {
+  unsigned long long edge_pixels;   // pixels with Q > 0
+  unsigned long long top_pixels;    // pixels with Q == levels
+  uint32_t flags, pad;
+};
+
+// The persistence plane of the H x W plane of dense region numbers (row pitch PlanePitch(width), -1: no
+// region, the spare columns -1 as well): q[y * q_pitch + x] = the larger of the persistences of the pixel
+// against its in-frame right and below neighbours, 0 where it equals both.  table: (levels - 1) rows of
+// `regions` ancestors (persistence_table.h), not looked at when levels == 1; every number of the plane is
+// below `regions`.  status->edge_pixels and ->top_pixels are added to.
+void LaunchPersistPlane(const int32_t* plane, int pitch, int width, int height, const int32_t* table,
+                        uint32_t regions, int levels, int32_t* q, size_t q_pitch, PersStatus* status,
+                        hipStream_t stream);
+// Every byte of the H rows of 3 * width: (s * (levels - Q) + levels / 2) / levels with s the source's byte,
+// or 255 when src is null.  q: 16-byte aligned, q_pitch a multiple of 4.
+void LaunchPersistCompose(const int32_t* q, size_t q_pitch, int width, int height, int levels, const uint8_t* src,
+                          size_t src_stride, uint8_t* out, size_t out_stride, hipStream_t stream);
+// persistence[e] of every directed edge of the level-0 graph (LaunchAdjTable's nodes and edges, region
+// planes), hist[p] += shared_n4 of the edges with persistence p.  ids: the n_ids sorted region ids the
+// table's columns stand for.  hist has levels + 1 entries, cleared to zero before.  No launch without an
+// edge.
+void LaunchPersistEdges(const int32_t* nodes, uint32_t n_nodes, const int32_t* edges, uint32_t n_edges,
+                        const int32_t* ids, uint32_t n_ids, const int32_t* table, int levels, int32_t* persistence,
+                        unsigned long long* hist, PersStatus* status, hipStream_t stream);
+// level_sides[l] = half the sum of hist[p] over p > l, l in [0, levels).
+void LaunchPersistSides(const unsigned long long* hist, int levels, long long* level_sides, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

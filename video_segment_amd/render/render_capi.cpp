@@ -13,6 +13,7 @@
 
 #include "../../include/vsg_render.h"
 #include "render.h"
+#include "persistence_table.h"
 #include "../common/capi_support.h"
 
 namespace {
@@ -23,6 +24,7 @@ using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
 using vsg_render_impl::OvlStatus;
+using vsg_render_impl::PersStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
 
@@ -34,6 +36,8 @@ enum CompStage { CMP_LINK = 0, CMP_ORDER, CMP_MOMENTS, CMP_LABEL, CMP_WAIT, CMP_
 enum BoundStage { BND_COUNT = 0, BND_EMIT, BND_SORT, BND_TABLE, BND_STAGES };
 enum AdjStage { ADJ_COUNT = 0, ADJ_EMIT, ADJ_SORT, ADJ_TABLE, ADJ_STAGES };
 enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_STAGES };
+// PRS_WAIT: the source frame's upload between the two kernels of a picture; reported with no stage
+enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -332,7 +336,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -370,6 +374,11 @@ struct vsg_render {
   // outputs come back through
   Block d_other, h_other, d_ovl_totals, d_ovl_runs, d_ovl_heads, d_ovl_keys, d_ovl_rows, d_ovl_cols, d_ovl_pairs,
       d_ovl_status, h_ovl;
+  // boundary persistence: the region ids the ancestor table's columns stand for and the table (host, then
+  // one upload through the pinned block into d_anc: ids, then rows); the persistence plane of a picture or
+  // of a host output; the edges' persistences, the histogram and the levels' sides; the status words
+  std::vector<int32_t> pers_ids, pers_table;
+  Block d_anc, d_pq, d_pers_out, d_pers_status, h_pers;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
@@ -378,6 +387,7 @@ struct vsg_render {
   vsg_render_boundary_stats bstats;
   vsg_render_adjacency_stats astats;
   vsg_render_overlap_stats ostats;
+  vsg_render_persistence_stats pstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -589,9 +599,12 @@ int64_t AssignRegionValues(vsg_render* h, int level, const Hierarchy& hier, Valu
 // value_of(its id at `level`) and paints the W-pitched plane `ids` (device memory; -1 where no region
 // is).  Leaves clock between STAGE_FILL and the next mark, and the vector path's status in flight:
 // the caller calls CheckVector after its synchronisation when the desc was vector-only (returned).
-template <class ValueOf>
-bool PaintIds(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint32_t* ids, ValueOf value_of) {
-  const int W = h->W, H = h->H;
+// The plane's rows are `pitch` values apart, all of them cleared; ready() is called once every region has
+// its value, before any device work.
+template <class ValueOf, class Ready>
+bool PaintIdsAt(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint32_t* ids, int pitch,
+                ValueOf value_of, Ready ready) {
+  const int H = h->H;
   std::memset(&h->stats, 0, sizeof(h->stats));
   std::memset(&h->vstats, 0, sizeof(h->vstats));
   const double t0 = NowMs();
@@ -610,20 +623,27 @@ bool PaintIds(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint
   }
   const int64_t n_intervals = vector ? n_cross / 2 : (int64_t)h->intervals.size();
   h->stats.intervals = n_intervals;
+  ready();
   const double t1 = NowMs();
   h->stats.decode_ms = t1 - t0;
   if (vector) h->RunVector(n_cross);
   else h->UploadIntervals();
-  const size_t bytes = (size_t)W * H * sizeof(int32_t);
+  const size_t bytes = (size_t)pitch * H * sizeof(int32_t);
   h->stats.upload_ms = NowMs() - t1;
   h->clock.Begin(h->stream);
   VSG_HIP(hipMemsetAsync(ids, 0xff, bytes, h->stream));   // -1: no region
   h->clock.Mark(STAGE_CLEAR);
-  vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, W, h->stream);
+  vsg_render_impl::LaunchFill(static_cast<const Interval*>(h->d_intervals.p), n_intervals, ids, pitch, h->stream);
   VSG_HIP(hipGetLastError());
   h->clock.Mark(STAGE_FILL);
   h->stats.launches += 1 + (n_intervals == 0 ? 0 : 1);
   return vector;
+}
+
+// The W-pitched plane of vsg_render_id_image and the level calls.
+template <class ValueOf>
+bool PaintIds(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, uint32_t* ids, ValueOf value_of) {
+  return PaintIdsAt(h, seg, seg_len, level, ids, h->W, value_of, [] {});
 }
 
 // What the front half of the level calls leaves behind: n runs, unsorted (keys, rights) and, after
@@ -958,6 +978,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->h_other.pinned = true;
     h->h_ovl.pinned = true;
     std::memset(&h->ostats, 0, sizeof(h->ostats));
+    h->pclock.Create(PRS_STAGES + 1);
+    h->h_pers.pinned = true;
+    std::memset(&h->pstats, 0, sizeof(h->pstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -1400,201 +1423,218 @@ int vsg_render_last_boundary_stats(vsg_render* h, vsg_render_boundary_stats* s) 
   });
 }
 
+}  // extern "C"
+
+namespace {
+
+// The body of vsg_render_level_adjacency; vsg_render_persistence_graph runs it for the counts alone and
+// takes the lists from h->d_adj_nodes and h->d_adj_edges.
+void LevelAdjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                    int neighbourhood, vsg_render_level_node* nodes, size_t capacity_nodes, size_t* num_nodes,
+                    vsg_render_level_edge* edges, size_t capacity_edges, size_t* num_edges, int mem_out) {
+  using namespace vsg_render_impl;
+  static_assert(sizeof(vsg_render_level_node) == kLevelNodeWords * sizeof(int32_t), "moved as int32 words");
+  static_assert(sizeof(vsg_render_level_edge) == kLevelEdgeWords * sizeof(int32_t), "moved as int32 words");
+  if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+    Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+  }
+  if (neighbourhood != VSG_RENDER_ADJACENT_N4 && neighbourhood != VSG_RENDER_ADJACENT_N8) {
+    Throw(VSG_ERR_INVALID, "neighbourhood is neither VSG_RENDER_ADJACENT_N4 nor VSG_RENDER_ADJACENT_N8");
+  }
+  if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+  if (!num_nodes || !num_edges) Throw(VSG_ERR_INVALID, "a count pointer is null");
+  *num_nodes = *num_edges = 0;
+  CheckMem(mem_out, "outputs");
+  const bool count_only = !nodes && !edges && capacity_nodes == 0 && capacity_edges == 0;
+  const bool diagonal = neighbourhood == VSG_RENDER_ADJACENT_N8;
+  const int W = h->W, H = h->H;
+  if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+  DeviceGuard guard(h->device);
+  vsg_render_adjacency_stats& as = h->astats;
+  std::memset(&as, 0, sizeof(as));
+
+  // ---- the plane: the level's ids, or the indices of its regions' components ----
+  const int32_t* plane = nullptr;
+  const int32_t* comp_table = nullptr;
+  uint32_t max_group = 0;
+  uint64_t groups_bound = 0;   // no more groups than this
+  bool vector = false;
+  if (connectedness == 0) {
+    int32_t max_id = 0;
+    vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
+    plane = h->d_ids.As<int32_t>();
+    max_group = (uint32_t)max_id;
+    groups_bound = (uint64_t)h->stats.distinct_ids;
+    as.launches = h->stats.launches;
+  } else {
+    size_t n_components = 0, n_intervals = 0;
+    LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
+                    nullptr, VSG_MEM_DEVICE, true);
+    plane = h->d_labels.As<int32_t>();
+    comp_table = h->d_comp_table.As<int32_t>();
+    max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
+    groups_bound = n_components;
+    const vsg_render_component_stats& cs = h->cstats;
+    as.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                  cs.label_us;
+    as.launches = h->stats.launches;
+  }
+  int group_bits = 1;
+  while (group_bits < 31 && (max_group >> group_bits)) ++group_bits;
+
+  // ---- count: the number of keys sizes everything below ----
+  h->d_adj_status.Reserve(sizeof(AdjStatus), &h->allocations);
+  h->h_adj.Reserve(2 * sizeof(AdjStatus), &h->allocations);
+  AdjStatus* status = h->d_adj_status.As<AdjStatus>();
+  AdjStatus* seen = h->h_adj.As<AdjStatus>();   // [0] after the count, [1] at the end
+  std::memset(seen, 0, 2 * sizeof(AdjStatus));
+  VSG_HIP(hipMemsetAsync(status, 0, sizeof(AdjStatus), h->stream));
+  h->aclock.Begin(h->stream);
+  LaunchAdjClassify(plane, W, H, group_bits, diagonal, false, 0, nullptr, status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->aclock.Mark(ADJ_COUNT);
+  VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
+  int launches = 3;
+  VSG_HIP(hipStreamSynchronize(h->stream));
+  {
+    float us[ADJ_STAGES];
+    h->aclock.Read(us, ADJ_STAGES);
+    as.count_us = us[ADJ_COUNT];
+  }
+  if (connectedness == 0) {
+    float us[STAGE_COUNT];
+    h->clock.Read(us, STAGE_COUNT);
+    h->stats.clear_us = us[STAGE_CLEAR];
+    h->stats.fill_us = us[STAGE_FILL];
+    as.plane_us = us[STAGE_CLEAR] + us[STAGE_FILL];
+    if (vector) h->CheckVector();
+  }
+  auto finish = [&] {
+    as.launches += launches;
+    h->stats.launches += launches;
+    h->stats.device_allocations = h->allocations;
+  };
+  if (seen[0].keys > 0x7fffffffull) {
+    finish();
+    Throw(VSG_ERR_INVALID, "the level has more than 2^31 - 1 bordering sides and diagonal contacts");
+  }
+  const uint32_t n = (uint32_t)seen[0].keys;
+  as.sides = as.keys = n;
+  if (n == 0) return finish();   // no covered pixel: both lists are empty
+
+  // ---- emit, sort, table ----
+  const uint32_t cap_nodes = (uint32_t)std::min<uint64_t>(groups_bound, n);   // every group has a key
+  if (cap_nodes == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
+  const uint32_t cap_edges = n;                                               // every edge has a key
+  const int end_bit = 2 * group_bits + 2;
+  const size_t temp_bytes = std::max<size_t>(AdjTempBytes(n, end_bit), 16);
+  const size_t node_bytes = (size_t)cap_nodes * sizeof(vsg_render_level_node);
+  const size_t edge_bytes = (size_t)cap_edges * sizeof(vsg_render_level_edge);
+  h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+  h->d_adj_keys.Reserve((size_t)n * 2 * sizeof(unsigned long long), &h->allocations);
+  h->d_adj_heads.Reserve((size_t)n * sizeof(unsigned long long), &h->allocations);
+  h->d_adj_nodes.Reserve(node_bytes, &h->allocations);
+  h->d_adj_edges.Reserve(edge_bytes, &h->allocations);
+  unsigned long long* keys = h->d_adj_keys.As<unsigned long long>();
+  unsigned long long* keys_sorted = keys + n;
+  unsigned long long* heads = h->d_adj_heads.As<unsigned long long>();
+  int32_t* d_nodes = h->d_adj_nodes.As<int32_t>();
+  int32_t* d_edges = h->d_adj_edges.As<int32_t>();
+  h->aclock.Begin(h->stream);
+  LaunchAdjClassify(plane, W, H, group_bits, diagonal, true, n, keys, status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->aclock.Mark(ADJ_EMIT);
+  VSG_HIP(AdjSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
+  h->aclock.Mark(ADJ_SORT);
+  VSG_HIP(hipMemsetAsync(d_nodes, 0, node_bytes, h->stream));   // the counts are summed into them
+  VSG_HIP(hipMemsetAsync(d_edges, 0, edge_bytes, h->stream));
+  VSG_HIP(AdjRank(h->d_sort_temp.p, temp_bytes, keys_sorted, group_bits, heads, n, h->stream));
+  LaunchAdjTable(keys_sorted, heads, n, group_bits, max_group, cap_nodes, cap_edges, comp_table, d_nodes, d_edges,
+                 status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->aclock.Mark(ADJ_TABLE);
+  // emit, the sort and the scan counted as one each, two clears, table, finish, resolve
+  launches += 7 + (comp_table ? 0 : 1);
+  const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && nodes && edges;
+  if (to_device) {
+    // the lengths of both lists are on the device: the copy decides there whether they fit
+    LaunchAdjCopy(d_nodes, d_edges, (uint32_t)std::min<size_t>(capacity_nodes, cap_nodes),
+                  (uint32_t)std::min<size_t>(capacity_edges, cap_edges), reinterpret_cast<int32_t*>(nodes),
+                  reinterpret_cast<int32_t*>(edges), status, h->stream);
+    VSG_HIP(hipGetLastError());
+    ++launches;
+  }
+  VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
+  ++launches;
+  VSG_HIP(hipStreamSynchronize(h->stream));
+  {
+    float us[ADJ_STAGES];
+    h->aclock.Read(us, ADJ_STAGES);
+    as.emit_us = us[ADJ_EMIT];
+    as.sort_us = us[ADJ_SORT];
+    as.table_us = us[ADJ_TABLE];
+  }
+  if ((seen[1].flags & ADJ_FLAG_OVERFLOW) || seen[1].emitted != n) {
+    finish();
+    Throw(VSG_ERR_INTERNAL, "the emit pass found other adjacency keys than the count pass");
+  }
+  if ((seen[1].flags & ADJ_FLAG_RANGE) || seen[1].nodes == 0 || seen[1].nodes > cap_nodes ||
+      seen[1].edges > cap_edges || (comp_table && seen[1].nodes != groups_bound)) {
+    finish();
+    Throw(VSG_ERR_INTERNAL, "a sorted adjacency key, a node or an edge is out of range");
+  }
+  const size_t n_nodes = seen[1].nodes, n_edges = seen[1].edges;
+  *num_nodes = n_nodes;
+  *num_edges = n_edges;
+  as.nodes = (int64_t)n_nodes;
+  as.edges = (int64_t)n_edges;
+  as.largest_node_edges = seen[1].largest;
+  if (count_only) return finish();
+  if (n_nodes > capacity_nodes || n_edges > capacity_edges) {
+    finish();
+    Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_nodes) + " nodes and " + std::to_string(n_edges) +
+                               " edges, the capacities are " + std::to_string(capacity_nodes) + " and " +
+                               std::to_string(capacity_edges));
+  }
+  if (!nodes || (n_edges && !edges)) {
+    finish();
+    Throw(VSG_ERR_INVALID, "an output is null");
+  }
+  if (mem_out == VSG_MEM_HOST) {
+    // through the pinned block, now that the lengths are known
+    const size_t nb = n_nodes * sizeof(vsg_render_level_node), eb = n_edges * sizeof(vsg_render_level_edge);
+    h->h_adj.Reserve(2 * sizeof(AdjStatus) + nb + eb, &h->allocations);
+    char* stage = reinterpret_cast<char*>(h->h_adj.As<AdjStatus>() + 2);
+    VSG_HIP(hipMemcpyAsync(stage, d_nodes, nb, hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    if (eb) {
+      VSG_HIP(hipMemcpyAsync(stage + nb, d_edges, eb, hipMemcpyDeviceToHost, h->stream));
+      ++launches;
+    }
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    std::memcpy(nodes, stage, nb);
+    if (eb) std::memcpy(edges, stage + nb, eb);
+  } else if (!to_device) {
+    // edges was null with no edge to deliver: the copy kernel was not launched
+    VSG_HIP(hipMemcpyAsync(nodes, d_nodes, n_nodes * sizeof(vsg_render_level_node), hipMemcpyDeviceToDevice,
+                           h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+  }
+  finish();
+}
+
+}  // namespace
+
+extern "C" {
+
 int vsg_render_level_adjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
                                int neighbourhood, vsg_render_level_node* nodes, size_t capacity_nodes,
                                size_t* num_nodes, vsg_render_level_edge* edges, size_t capacity_edges,
                                size_t* num_edges, int mem_out) {
   return Guard([&] {
-    using namespace vsg_render_impl;
-    static_assert(sizeof(vsg_render_level_node) == kLevelNodeWords * sizeof(int32_t), "moved as int32 words");
-    static_assert(sizeof(vsg_render_level_edge) == kLevelEdgeWords * sizeof(int32_t), "moved as int32 words");
-    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
-      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
-    }
-    if (neighbourhood != VSG_RENDER_ADJACENT_N4 && neighbourhood != VSG_RENDER_ADJACENT_N8) {
-      Throw(VSG_ERR_INVALID, "neighbourhood is neither VSG_RENDER_ADJACENT_N4 nor VSG_RENDER_ADJACENT_N8");
-    }
-    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
-    if (!num_nodes || !num_edges) Throw(VSG_ERR_INVALID, "a count pointer is null");
-    *num_nodes = *num_edges = 0;
-    CheckMem(mem_out, "outputs");
-    const bool count_only = !nodes && !edges && capacity_nodes == 0 && capacity_edges == 0;
-    const bool diagonal = neighbourhood == VSG_RENDER_ADJACENT_N8;
-    const int W = h->W, H = h->H;
-    if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
-    DeviceGuard guard(h->device);
-    vsg_render_adjacency_stats& as = h->astats;
-    std::memset(&as, 0, sizeof(as));
-
-    // ---- the plane: the level's ids, or the indices of its regions' components ----
-    const int32_t* plane = nullptr;
-    const int32_t* comp_table = nullptr;
-    uint32_t max_group = 0;
-    uint64_t groups_bound = 0;   // no more groups than this
-    bool vector = false;
-    if (connectedness == 0) {
-      int32_t max_id = 0;
-      vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
-      plane = h->d_ids.As<int32_t>();
-      max_group = (uint32_t)max_id;
-      groups_bound = (uint64_t)h->stats.distinct_ids;
-      as.launches = h->stats.launches;
-    } else {
-      size_t n_components = 0, n_intervals = 0;
-      LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
-                      nullptr, VSG_MEM_DEVICE, true);
-      plane = h->d_labels.As<int32_t>();
-      comp_table = h->d_comp_table.As<int32_t>();
-      max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
-      groups_bound = n_components;
-      const vsg_render_component_stats& cs = h->cstats;
-      as.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
-                    cs.label_us;
-      as.launches = h->stats.launches;
-    }
-    int group_bits = 1;
-    while (group_bits < 31 && (max_group >> group_bits)) ++group_bits;
-
-    // ---- count: the number of keys sizes everything below ----
-    h->d_adj_status.Reserve(sizeof(AdjStatus), &h->allocations);
-    h->h_adj.Reserve(2 * sizeof(AdjStatus), &h->allocations);
-    AdjStatus* status = h->d_adj_status.As<AdjStatus>();
-    AdjStatus* seen = h->h_adj.As<AdjStatus>();   // [0] after the count, [1] at the end
-    std::memset(seen, 0, 2 * sizeof(AdjStatus));
-    VSG_HIP(hipMemsetAsync(status, 0, sizeof(AdjStatus), h->stream));
-    h->aclock.Begin(h->stream);
-    LaunchAdjClassify(plane, W, H, group_bits, diagonal, false, 0, nullptr, status, h->stream);
-    VSG_HIP(hipGetLastError());
-    h->aclock.Mark(ADJ_COUNT);
-    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
-    int launches = 3;
-    VSG_HIP(hipStreamSynchronize(h->stream));
-    {
-      float us[ADJ_STAGES];
-      h->aclock.Read(us, ADJ_STAGES);
-      as.count_us = us[ADJ_COUNT];
-    }
-    if (connectedness == 0) {
-      float us[STAGE_COUNT];
-      h->clock.Read(us, STAGE_COUNT);
-      h->stats.clear_us = us[STAGE_CLEAR];
-      h->stats.fill_us = us[STAGE_FILL];
-      as.plane_us = us[STAGE_CLEAR] + us[STAGE_FILL];
-      if (vector) h->CheckVector();
-    }
-    auto finish = [&] {
-      as.launches += launches;
-      h->stats.launches += launches;
-      h->stats.device_allocations = h->allocations;
-    };
-    if (seen[0].keys > 0x7fffffffull) {
-      finish();
-      Throw(VSG_ERR_INVALID, "the level has more than 2^31 - 1 bordering sides and diagonal contacts");
-    }
-    const uint32_t n = (uint32_t)seen[0].keys;
-    as.sides = as.keys = n;
-    if (n == 0) return finish();   // no covered pixel: both lists are empty
-
-    // ---- emit, sort, table ----
-    const uint32_t cap_nodes = (uint32_t)std::min<uint64_t>(groups_bound, n);   // every group has a key
-    if (cap_nodes == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
-    const uint32_t cap_edges = n;                                               // every edge has a key
-    const int end_bit = 2 * group_bits + 2;
-    const size_t temp_bytes = std::max<size_t>(AdjTempBytes(n, end_bit), 16);
-    const size_t node_bytes = (size_t)cap_nodes * sizeof(vsg_render_level_node);
-    const size_t edge_bytes = (size_t)cap_edges * sizeof(vsg_render_level_edge);
-    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
-    h->d_adj_keys.Reserve((size_t)n * 2 * sizeof(unsigned long long), &h->allocations);
-    h->d_adj_heads.Reserve((size_t)n * sizeof(unsigned long long), &h->allocations);
-    h->d_adj_nodes.Reserve(node_bytes, &h->allocations);
-    h->d_adj_edges.Reserve(edge_bytes, &h->allocations);
-    unsigned long long* keys = h->d_adj_keys.As<unsigned long long>();
-    unsigned long long* keys_sorted = keys + n;
-    unsigned long long* heads = h->d_adj_heads.As<unsigned long long>();
-    int32_t* d_nodes = h->d_adj_nodes.As<int32_t>();
-    int32_t* d_edges = h->d_adj_edges.As<int32_t>();
-    h->aclock.Begin(h->stream);
-    LaunchAdjClassify(plane, W, H, group_bits, diagonal, true, n, keys, status, h->stream);
-    VSG_HIP(hipGetLastError());
-    h->aclock.Mark(ADJ_EMIT);
-    VSG_HIP(AdjSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
-    h->aclock.Mark(ADJ_SORT);
-    VSG_HIP(hipMemsetAsync(d_nodes, 0, node_bytes, h->stream));   // the counts are summed into them
-    VSG_HIP(hipMemsetAsync(d_edges, 0, edge_bytes, h->stream));
-    VSG_HIP(AdjRank(h->d_sort_temp.p, temp_bytes, keys_sorted, group_bits, heads, n, h->stream));
-    LaunchAdjTable(keys_sorted, heads, n, group_bits, max_group, cap_nodes, cap_edges, comp_table, d_nodes, d_edges,
-                   status, h->stream);
-    VSG_HIP(hipGetLastError());
-    h->aclock.Mark(ADJ_TABLE);
-    // emit, the sort and the scan counted as one each, two clears, table, finish, resolve
-    launches += 7 + (comp_table ? 0 : 1);
-    const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && nodes && edges;
-    if (to_device) {
-      // the lengths of both lists are on the device: the copy decides there whether they fit
-      LaunchAdjCopy(d_nodes, d_edges, (uint32_t)std::min<size_t>(capacity_nodes, cap_nodes),
-                    (uint32_t)std::min<size_t>(capacity_edges, cap_edges), reinterpret_cast<int32_t*>(nodes),
-                    reinterpret_cast<int32_t*>(edges), status, h->stream);
-      VSG_HIP(hipGetLastError());
-      ++launches;
-    }
-    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(AdjStatus), hipMemcpyDeviceToHost, h->stream));
-    ++launches;
-    VSG_HIP(hipStreamSynchronize(h->stream));
-    {
-      float us[ADJ_STAGES];
-      h->aclock.Read(us, ADJ_STAGES);
-      as.emit_us = us[ADJ_EMIT];
-      as.sort_us = us[ADJ_SORT];
-      as.table_us = us[ADJ_TABLE];
-    }
-    if ((seen[1].flags & ADJ_FLAG_OVERFLOW) || seen[1].emitted != n) {
-      finish();
-      Throw(VSG_ERR_INTERNAL, "the emit pass found other adjacency keys than the count pass");
-    }
-    if ((seen[1].flags & ADJ_FLAG_RANGE) || seen[1].nodes == 0 || seen[1].nodes > cap_nodes ||
-        seen[1].edges > cap_edges || (comp_table && seen[1].nodes != groups_bound)) {
-      finish();
-      Throw(VSG_ERR_INTERNAL, "a sorted adjacency key, a node or an edge is out of range");
-    }
-    const size_t n_nodes = seen[1].nodes, n_edges = seen[1].edges;
-    *num_nodes = n_nodes;
-    *num_edges = n_edges;
-    as.nodes = (int64_t)n_nodes;
-    as.edges = (int64_t)n_edges;
-    as.largest_node_edges = seen[1].largest;
-    if (count_only) return finish();
-    if (n_nodes > capacity_nodes || n_edges > capacity_edges) {
-      finish();
-      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_nodes) + " nodes and " + std::to_string(n_edges) +
-                                 " edges, the capacities are " + std::to_string(capacity_nodes) + " and " +
-                                 std::to_string(capacity_edges));
-    }
-    if (!nodes || (n_edges && !edges)) {
-      finish();
-      Throw(VSG_ERR_INVALID, "an output is null");
-    }
-    if (mem_out == VSG_MEM_HOST) {
-      // through the pinned block, now that the lengths are known
-      const size_t nb = n_nodes * sizeof(vsg_render_level_node), eb = n_edges * sizeof(vsg_render_level_edge);
-      h->h_adj.Reserve(2 * sizeof(AdjStatus) + nb + eb, &h->allocations);
-      char* stage = reinterpret_cast<char*>(h->h_adj.As<AdjStatus>() + 2);
-      VSG_HIP(hipMemcpyAsync(stage, d_nodes, nb, hipMemcpyDeviceToHost, h->stream));
-      ++launches;
-      if (eb) {
-        VSG_HIP(hipMemcpyAsync(stage + nb, d_edges, eb, hipMemcpyDeviceToHost, h->stream));
-        ++launches;
-      }
-      VSG_HIP(hipStreamSynchronize(h->stream));
-      std::memcpy(nodes, stage, nb);
-      if (eb) std::memcpy(edges, stage + nb, eb);
-    } else if (!to_device) {
-      // edges was null with no edge to deliver: the copy kernel was not launched
-      VSG_HIP(hipMemcpyAsync(nodes, d_nodes, n_nodes * sizeof(vsg_render_level_node), hipMemcpyDeviceToDevice,
-                             h->stream));
-      ++launches;
-      VSG_HIP(hipStreamSynchronize(h->stream));
-    }
-    finish();
+    LevelAdjacency(h, seg, seg_len, level, connectedness, neighbourhood, nodes, capacity_nodes, num_nodes, edges,
+                   capacity_edges, num_edges, mem_out);
   });
 }
 
@@ -1869,6 +1909,338 @@ int vsg_render_last_overlap_stats(vsg_render* h, vsg_render_overlap_stats* s) {
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->ostats;
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// The hierarchy's height and the ancestor table of h->pers_ids in h->pers_table, or the refusals of
+// vsg_render_id_image at the top level.  Host work only.
+int BuildPersistenceTable(vsg_render* h) {
+  const size_t L = vsg_render_impl::PersistenceHeight(h->kept.size());
+  if (L > 65535) Throw(VSG_ERR_INVALID, "the hierarchy has " + std::to_string(L) + " levels, more than 65535");
+  if (h->pers_ids.size() > (1u << 30)) Throw(VSG_ERR_INVALID, "too many regions");
+  int bad_level = 0;
+  int32_t bad_id = 0;
+  if (!vsg_render_impl::BuildAncestorTable(h->kept, h->pers_ids.data(), h->pers_ids.size(), &h->pers_table,
+                                           &bad_level, &bad_id)) {
+    Throw(VSG_ERR_INVALID,
+          "region " + std::to_string(bad_id) + " is not in hierarchy level " + std::to_string(bad_level));
+  }
+  return (int)L;
+}
+
+// Region ids, then the table's rows, to h->d_anc in one copy on the stream; returns the table (null
+// when there is none: one level, or no region).  The pinned block gets room for at least pinned_bytes, what
+// the call reads back through it later: it must not grow while the copy is in flight.
+const int32_t* UploadPersistenceTable(vsg_render* h, size_t pinned_bytes, int* launches) {
+  const size_t n = h->pers_ids.size() + h->pers_table.size();
+  h->d_anc.Reserve(std::max<size_t>(n, 1) * sizeof(int32_t), &h->allocations);
+  h->h_pers.Reserve(std::max(n * sizeof(int32_t), pinned_bytes), &h->allocations);
+  if (n == 0) return nullptr;
+  int32_t* stage = h->h_pers.As<int32_t>();
+  std::copy(h->pers_ids.begin(), h->pers_ids.end(), stage);
+  std::copy(h->pers_table.begin(), h->pers_table.end(), stage + h->pers_ids.size());
+  VSG_HIP(hipMemcpyAsync(h->d_anc.p, stage, n * sizeof(int32_t), hipMemcpyHostToDevice, h->stream));
+  ++*launches;
+  return h->pers_table.empty() ? nullptr : h->d_anc.As<int32_t>() + h->pers_ids.size();
+}
+
+// The front half of the image and the frame call: the level-0 plane in h->d_plane painted with a dense
+// number per distinct region id (so that sparse ids cost nothing), the ancestor table on the device, and
+// Q written to q.  Leaves pclock after PRS_PERSIST and the status in flight.  Returns whether the desc was
+// vector-only; *levels = L.
+bool PaintPersistence(vsg_render* h, const uint8_t* seg, size_t seg_len, int32_t* q, size_t q_pitch, int* levels,
+                      int* launches) {
+  const int W = h->W, H = h->H;
+  vsg_render_persistence_stats& ps = h->pstats;
+  h->pers_ids.clear();
+  int L = 1;
+  uint32_t* plane = h->d_plane.As<uint32_t>();
+  const bool vector = PaintIdsAt(
+      h, seg, seg_len, 0, plane, h->pitch,
+      [&](int mapped) {
+        if (mapped < 0) Throw(VSG_ERR_INVALID, "region id " + std::to_string(mapped) + " is negative");
+        h->pers_ids.push_back(mapped);
+        return (uint32_t)(h->pers_ids.size() - 1);
+      },
+      [&] { L = BuildPersistenceTable(h); });
+  *levels = L;
+  ps.levels = L;
+  ps.regions = (int64_t)h->pers_ids.size();
+  const int32_t* table = UploadPersistenceTable(h, sizeof(PersStatus), launches);
+  h->d_pers_status.Reserve(sizeof(PersStatus), &h->allocations);
+  PersStatus* status = h->d_pers_status.As<PersStatus>();
+  VSG_HIP(hipMemsetAsync(status, 0, sizeof(PersStatus), h->stream));
+  h->pclock.Begin(h->stream);
+  vsg_render_impl::LaunchPersistPlane(reinterpret_cast<const int32_t*>(plane), h->pitch, W, H, table,
+                                      (uint32_t)h->pers_ids.size(), L, q, q_pitch, status, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->pclock.Mark(PRS_PERSIST);
+  *launches += 2;
+  return vector;
+}
+
+// The back half: the status back, the one synchronisation, the stats, the device's flag.
+void FinishPersistence(vsg_render* h, bool vector, int launches) {
+  vsg_render_persistence_stats& ps = h->pstats;
+  // the table went through the pinned block before the plane kernel ran; the status may follow it
+  PersStatus* seen = h->h_pers.As<PersStatus>();
+  VSG_HIP(hipMemcpyAsync(seen, h->d_pers_status.p, sizeof(PersStatus), hipMemcpyDeviceToHost, h->stream));
+  ++launches;
+  h->FinishStats();
+  float us[PRS_STAGES];
+  h->pclock.Read(us, PRS_STAGES);
+  ps.plane_us = h->stats.clear_us + h->stats.fill_us;
+  ps.persist_us = us[PRS_PERSIST];
+  ps.compose_us = us[PRS_COMPOSE];
+  h->stats.launches += launches;
+  ps.launches = h->stats.launches;
+  if (vector) h->CheckVector();
+  if (seen->flags) Throw(VSG_ERR_INTERNAL, "the plane holds a region number the host did not give out");
+  ps.edge_pixels = (int64_t)seen->edge_pixels;
+  ps.top_pixels = (int64_t)seen->top_pixels;
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsg_render_persistence_image(vsg_render* h, const uint8_t* seg, size_t seg_len, int32_t* out, int* num_levels,
+                                 int mem_out) {
+  return Guard([&] {
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    if (!num_levels) Throw(VSG_ERR_INVALID, "the count pointer is null");
+    CheckMem(mem_out, "out");
+    *num_levels = 0;
+    const int W = h->W, H = h->H;
+    const size_t bytes = (size_t)W * H * sizeof(int32_t);
+    DeviceGuard guard(h->device);
+    std::memset(&h->pstats, 0, sizeof(h->pstats));
+    int32_t* q = out;   // device output: written in place
+    if (mem_out == VSG_MEM_HOST) {
+      h->d_pq.Reserve(bytes, &h->allocations);
+      q = h->d_pq.As<int32_t>();
+    }
+    int launches = 0, levels = 0;
+    const bool vector = PaintPersistence(h, seg, seg_len, q, (size_t)W, &levels, &launches);
+    if (mem_out == VSG_MEM_HOST) {
+      VSG_HIP(hipMemcpyAsync(out, q, bytes, hipMemcpyDeviceToHost, h->stream));
+      ++launches;
+    }
+    FinishPersistence(h, vector, launches);
+    *num_levels = levels;
+  });
+}
+
+int vsg_render_persistence_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, const uint8_t* bgr, size_t stride,
+                                 int mem_in, uint8_t* out, size_t out_stride, int mem_out, int* num_levels) {
+  return Guard([&] {
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    if (!num_levels) Throw(VSG_ERR_INVALID, "the count pointer is null");
+    CheckMem(mem_in, "bgr");
+    CheckMem(mem_out, "out");
+    *num_levels = 0;
+    const int W = h->W, H = h->H;
+    const size_t row_bytes = (size_t)W * 3;
+    const bool video = h->opt.has_video != 0;
+    if (video && !bgr) Throw(VSG_ERR_INVALID, "the handle was created with has_video: bgr is null");
+    if (video && stride < row_bytes) Throw(VSG_ERR_INVALID, "stride is smaller than 3 * width");
+    if (out_stride == 0) out_stride = vsg_render_default_stride(W);
+    if (out_stride < row_bytes) Throw(VSG_ERR_INVALID, "out_stride is smaller than 3 * width");
+    DeviceGuard guard(h->device);
+    std::memset(&h->pstats, 0, sizeof(h->pstats));
+    // Q has the plane's pitch: every tile row of it is 16-byte aligned
+    h->d_pq.Reserve((size_t)h->pitch * H * sizeof(int32_t), &h->allocations);
+    int32_t* q = h->d_pq.As<int32_t>();
+    int launches = 0, levels = 0;
+    const bool vector = PaintPersistence(h, seg, seg_len, q, (size_t)h->pitch, &levels, &launches);
+    const uint8_t* src = nullptr;
+    size_t src_stride = 0;
+    if (video) {
+      if (mem_in == VSG_MEM_DEVICE) {
+        src = bgr;
+        src_stride = stride;
+      } else {
+        src_stride = vsg_render_default_stride(W);
+        h->d_src.Reserve(src_stride * H, &h->allocations);
+        VSG_HIP(hipMemcpy2DAsync(h->d_src.p, src_stride, bgr, stride, row_bytes, H, hipMemcpyHostToDevice,
+                                 h->stream));
+        ++launches;
+        src = static_cast<const uint8_t*>(h->d_src.p);
+      }
+    }
+    uint8_t* dst = out;
+    size_t dst_stride = out_stride;
+    if (mem_out == VSG_MEM_HOST) {
+      dst_stride = vsg_render_default_stride(W);
+      h->d_out.Reserve(dst_stride * H, &h->allocations);
+      dst = static_cast<uint8_t*>(h->d_out.p);
+    }
+    h->pclock.Mark(PRS_WAIT);
+    vsg_render_impl::LaunchPersistCompose(q, (size_t)h->pitch, W, H, levels, src, src_stride, dst, dst_stride,
+                                          h->stream);
+    VSG_HIP(hipGetLastError());
+    h->pclock.Mark(PRS_COMPOSE);
+    ++launches;
+    if (mem_out == VSG_MEM_HOST) {
+      VSG_HIP(hipMemcpy2DAsync(out, out_stride, dst, dst_stride, row_bytes, H, hipMemcpyDeviceToHost, h->stream));
+      ++launches;
+    }
+    FinishPersistence(h, vector, launches);
+    *num_levels = levels;
+  });
+}
+
+int vsg_render_persistence_graph(vsg_render* h, const uint8_t* seg, size_t seg_len, int neighbourhood,
+                                 vsg_render_level_node* nodes, size_t capacity_nodes, size_t* num_nodes,
+                                 vsg_render_level_edge* edges, size_t capacity_edges, size_t* num_edges,
+                                 int32_t* persistence, int64_t* level_sides, size_t capacity_levels,
+                                 size_t* num_levels, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    if (neighbourhood != VSG_RENDER_ADJACENT_N4 && neighbourhood != VSG_RENDER_ADJACENT_N8) {
+      Throw(VSG_ERR_INVALID, "neighbourhood is neither VSG_RENDER_ADJACENT_N4 nor VSG_RENDER_ADJACENT_N8");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_nodes || !num_edges || !num_levels) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_nodes = *num_edges = *num_levels = 0;
+    CheckMem(mem_out, "outputs");
+    const bool count_only = !nodes && !edges && !persistence && !level_sides && capacity_nodes == 0 &&
+                            capacity_edges == 0 && capacity_levels == 0;
+    DeviceGuard guard(h->device);
+    vsg_render_persistence_stats& ps = h->pstats;
+    std::memset(&ps, 0, sizeof(ps));
+
+    // ---- the level-0 graph, left on the device ----
+    size_t n_nodes = 0, n_edges = 0;
+    LevelAdjacency(h, seg, seg_len, 0, 0, neighbourhood, nullptr, 0, &n_nodes, nullptr, 0, &n_edges, VSG_MEM_DEVICE);
+    const vsg_render_adjacency_stats& as = h->astats;
+    ps.nodes = (int64_t)n_nodes;
+    ps.edges = (int64_t)n_edges;
+    ps.plane_us = as.plane_us;
+    ps.graph_us = as.count_us + as.emit_us + as.sort_us + as.table_us;
+    int launches = 0;
+    auto finish = [&] {
+      h->stats.launches += launches;
+      ps.launches = h->stats.launches;
+      h->stats.device_allocations = h->allocations;
+    };
+
+    // ---- the ancestors of every region that paints, by ascending id ----
+    const ParsedDesc& d = h->desc;
+    const bool vector = d.rasterization_removed && d.has_mesh;
+    h->pers_ids.clear();
+    for (size_t r = 0; r < d.region_ids.size(); ++r) {
+      const bool paints = vector ? d.region_poly_begin[r] != d.region_poly_begin[r + 1]
+                                 : d.region_begin[r] != d.region_begin[r + 1];
+      if (paints) h->pers_ids.push_back(d.region_ids[r]);   // none is negative: the adjacency call refused those
+    }
+    std::sort(h->pers_ids.begin(), h->pers_ids.end());
+    h->pers_ids.erase(std::unique(h->pers_ids.begin(), h->pers_ids.end()), h->pers_ids.end());
+    int L = 1;
+    try {
+      L = BuildPersistenceTable(h);
+    } catch (...) {
+      finish();
+      throw;
+    }
+    ps.levels = L;
+    ps.regions = (int64_t)h->pers_ids.size();
+    *num_nodes = n_nodes;
+    *num_edges = n_edges;
+    *num_levels = (size_t)L;
+
+    // ---- one thread per edge, then the levels' sums ----
+    const size_t hist_bytes = ((size_t)L + 1) * sizeof(unsigned long long);
+    const size_t sides_bytes = (size_t)L * sizeof(int64_t);
+    const size_t pers_bytes = n_edges * sizeof(int32_t);
+    h->d_pers_out.Reserve(hist_bytes + sides_bytes + pers_bytes, &h->allocations);
+    h->d_pers_status.Reserve(sizeof(PersStatus), &h->allocations);
+    unsigned long long* hist = h->d_pers_out.As<unsigned long long>();
+    long long* d_sides = reinterpret_cast<long long*>(hist + L + 1);
+    int32_t* d_pers = reinterpret_cast<int32_t*>(d_sides + L);
+    PersStatus* status = h->d_pers_status.As<PersStatus>();
+    // the table has left the pinned block by the time the status and the lists arrive in it
+    const size_t nb = n_nodes * sizeof(vsg_render_level_node), eb = n_edges * sizeof(vsg_render_level_edge);
+    const bool fits = n_nodes <= capacity_nodes && n_edges <= capacity_edges && (size_t)L <= capacity_levels;
+    const bool have = (n_nodes == 0 || nodes) && level_sides && (n_edges == 0 || (edges && persistence));
+    const bool to_host = !count_only && fits && have && mem_out == VSG_MEM_HOST;
+    const int32_t* table = UploadPersistenceTable(
+        h, sizeof(PersStatus) + (to_host ? sides_bytes + nb + eb + pers_bytes : 0), &launches);
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(PersStatus), h->stream));
+    VSG_HIP(hipMemsetAsync(hist, 0, hist_bytes, h->stream));
+    h->pclock.Begin(h->stream);
+    LaunchPersistEdges(h->d_adj_nodes.As<int32_t>(), (uint32_t)n_nodes, h->d_adj_edges.As<int32_t>(),
+                       (uint32_t)n_edges, h->d_anc.As<int32_t>(), (uint32_t)h->pers_ids.size(), table, L, d_pers, hist,
+                       status, h->stream);
+    LaunchPersistSides(hist, L, d_sides, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->pclock.Mark(PRS_PERSIST);
+    launches += 3 + (n_edges ? 1 : 0);
+    char* stage = h->h_pers.As<char>();
+    VSG_HIP(hipMemcpyAsync(stage, status, sizeof(PersStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[PRS_STAGES];
+      h->pclock.Read(us, PRS_STAGES);
+      ps.persist_us = us[PRS_PERSIST];
+    }
+    if (reinterpret_cast<const PersStatus*>(stage)->flags) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "an edge of the level-0 graph, its node or a region id is out of range");
+    }
+    if (count_only) return finish();
+    if (!fits) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the graph has " + std::to_string(n_nodes) + " nodes and " + std::to_string(n_edges) +
+                                 " edges, the hierarchy " + std::to_string(L) + " levels; the capacities are " +
+                                 std::to_string(capacity_nodes) + ", " + std::to_string(capacity_edges) + " and " +
+                                 std::to_string(capacity_levels));
+    }
+    if (!have) {
+      finish();
+      Throw(VSG_ERR_INVALID, "an output is null");
+    }
+    // the lengths are known: four copies, through the pinned block for host outputs
+    struct Part {
+      void* to;
+      const void* from;
+      size_t bytes;
+    };
+    const Part parts[4] = {{level_sides, d_sides, sides_bytes},
+                           {nodes, h->d_adj_nodes.p, nb},
+                           {edges, h->d_adj_edges.p, eb},
+                           {persistence, d_pers, pers_bytes}};
+    char* at = stage + sizeof(PersStatus);
+    for (const Part& part : parts) {
+      if (!part.bytes) continue;
+      if (to_host) VSG_HIP(hipMemcpyAsync(at, part.from, part.bytes, hipMemcpyDeviceToHost, h->stream));
+      else VSG_HIP(hipMemcpyAsync(part.to, part.from, part.bytes, hipMemcpyDeviceToDevice, h->stream));
+      at += part.bytes;
+      ++launches;
+    }
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    if (to_host) {
+      at = stage + sizeof(PersStatus);
+      for (const Part& part : parts) {
+        if (part.bytes) std::memcpy(part.to, at, part.bytes);
+        at += part.bytes;
+      }
+    }
+    finish();
+  });
+}
+
+int vsg_render_last_persistence_stats(vsg_render* h, vsg_render_persistence_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->pstats;
   });
 }
 
