@@ -50,6 +50,9 @@
  * map they are functions of is: vsg_render_persistence_image, vsg_render_persistence_frame and
  * vsg_render_persistence_graph return, for every pixel side and for every pair of touching level-0
  * regions, the number of hierarchy levels at which the two sides are still different regions.
+ * Appearance descriptors (Lab histograms, the hierarchical stage's) are not offered; the exact colour sums
+ * of every group of a level and the mean-colour picture are: vsg_render_level_colors and
+ * vsg_render_mean_frame.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -580,6 +583,86 @@ typedef struct vsg_render_persistence_stats {
   int launches;
 } vsg_render_persistence_stats;
 int vsg_render_last_persistence_stats(vsg_render* h, vsg_render_persistence_stats* s);
+
+/* ---- Level colours: per-group colour sums and the mean-colour picture ----
+ *
+ * One record of the colour table, as vsg_render_level_colors returns it. */
+typedef struct vsg_render_level_color {   /* 72 bytes, no padding */
+  int32_t id;            /* region id at `level` */
+  int32_t component;     /* index among its region's components; -1 with connectedness 0 */
+  int32_t area;          /* pixels of the group */
+  uint8_t mean[3];       /* B, G, R: (2 * sum[c] + area) / (2 * area), integer division */
+  uint8_t reserved0;     /* written as 0 */
+  int64_t sum[3];        /* B, G, R over the group's pixels */
+  int64_t sum_sq[3];     /* squares of the same bytes */
+  uint8_t min[3], max[3];
+  uint8_t reserved1[2];  /* written as 0 */
+} vsg_render_level_color;
+
+/* What every group of hierarchy level `level` looks like in the frame: the sums, the sums of squares, the
+ * minima and the maxima of the three 8-bit channels over the group's pixels, and the picture of the level
+ * painted in mean colours.  Computed on the device, in integers throughout: there are no floats, no colour
+ * conversion and no histogram in it.
+ *
+ * The planes.  P is the plane of vsg_render_level_overlap: the id plane of vsg_render_id_image at `level`
+ * for connectedness 0, or the label image of vsg_render_level_components for VSG_RENDER_CONNECT_N4 / _N8
+ * (that call is made internally: vsg_render_last_component_stats then describes it).  F is `bgr`: H rows
+ * of `stride` bytes of BGR24 in mem_in memory, host or device, independent of mem_out.  Only the first
+ * 3 * W bytes of a row are read; a stride below 3 * W is VSG_ERR_INVALID.  F is required whatever the
+ * handle's has_video.  It is read once per call; a host frame is copied to the device first, as in
+ * vsg_render_frame.
+ *
+ * The table.  One record per group of P, in the order of the sibling calls: record k belongs to record k of
+ * vsg_render_level_regions for connectedness 0, of vsg_render_level_components otherwise, with the same id,
+ * component and area.  Pixels with P < 0 enter no record.  sum[c], sum_sq[c], min[c] and max[c] are over
+ * the bytes F(x, y)[c] of the group's pixels, c = 0, 1, 2 being B, G, R.  mean[c] is sum[c] / area rounded
+ * half up, in integers: (2 * sum[c] + area) / (2 * area).  Nothing else is derived on the device: the
+ * variance of a channel is sum_sq / area - (sum / area)^2, left to the caller.
+ *
+ * The picture.  C(x, y) is the packed mean (B | G << 8 | R << 16) of the group at (x, y), and 0 (black)
+ * where P < 0, exactly as the cleared plane of vsg_render_frame.  vsg_render_mean_frame writes what
+ * vsg_render_frame makes of that colour plane with the handle's own options: the edge rule on colours
+ * (highlight_edges: a pixel is black where its colour differs from its in-frame right or below neighbour's,
+ * so two touching groups with equal means show no edge between them, and a group whose mean is black shows
+ * none against uncovered pixels), the blend with blend_alpha (forced to 1 without has_video),
+ * concat_with_source, out_stride 0 = vsg_render_default_stride, and only the first 3 * W bytes of each
+ * output row written.  The picture is made by the two kernels of vsg_render_frame, unchanged.  The call
+ * neither resolves nor changes the level the handle keeps for vsg_render_frame (vsg_render_level).
+ *
+ * Decode, hierarchy rules (the desc's own hierarchy replaces the kept one), level refusals, the
+ * non-negative ids and the handling of vector-only descs are those of vsg_render_level_regions.
+ * *num_colors is always set on VSG_OK and when the capacity is too small; in that case the call fails with
+ * VSG_ERR_INVALID and nothing is written.  colors == NULL with capacity 0 asks for the count only (VSG_OK;
+ * needs the device).  A null handle, a null count pointer, a null bgr, a null out, a memory kind other than
+ * the two, or a connectedness other than 0, VSG_RENDER_CONNECT_N4 and VSG_RENDER_CONNECT_N8 is
+ * VSG_ERR_INVALID, answered before the handle is dereferenced, and touches no device.  The stride is the
+ * exception: it is compared with the handle's width, so it is answered after the handle is read.  A frame
+ * with no covered pixel returns zero records, and a picture that is black before the blend.  The table in
+ * mem_out memory. */
+int vsg_render_level_colors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                            const uint8_t* bgr, size_t stride, int mem_in,
+                            vsg_render_level_color* colors, size_t capacity_colors, size_t* num_colors,
+                            int mem_out);
+
+int vsg_render_mean_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          const uint8_t* bgr, size_t stride, int mem_in,
+                          uint8_t* out, size_t out_stride, int mem_out);
+
+/* What the last vsg_render_level_colors or vsg_render_mean_frame call of the handle did.  groups: the
+ * records.  intervals: the maximal runs of P, the entries of the interval list.  covered: pixels with
+ * P >= 0, the sum of the areas.  largest_group_intervals: most intervals of one group.  Device times are
+ * HIP events around the stages: plane_us, everything that makes the interval list (the id plane's clear and
+ * fill, the runs, the sort and the table; with a connectedness, every stage of the internal
+ * vsg_render_level_components call) and bringing a host F to the device; sums_us, k_color_runs; table_us,
+ * the clear, k_color_table and k_color_finish; paint_us (vsg_render_mean_frame), k_color_intervals, the
+ * plane's clear, k_render_fill and k_render_compose.  launches does not depend on H, on the number of
+ * groups or on the number of intervals. */
+typedef struct vsg_render_color_stats {
+  int64_t groups, intervals, covered, largest_group_intervals;
+  float plane_us, sums_us, table_us, paint_us;
+  int launches;
+} vsg_render_color_stats;                 /* 56 bytes with the tail padding */
+int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -44,6 +44,12 @@
 // persistence_levels=<L of the last frame> persistence_edge_pixels=<sum> persistence_edges=<sum>
 // persistence_fnv1a32=<hash of every frame's plane, then persistence, then level_sides bytes>.
 //
+//   --level_colors <level> [--colors_components [--components_n8]]
+// asks vsg_render_level_colors for the colour sums of that level's regions, or of their connected components
+// (N4, or N8), in every frame of the video, and vsg_render_mean_frame for the level painted in their mean
+// colours (default options: edges, blend 0.5), and prints a line
+// level_colors_groups=<sum> level_colors_fnv1a32=<hash of every frame's records, then its mean frame bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -656,6 +662,82 @@ class LevelOverlapSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_colors: the colour table of a level's regions, or of their connected components, in the video's
+// frame (vsg_render_level_colors) and the level painted in mean colours (vsg_render_mean_frame): the
+// records, then the 3 * width pixel bytes of every picture row, of every frame.
+class LevelColorsSinkUnit : public VideoUnit {
+ public:
+  LevelColorsSinkUnit(int level, int connectedness, int device)
+      : level_(level), connect_(connectedness), device_(device) {}
+  ~LevelColorsSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    vid_idx_ = FindStreamIdx("VideoStream", set);
+    if (seg_idx_ < 0 || vid_idx_ < 0) return false;
+    const VideoStream& v = set->at(vid_idx_)->As<VideoStream>();
+    if (v.pixel_format() != PIXEL_FORMAT_BGR24) {
+      std::fprintf(stderr, "ERROR: --level_colors needs a BGR24 video stream\n");
+      return false;
+    }
+    width_ = v.frame_width();
+    height_ = v.frame_height();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.device = device_;
+    if (vsg_render_create(&o, width_, height_, &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    stride_ = vsg_render_default_stride(width_);
+    picture_.resize(stride_ * height_);
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    VF_CHECK(input->at(vid_idx_) != nullptr, "the video frame was freed before the colour sink");
+    const VideoFrame& frame = input->at(vid_idx_)->As<VideoFrame>();
+    size_t n = 0;
+    VF_CHECK(vsg_render_level_colors(render_, seg, desc.wire.size(), level_, connect_, frame.data(),
+                                     (size_t)frame.width_step(), VSG_MEM_HOST, nullptr, 0, &n, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    colors_buf_.resize(n);
+    if (n) {
+      VF_CHECK(vsg_render_level_colors(render_, seg, desc.wire.size(), level_, connect_, frame.data(),
+                                       (size_t)frame.width_step(), VSG_MEM_HOST, colors_buf_.data(), n, &n,
+                                       VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+    }
+    Hash(colors_buf_.data(), n * sizeof(vsg_render_level_color));
+    groups_ += (long)n;
+    VF_CHECK(vsg_render_mean_frame(render_, seg, desc.wire.size(), level_, connect_, frame.data(),
+                                   (size_t)frame.width_step(), VSG_MEM_HOST, picture_.data(), stride_,
+                                   VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    for (int y = 0; y < height_; ++y) Hash(picture_.data() + (size_t)y * stride_, (size_t)width_ * 3);
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long groups() const { return groups_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1, vid_idx_ = -1, width_ = 0, height_ = 0;
+  size_t stride_ = 0;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_color> colors_buf_;
+  std::vector<uint8_t> picture_;
+  long groups_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -767,6 +849,10 @@ struct Flags {
   // vsg_render_persistence_image and vsg_render_persistence_graph for every frame; the graph's
   // neighbourhood is --adjacency_n8's
   bool persistence = false;
+  // vsg_render_level_colors and vsg_render_mean_frame at this level for every frame; < 0: off.  Of the
+  // regions, or of the components (N4, or N8 with --components_n8) with --colors_components
+  int level_colors = -1;
+  bool colors_components = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -800,7 +886,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "two_stage_oversegment", "region_segmentation", "render_concat",
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
-                                   "adjacency_components", "overlap_components", "persistence", "help"};
+                                   "adjacency_components", "overlap_components", "persistence", "colors_components",
+                                   "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
       if (a == b) is_bool = true;
@@ -856,6 +943,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_overlap") f->level_overlap = atoi(v.c_str());
     else if (a == "overlap_components") f->overlap_components = bv;
     else if (a == "persistence") f->persistence = bv;
+    else if (a == "level_colors") f->level_colors = atoi(v.c_str());
+    else if (a == "colors_components") f->colors_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -1097,6 +1186,15 @@ int main(int argc, char** argv) {
     persistence_sink->AttachTo(input);
     input = persistence_sink.get();
   }
+  std::unique_ptr<LevelColorsSinkUnit> colors_sink;
+  if (FLAGS.level_colors >= 0) {
+    const int connectedness = !FLAGS.colors_components ? 0
+                              : FLAGS.components_n8    ? VSG_RENDER_CONNECT_N8
+                                                       : VSG_RENDER_CONNECT_N4;
+    colors_sink.reset(new LevelColorsSinkUnit(FLAGS.level_colors, connectedness, FLAGS.device));
+    colors_sink->AttachTo(input);
+    input = colors_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -1164,6 +1262,9 @@ int main(int argc, char** argv) {
     std::printf("persistence_levels=%d persistence_edge_pixels=%ld persistence_edges=%ld persistence_fnv1a32=%08x\n",
                 persistence_sink->levels(), persistence_sink->edge_pixels(), persistence_sink->edges(),
                 persistence_sink->hash());
+  }
+  if (colors_sink) {
+    std::printf("level_colors_groups=%ld level_colors_fnv1a32=%08x\n", colors_sink->groups(), colors_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

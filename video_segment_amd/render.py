@@ -101,6 +101,15 @@ class VsgRenderPersistenceStats(_capi.Structure):
     ]
 
 
+class VsgRenderColorStats(_capi.Structure):
+    _fields_ = [
+        ("groups", C.c_int64), ("intervals", C.c_int64), ("covered", C.c_int64),
+        ("largest_group_intervals", C.c_int64),
+        ("plane_us", C.c_float), ("sums_us", C.c_float), ("table_us", C.c_float), ("paint_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -173,6 +182,16 @@ OVERLAP_PAIR_DTYPE = np.dtype([("row", np.int32), ("col", np.int32), ("label", n
 assert OVERLAP_PAIR_DTYPE.itemsize == 16
 OVERLAP_PAIR_WORDS = 4
 
+# vsg_render_level_color: 72 bytes, no padding
+LEVEL_COLOR_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("area", np.int32),
+    ("mean", np.uint8, (3,)), ("reserved0", np.uint8),
+    ("sum", np.int64, (3,)), ("sum_sq", np.int64, (3,)),
+    ("min", np.uint8, (3,)), ("max", np.uint8, (3,)), ("reserved1", np.uint8, (2,)),
+])
+assert LEVEL_COLOR_DTYPE.itemsize == 72
+LEVEL_COLOR_WORDS = 18
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -190,6 +209,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_overlap", "vsg_render_last_overlap_stats",
     "vsg_render_persistence_image", "vsg_render_persistence_frame", "vsg_render_persistence_graph",
     "vsg_render_last_persistence_stats",
+    "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
 ]
 
 
@@ -248,6 +268,11 @@ def lib():
                                                C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), vp, vp,
                                                C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_persistence_stats.argtypes = [vp, C.POINTER(VsgRenderPersistenceStats)]
+    L.vsg_render_level_colors.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp,
+                                          C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_mean_frame.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp,
+                                        C.c_size_t, C.c_int]
+    L.vsg_render_last_color_stats.argtypes = [vp, C.POINTER(VsgRenderColorStats)]
     _handle = L
     return L
 
@@ -734,6 +759,64 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_persistence_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def level_colors(self, seg_bytes, level=0, frame=None, connectedness=0, colors_out=None):
+        """What every group of hierarchy level `level` looks like in `frame`: a LEVEL_COLOR_DTYPE array, record
+        k belonging to record k of level_regions (connectedness 0) or level_components (N4 or N8), with the
+        group's area and, per channel in B, G, R order, the sum, the sum of squares, the minimum, the maximum
+        and the mean rounded half up, all in integers.  frame: the H x W x 3 uint8 BGR24 frame, a numpy array
+        or a torch CUDA tensor (its rows may be further apart than 3 * W bytes).  Without colors_out the count
+        is asked for first and the array is allocated exactly.  colors_out: a buffer to fill instead, a
+        LEVEL_COLOR_DTYPE array or a (capacity, 18) int32 torch CUDA tensor; the filled part of it is
+        returned."""
+        if frame is None:
+            raise ValueError("frame is needed")
+        seg_bytes = bytes(seg_bytes)
+        p_bgr, stride, mem_in = _frame_ptr(frame, self.H, self.W, "frame")
+        n = C.c_size_t()
+        if colors_out is None:
+            check(lib().vsg_render_level_colors(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                p_bgr, stride, mem_in, None, 0, C.byref(n), VSG_MEM_HOST))
+            colors_out = np.empty(n.value, LEVEL_COLOR_DTYPE)
+            if n.value == 0:
+                return colors_out
+        if _capi.is_torch(colors_out):
+            if (colors_out.dim() != 2 or colors_out.shape[1] != LEVEL_COLOR_WORDS
+                    or str(colors_out.dtype) != "torch.int32"):
+                raise ValueError("colors_out has to be (capacity, %d) int32" % LEVEL_COLOR_WORDS)
+        elif colors_out.dtype != LEVEL_COLOR_DTYPE or colors_out.ndim != 1:
+            raise ValueError("colors_out has to be a one-dimensional LEVEL_COLOR_DTYPE array")
+        p, mem = _capi.contiguous_ptr(colors_out)
+        check(lib().vsg_render_level_colors(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), p_bgr,
+                                            stride, mem_in, p, colors_out.shape[0], C.byref(n), mem))
+        return colors_out[:n.value]
+
+    def mean_frame(self, seg_bytes, level=0, frame=None, connectedness=0, out=None):
+        """Hierarchy level `level` painted in the mean colours of its groups (level_colors' `mean`), then
+        treated as render() treats its colour plane: edges, blend with `frame`, concatenation.  The
+        out_rows x W x 3 uint8 picture: a numpy array, or a torch CUDA tensor when frame is one.  frame is
+        needed whatever has_video.  out: a caller's buffer instead, as in render().  The level the renderer
+        keeps for render() is neither resolved nor changed."""
+        if frame is None:
+            raise ValueError("frame is needed")
+        p_bgr, stride, mem_in = _frame_ptr(frame, self.H, self.W, "frame")
+        if out is None:
+            if _capi.is_torch(frame) and frame.is_cuda:
+                import torch
+                out = torch.empty((self.out_rows, self.W, 3), dtype=torch.uint8, device=frame.device)
+            else:
+                out = np.empty((self.out_rows, self.W, 3), np.uint8)
+        p_out, out_stride, mem_out = _frame_ptr(out, self.out_rows, self.W, "out")
+        seg_bytes = bytes(seg_bytes)
+        check(lib().vsg_render_mean_frame(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), p_bgr,
+                                          stride, mem_in, p_out, out_stride, mem_out))
+        return out
+
+    def last_color_stats(self):
+        """vsg_render_last_color_stats of the last level_colors or mean_frame call, as a dict."""
+        s = VsgRenderColorStats()
+        check(lib().vsg_render_last_color_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""
         s = VsgRenderVectorStats()
@@ -762,3 +845,13 @@ def overlap_scores(rows, pairs):
     ue_sum = int(np.minimum(count, inside - count).sum())
     return {"n": n, "asa_sum": asa_sum, "ue_sum": ue_sum,
             "asa": asa_sum / n if n else None, "ue": ue_sum / n if n else None}
+
+
+def color_moments(records):
+    """(mean, variance) of every record of level_colors, two (n, 3) float64 arrays in B, G, R order:
+    sum / area and sum_sq / area - (sum / area)^2 (the population variance; never below 0).  Host numpy only."""
+    records = np.asarray(records)
+    area = records["area"].astype(np.float64)[:, None]
+    mean = records["sum"].astype(np.float64) / area
+    variance = np.maximum(records["sum_sq"].astype(np.float64) / area - mean * mean, 0.0)
+    return mean, variance

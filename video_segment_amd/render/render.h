@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -355,6 +355,42 @@ void LaunchPersistEdges(const int32_t* nodes, uint32_t n_nodes, const int32_t* e
                         unsigned long long* hist, PersStatus* status, hipStream_t stream);
 // level_sides[l] = half the sum of hist[p] over p > l, l in [0, levels).
 void LaunchPersistSides(const unsigned long long* hist, int levels, long long* level_sides, hipStream_t stream);
+
+// ---- level colours (colors.hip): colour sums of every group of a level, the mean-colour intervals ------
+
+constexpr int kLevelColorWords = 18;     // vsg_render_level_color as int32 words
+constexpr int kColorPartialWords = 8;    // one interval's partial: 3 sums, 3 sums of squares, min, max
+constexpr size_t kColorAccBytes = 80;    // what a record gathers before it is finished
+
+enum ColorFlag {
+  COLOR_FLAG_RANGE = 1,   // an interval's record was out of range, or a record had no pixel
+};
+
+// Written by the colour kernels; read by the host at the end of a call.
+struct ColorStatus {
+  unsigned long long covered;   // sum of the records' areas
+  uint32_t largest;             // most intervals of one record
+  uint32_t flags;
+};
+
+// One partial of kColorPartialWords words per interval from the BGR24 frame `bgr` (rows `stride` bytes
+// apart, device memory): the sums and the sums of squares of the three channels (uint32 each), the minima
+// and the maxima packed as c0 | c1 << 8 | c2 << 16.  Only bytes [3 * left_x, 3 * right_x + 2] of row y are
+// read.  Dword loads when bgr and stride are multiples of 4.
+void LaunchColorRuns(const Interval* intervals, uint32_t n, int width, int height, const uint8_t* bgr, size_t stride,
+                     uint32_t* partials, hipStream_t stream);
+// The partials summed per record, then the records.  rank[i] - 1 is the record of interval i (LevelRank's
+// or CompRank's scan; records are contiguous in the list).  acc: capacity_acc entries of kColorAccBytes,
+// cleared to zero before.  table: table_words words per record, word 0 its id, word 1 (has_component) its
+// component.  *count records exist (device memory); they are written to `records` unless there are more
+// than `capacity`.  status->covered and ->largest are added to.
+void LaunchColorTable(const Interval* intervals, const uint32_t* rank, const uint32_t* partials, uint32_t n,
+                      uint32_t capacity_acc, void* acc, const int32_t* table, int table_words, bool has_component,
+                      const uint32_t* count, uint32_t capacity, int32_t* records, ColorStatus* status,
+                      hipStream_t stream);
+// out[i] = interval i with the packed mean of its record as its value.
+void LaunchColorIntervals(const Interval* intervals, const uint32_t* rank, uint32_t n, const int32_t* records,
+                          uint32_t capacity, Interval* out, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -20,6 +20,7 @@ namespace {
 
 using vsg_render_impl::AdjStatus;
 using vsg_render_impl::BoundStatus;
+using vsg_render_impl::ColorStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
@@ -38,6 +39,7 @@ enum AdjStage { ADJ_COUNT = 0, ADJ_EMIT, ADJ_SORT, ADJ_TABLE, ADJ_STAGES };
 enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_STAGES };
 // PRS_WAIT: the source frame's upload between the two kernels of a picture; reported with no stage
 enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
+enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -336,7 +338,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -379,6 +381,10 @@ struct vsg_render {
   // of a host output; the edges' persistences, the histogram and the levels' sides; the status words
   std::vector<int32_t> pers_ids, pers_table;
   Block d_anc, d_pq, d_pers_out, d_pers_status, h_pers;
+  // level colours: the intervals' partials; what the records gather; the records of a host output or of a
+  // picture; the interval list with the means as values; the status words and the pinned block the status,
+  // the number of records and a host table come back through
+  Block d_color_partials, d_color_acc, d_color_records, d_color_intervals, d_color_status, h_color;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
@@ -388,6 +394,7 @@ struct vsg_render {
   vsg_render_adjacency_stats astats;
   vsg_render_overlap_stats ostats;
   vsg_render_persistence_stats pstats;
+  vsg_render_color_stats kstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -981,6 +988,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->pclock.Create(PRS_STAGES + 1);
     h->h_pers.pinned = true;
     std::memset(&h->pstats, 0, sizeof(h->pstats));
+    h->kclock.Create(CLR_STAGES + 1);
+    h->h_color.pinned = true;
+    std::memset(&h->kstats, 0, sizeof(h->kstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -2241,6 +2251,250 @@ int vsg_render_last_persistence_stats(vsg_render* h, vsg_render_persistence_stat
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->pstats;
+  });
+}
+
+}  // extern "C"
+
+namespace {
+
+// vsg_render_level_colors (picture == nullptr) and vsg_render_mean_frame (colors == nullptr) behind their
+// argument checks that need no handle.
+void LevelColors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness, const uint8_t* bgr,
+                 size_t stride, int mem_in, vsg_render_level_color* colors, size_t capacity_colors, size_t* num_colors,
+                 uint8_t* picture, size_t out_stride, int mem_out) {
+  using namespace vsg_render_impl;
+  static_assert(sizeof(vsg_render_level_color) == kLevelColorWords * sizeof(int32_t), "moved as int32 words");
+  static_assert(sizeof(vsg_render_color_stats) == 56, "as the header says");
+  const int W = h->W, H = h->H;
+  const size_t row_bytes = (size_t)W * 3;
+  if (stride < row_bytes) Throw(VSG_ERR_INVALID, "stride is smaller than 3 * width");
+  if (picture) {
+    if (out_stride == 0) out_stride = vsg_render_default_stride(W);
+    if (out_stride < row_bytes) Throw(VSG_ERR_INVALID, "out_stride is smaller than 3 * width");
+  }
+  const bool count_only = !picture && !colors && capacity_colors == 0;
+  if (!picture && !colors && capacity_colors) Throw(VSG_ERR_INVALID, "colors is null");
+  if ((uint64_t)W * (uint64_t)H >= (1ull << 32)) Throw(VSG_ERR_INVALID, "the frame has 2^32 pixels or more");
+  DeviceGuard guard(h->device);
+  vsg_render_color_stats& ks = h->kstats;
+  std::memset(&ks, 0, sizeof(ks));
+
+  // ---- the interval list grouped by record, every interval's record, id and component of every record ----
+  const Interval* list = nullptr;
+  const uint32_t* rank = nullptr;
+  const int32_t* table = nullptr;
+  const uint32_t* d_count = nullptr;
+  int table_words = 0;
+  uint32_t n = 0, cap_records = 0;
+  vsg_render_level_stats ls;   // of the shared front half; the last level_regions call's stay
+  std::memset(&ls, 0, sizeof(ls));
+  if (connectedness == 0) {
+    LevelFront f = PaintLevelRuns(h, seg, seg_len, level, &ls);
+    n = f.n;
+    if (n) SortLevelRuns(h, &f, &ls);
+    list = f.intervals;
+    rank = f.rank;
+    table = f.regions;
+    table_words = kLevelRegionWords;
+    d_count = &f.status->regions;
+    cap_records = f.cap_regions;
+    ks.plane_us = h->stats.clear_us + h->stats.fill_us + ls.runs_us;
+    h->stats.launches += ls.launches;
+  } else {
+    size_t n_components = 0, n_intervals = 0;
+    LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals, nullptr,
+                    VSG_MEM_DEVICE, true);
+    n = (uint32_t)n_intervals;
+    list = h->d_comp_intervals.As<Interval>();
+    rank = h->d_comp_work.As<uint32_t>() + (size_t)5 * n;   // LevelComponents' comp_rank
+    table = h->d_comp_table.As<int32_t>();
+    table_words = kLevelComponentWords;
+    d_count = &h->d_comp_status.As<CompStatus>()->components;
+    cap_records = (uint32_t)n_components;
+    const vsg_render_component_stats& cs = h->cstats;
+    ks.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                  cs.label_us;
+  }
+  ks.launches = h->stats.launches;
+  ks.intervals = n;
+  if (n && cap_records == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
+
+  // ---- blocks, all before anything that uses them is enqueued ----
+  struct Seen {
+    ColorStatus status;
+    uint32_t records, pad[3];
+  };
+  const size_t record_bytes = (size_t)cap_records * sizeof(vsg_render_level_color);
+  const bool host_table = colors && mem_out == VSG_MEM_HOST;
+  h->d_color_status.Reserve(sizeof(ColorStatus), &h->allocations);
+  h->h_color.Reserve(sizeof(Seen) + (host_table ? record_bytes : 0), &h->allocations);
+  h->d_color_partials.Reserve((size_t)n * kColorPartialWords * sizeof(uint32_t), &h->allocations);
+  h->d_color_acc.Reserve((size_t)cap_records * kColorAccBytes, &h->allocations);
+  if (host_table || picture) h->d_color_records.Reserve(record_bytes, &h->allocations);
+  if (picture) h->d_color_intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
+  ColorStatus* status = h->d_color_status.As<ColorStatus>();
+  Seen* seen = h->h_color.As<Seen>();
+  std::memset(seen, 0, sizeof(Seen));
+  int launches = 0;
+
+  // ---- F: where it is, or to the device with the default stride ----
+  const uint8_t* src = bgr;
+  size_t src_stride = stride;
+  h->kclock.Begin(h->stream);
+  if (mem_in == VSG_MEM_HOST) {
+    src_stride = vsg_render_default_stride(W);
+    h->d_src.Reserve(src_stride * H, &h->allocations);
+    VSG_HIP(hipMemcpy2DAsync(h->d_src.p, src_stride, bgr, stride, row_bytes, H, hipMemcpyHostToDevice, h->stream));
+    ++launches;
+    src = h->d_src.As<uint8_t>();
+  }
+  uint8_t* dst = picture;
+  size_t dst_stride = out_stride;
+  const int out_rows = h->opt.concat_with_source ? 2 * H : H;
+  if (picture && mem_out == VSG_MEM_HOST) {
+    dst_stride = vsg_render_default_stride(W);
+    h->d_out.Reserve(dst_stride * out_rows, &h->allocations);
+    dst = h->d_out.As<uint8_t>();
+  }
+  h->kclock.Mark(CLR_UPLOAD);
+
+  // ---- partials, table ----
+  uint32_t* partials = h->d_color_partials.As<uint32_t>();
+  LaunchColorRuns(list, n, W, H, src, src_stride, partials, h->stream);
+  VSG_HIP(hipGetLastError());
+  h->kclock.Mark(CLR_SUMS);
+  // where the records go: the caller's device memory (the kernel decides there whether they fit), or the
+  // handle's block; nowhere in a count-only call
+  int32_t* records = nullptr;
+  uint32_t capacity = 0;
+  if (picture || host_table) {
+    records = h->d_color_records.As<int32_t>();
+    capacity = cap_records;
+  } else if (colors) {
+    records = reinterpret_cast<int32_t*>(colors);
+    capacity = (uint32_t)std::min<size_t>(capacity_colors, cap_records);
+  }
+  VSG_HIP(hipMemsetAsync(status, 0, sizeof(ColorStatus), h->stream));
+  ++launches;
+  if (n) {
+    VSG_HIP(hipMemsetAsync(h->d_color_acc.p, 0, (size_t)cap_records * kColorAccBytes, h->stream));
+    LaunchColorTable(list, rank, partials, n, cap_records, h->d_color_acc.p, table, table_words, connectedness != 0,
+                     d_count, capacity, records, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    VSG_HIP(hipMemcpyAsync(&seen->records, d_count, sizeof(uint32_t), hipMemcpyDeviceToHost, h->stream));
+    launches += 5;   // k_color_runs, the clear, k_color_table, k_color_finish, the count
+  }
+  h->kclock.Mark(CLR_TABLE);
+
+  // ---- the picture: vsg_render_frame's clear, fill and compose on the intervals with the means ----
+  if (picture) {
+    const bool video = h->opt.has_video != 0;
+    Interval* painted = h->d_color_intervals.As<Interval>();
+    uint32_t* plane = h->d_plane.As<uint32_t>();
+    LaunchColorIntervals(list, rank, n, records, capacity, painted, h->stream);
+    VSG_HIP(hipMemsetAsync(plane, 0, (size_t)h->pitch * H * sizeof(uint32_t), h->stream));
+    LaunchFill(painted, n, plane, h->pitch, h->stream);
+    const int mode = h->opt.concat_with_source ? COMPOSE_CONCAT : video ? COMPOSE_BLEND : COMPOSE_RENDER;
+    LaunchCompose(plane, h->pitch, W, H, src, src_stride, dst, dst_stride, h->opt.highlight_edges, mode,
+                  h->opt.blend_alpha, h->stream);
+    VSG_HIP(hipGetLastError());
+    launches += 2 + (n ? 2 : 0);
+    h->kclock.Mark(CLR_PAINT);
+    if (mem_out == VSG_MEM_HOST) {
+      VSG_HIP(hipMemcpy2DAsync(picture, out_stride, dst, dst_stride, row_bytes, out_rows, hipMemcpyDeviceToHost,
+                               h->stream));
+      ++launches;
+    }
+  }
+  if (host_table && n) {
+    VSG_HIP(hipMemcpyAsync(seen + 1, records, record_bytes, hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+  }
+  VSG_HIP(hipMemcpyAsync(&seen->status, status, sizeof(ColorStatus), hipMemcpyDeviceToHost, h->stream));
+  ++launches;
+  VSG_HIP(hipStreamSynchronize(h->stream));
+  {
+    float us[CLR_STAGES];
+    h->kclock.Read(us, CLR_STAGES);
+    ks.plane_us += us[CLR_UPLOAD];
+    ks.sums_us = us[CLR_SUMS];
+    ks.table_us = us[CLR_TABLE];
+    ks.paint_us = us[CLR_PAINT];
+    if (n && connectedness == 0) {
+      float lus[LVL_COUNT];
+      h->lclock.Read(lus, LVL_COUNT);
+      ks.plane_us += lus[LVL_SORT] + lus[LVL_TABLE];
+    }
+  }
+  ks.launches += launches;
+  h->stats.launches += launches;
+  h->stats.device_allocations = h->allocations;
+  const uint32_t n_records = seen->records;
+  if ((n == 0) != (n_records == 0) || n_records > cap_records || (connectedness != 0 && n_records != cap_records)) {
+    Throw(VSG_ERR_INTERNAL, "the level has other groups than the desc has ids for");
+  }
+  if ((seen->status.flags & COLOR_FLAG_RANGE) || seen->status.largest > n) {
+    Throw(VSG_ERR_INTERNAL, "an interval's record is out of range");
+  }
+  ks.groups = n_records;
+  ks.covered = (int64_t)seen->status.covered;
+  ks.largest_group_intervals = seen->status.largest;
+  if (num_colors) *num_colors = n_records;
+  if (picture || count_only) return;
+  if (n_records > capacity_colors) {
+    Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_records) + " groups, the capacity is " +
+                               std::to_string(capacity_colors));
+  }
+  if (host_table && n_records) std::memcpy(colors, seen + 1, (size_t)n_records * sizeof(vsg_render_level_color));
+}
+
+// The refusals of both calls that are answered before the handle is dereferenced.
+void CheckColorArguments(const vsg_render* h, int connectedness, const uint8_t* bgr, int mem_in, int mem_out) {
+  if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+  if (!bgr) Throw(VSG_ERR_INVALID, "bgr is null");
+  if (mem_in != VSG_MEM_HOST && mem_in != VSG_MEM_DEVICE) {
+    Throw(VSG_ERR_INVALID, "mem_in is neither VSG_MEM_HOST nor VSG_MEM_DEVICE");
+  }
+  if (mem_out != VSG_MEM_HOST && mem_out != VSG_MEM_DEVICE) {
+    Throw(VSG_ERR_INVALID, "mem_out is neither VSG_MEM_HOST nor VSG_MEM_DEVICE");
+  }
+  if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+    Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsg_render_level_colors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                            const uint8_t* bgr, size_t stride, int mem_in, vsg_render_level_color* colors,
+                            size_t capacity_colors, size_t* num_colors, int mem_out) {
+  return Guard([&] {
+    if (!num_colors) Throw(VSG_ERR_INVALID, "the count pointer is null");
+    *num_colors = 0;
+    CheckColorArguments(h, connectedness, bgr, mem_in, mem_out);
+    LevelColors(h, seg, seg_len, level, connectedness, bgr, stride, mem_in, colors, capacity_colors, num_colors,
+                nullptr, 0, mem_out);
+  });
+}
+
+int vsg_render_mean_frame(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          const uint8_t* bgr, size_t stride, int mem_in, uint8_t* out, size_t out_stride,
+                          int mem_out) {
+  return Guard([&] {
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    CheckColorArguments(h, connectedness, bgr, mem_in, mem_out);
+    LevelColors(h, seg, seg_len, level, connectedness, bgr, stride, mem_in, nullptr, 0, nullptr, out, out_stride,
+                mem_out);
+  });
+}
+
+int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->kstats;
   });
 }
 
