@@ -40,10 +40,13 @@
  * level above 0 is usually several blobs in one frame; vsg_render_level_components returns the same
  * per connected component, and vsg_render_level_boundaries the boundary point lists of either: the
  * reference's GetBoundary (segment_util/segmentation_boundary.{h,cpp}), the N4 inner or outer boundary
- * pixels of a rasterization in row-major order.  Contour tracing and vectorisation at a level
- * (BoundaryComputation, segmentation/boundary.cpp) are not offered.  Which regions or components of a
- * level touch in a frame, and along how many pixel sides, is what vsg_render_level_adjacency returns;
- * the reference has no per-frame counterpart (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
+ * pixels of a rasterization in row-major order.  Contour tracing at a level (BoundaryComputation,
+ * segmentation/boundary.cpp) is offered by vsg_render_level_contours: the closed outlines of every region or
+ * component as ordered vertex lists.  Still not offered: the reference's shared-segment mesh (segments cut at
+ * junctions and shared by the two regions they separate) and its approxPolyDP simplification.
+ * Which regions or components of a level touch in a frame, and along how many pixel sides, is what
+ * vsg_render_level_adjacency returns; the reference has no per-frame counterpart
+ * (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
  * against ground truth and correspondence between frames are not offered either, but the table they are
  * all functions of is: vsg_render_level_overlap relates a level to a ground-truth label image or to the id
  * image of another frame.  Boundary scores over a whole hierarchy are not offered; the ultrametric contour
@@ -663,6 +666,90 @@ typedef struct vsg_render_color_stats {
   int launches;
 } vsg_render_color_stats;                 /* 56 bytes with the tail padding */
 int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s);
+
+/* ---- Level contours: the traced closed outlines of every group of a level ----
+ *
+ * One contour, as vsg_render_level_contours returns it. */
+typedef struct vsg_render_level_contour {   /* 48 bytes, no padding */
+  int32_t id;             /* region id of the group */
+  int32_t component;      /* index among its region's components; -1 with connectedness 0 */
+  int32_t group;          /* index k of the group in the sibling list */
+  int32_t first_vertex;   /* offset of the contour's first vertex in `vertices`, in vertices */
+  int32_t num_vertices;   /* even, at least 4 */
+  int32_t length;         /* number of cracks, in pixel sides */
+  int32_t min_x, min_y, max_x, max_y;   /* bounding box in corner coordinates */
+  int64_t area2;          /* sum of x[i] * y[i + 1] - x[i + 1] * y[i]: twice the area, negative for a hole */
+} vsg_render_level_contour;
+
+/* The outlines of every region of hierarchy level `level`, or of every connected component of its regions,
+ * as ordered closed polylines on the corner lattice.  Traced on the device; everything is an integer and
+ * nothing depends on the order of execution.
+ *
+ * The plane.  P is the plane of vsg_render_level_boundaries: the id plane of vsg_render_id_image at `level`
+ * for connectedness 0, or the label image of vsg_render_level_components for VSG_RENDER_CONNECT_N4 / _N8
+ * (that call is made internally: vsg_render_last_component_stats then describes it).  Positions outside the
+ * frame count as -1.  A group g >= 0 is a value of P; group index k is record k of the sibling call,
+ * vsg_render_level_regions for connectedness 0 and vsg_render_level_components otherwise.
+ *
+ * Cracks.  Every pixel (x, y) of g has four sides: 0 top, 1 right, 2 bottom, 3 left.  A side is a crack of g
+ * when the pixel across it is not g: outside the frame, uncovered, or of another group.  These are exactly
+ * the sides the three border_* fields of vsg_render_level_adjacency count.  A crack is directed clockwise on
+ * screen around its own pixel, on the corner lattice [0, W] x [0, H]: top from (x, y) to (x + 1, y), right
+ * from (x + 1, y) to (x + 1, y + 1), bottom from (x + 1, y + 1) to (x, y + 1), left from (x, y + 1) to
+ * (x, y), so that g is always on the right hand of the direction of travel.  key = 4 * (y * W + x) + side
+ * identifies a crack.
+ *
+ * Successor.  At the corner where a crack ends the contour continues with the first crack of g, among those
+ * that start at that corner, in the order right turn (the next side of the same pixel), straight on (the
+ * same side of the next pixel of g), left turn (the side of the diagonal pixel of g); two reads of P decide
+ * it.  At a saddle corner (two diagonal pixels of g, the other two not g) the contour therefore stays with
+ * its own pixel, whatever the connectedness: positive contours bound N4-connected sets of g, holes bound
+ * N8-connected sets of the complement, and an N8 component made of two diagonal pixels has two positive
+ * contours.  The successor map is a permutation of the cracks; its cycles are the contours.
+ *
+ * Vertices.  A crack is a turn crack when its predecessor has another direction.  A contour's vertex list is
+ * the start corners of its turn cracks in travel order, beginning with the turn crack of smallest key (the
+ * crack of smallest key alone is not always a turn: under a hole two or more pixels wide it is not).
+ * Collinear corners are never listed; every contour has an even number of at least 4 vertices; a corner can
+ * occur twice in one list, at saddles.
+ *
+ * Order.  Contours are ordered by group, within a group by the key of their first turn crack: the first
+ * contour of every group is positive and starts at the top-left corner of the group's first pixel in
+ * row-major order.  vertices: int32 pairs {x, y}, grouped by contour in list order; capacity_vertices and
+ * *num_vertices count pairs.
+ *
+ * Decode, hierarchy rules (the desc's own hierarchy replaces the kept one), level refusals, the
+ * non-negative ids and the handling of vector-only descs are those of vsg_render_level_regions.
+ * *num_contours and *num_vertices are always set on VSG_OK and when a capacity is too small; in that case
+ * the call fails with VSG_ERR_INVALID and neither output is touched.  contours == NULL and vertices == NULL
+ * with both capacities 0 asks for the counts only (VSG_OK; needs the device).  A null handle, a null count
+ * pointer, a memory kind other than the two, or a connectedness other than 0, VSG_RENDER_CONNECT_N4 and
+ * VSG_RENDER_CONNECT_N8 is VSG_ERR_INVALID, answered before the handle is dereferenced.  A frame with no
+ * covered pixel returns zero contours and zero vertices.  The call neither resolves nor changes the level
+ * the handle keeps for vsg_render_frame (vsg_render_level).  Counts are 32-bit like the siblings': a handle
+ * whose crack keys would not fit (4 * W * H above 2^31) is refused with VSG_ERR_INVALID, and there are never
+ * more cracks than keys.  Both lists in mem_out memory. */
+int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                              vsg_render_level_contour* contours, size_t capacity_contours,
+                              size_t* num_contours, int32_t* vertices, size_t capacity_vertices,
+                              size_t* num_vertices, int mem_out);
+
+/* What the last vsg_render_level_contours call of the handle did.  cracks: the sides between a group and
+ * anything else, each counted for its own group; vertices and contours: the lengths of the two lists; holes:
+ * contours with area2 < 0; largest_contour_cracks: the longest `length`.  Device times are HIP events around
+ * the stages: plane_us, making the plane (as in vsg_render_boundary_stats); classify_us, the count pass (the
+ * crack masks and their scan) and the emit pass; trace_us, everything from the crack list to the ordered
+ * vertices (both doublings, the contours' sort and scans, the vertex scatter); table_us, the records, their
+ * lengths, boxes and areas, and the copies.  rounds: the pointer doubling rounds run, twice
+ * ceil(log2 cracks) made even (a launch does two rounds).  launches is a function of the connectedness, of ceil(log2 cracks), of where the outputs
+ * go and of how the plane is made (a vector-only desc adds its scan conversion), not of the plane's content.
+ * The stages after the count pass are not run, and everything but cracks is 0, when there is no crack. */
+typedef struct vsg_render_contour_stats {
+  int64_t cracks, vertices, contours, holes, largest_contour_cracks;
+  float plane_us, classify_us, trace_us, table_us;
+  int rounds, launches;
+} vsg_render_contour_stats;               /* 64 bytes */
+int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -50,6 +50,11 @@
 // colours (default options: edges, blend 0.5), and prints a line
 // level_colors_groups=<sum> level_colors_fnv1a32=<hash of every frame's records, then its mean frame bytes>.
 //
+//   --level_contours <level> [--contours_components [--components_n8]]
+// asks vsg_render_level_contours for the traced outlines of that level's regions, or of their connected
+// components, for every frame and prints
+// level_contours_count=<sum> level_contours_fnv1a32=<hash of every frame's records, then its vertices' bytes>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -443,6 +448,66 @@ class LevelBoundariesSinkUnit : public VideoUnit {
   std::vector<vsg_render_level_boundary> records_buf_;
   std::vector<int32_t> points_buf_;
   long boundaries_ = 0, points_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
+// --level_contours: the same for the traced contours of a level's regions or of their connected components
+// (vsg_render_level_contours), records first.
+class LevelContoursSinkUnit : public VideoUnit {
+ public:
+  LevelContoursSinkUnit(int level, int connectedness, int device)
+      : level_(level), connect_(connectedness), device_(device) {}
+  ~LevelContoursSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t nc = 0, nv = 0;
+    VF_CHECK(vsg_render_level_contours(render_, seg, desc.wire.size(), level_, connect_, nullptr, 0, &nc, nullptr, 0,
+                                       &nv, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    records_buf_.resize(nc);
+    vertices_buf_.resize(2 * nv);
+    if (nc) {
+      VF_CHECK(vsg_render_level_contours(render_, seg, desc.wire.size(), level_, connect_, records_buf_.data(), nc,
+                                         &nc, vertices_buf_.data(), nv, &nv, VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+    }
+    Hash(records_buf_.data(), nc * sizeof(vsg_render_level_contour));
+    Hash(vertices_buf_.data(), nv * 2 * sizeof(int32_t));
+    contours_ += (long)nc;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long contours() const { return contours_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_level_contour> records_buf_;
+  std::vector<int32_t> vertices_buf_;
+  long contours_ = 0;
   uint32_t hash_ = 2166136261u;
 };
 
@@ -853,6 +918,10 @@ struct Flags {
   // regions, or of the components (N4, or N8 with --components_n8) with --colors_components
   int level_colors = -1;
   bool colors_components = false;
+  // vsg_render_level_contours at this level for every frame; < 0: off.  Of the regions, or of the components
+  // (N4, or N8 with --components_n8) with --contours_components
+  int level_contours = -1;
+  bool contours_components = false;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -887,6 +956,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
                                    "adjacency_components", "overlap_components", "persistence", "colors_components",
+                                   "contours_components",
                                    "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
@@ -945,6 +1015,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "persistence") f->persistence = bv;
     else if (a == "level_colors") f->level_colors = atoi(v.c_str());
     else if (a == "colors_components") f->colors_components = bv;
+    else if (a == "level_contours") f->level_contours = atoi(v.c_str());
+    else if (a == "contours_components") f->contours_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -1195,6 +1267,15 @@ int main(int argc, char** argv) {
     colors_sink->AttachTo(input);
     input = colors_sink.get();
   }
+  std::unique_ptr<LevelContoursSinkUnit> contours_sink;
+  if (FLAGS.level_contours >= 0) {
+    const int connectedness = !FLAGS.contours_components ? 0
+                              : FLAGS.components_n8      ? VSG_RENDER_CONNECT_N8
+                                                         : VSG_RENDER_CONNECT_N4;
+    contours_sink.reset(new LevelContoursSinkUnit(FLAGS.level_contours, connectedness, FLAGS.device));
+    contours_sink->AttachTo(input);
+    input = contours_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -1265,6 +1346,10 @@ int main(int argc, char** argv) {
   }
   if (colors_sink) {
     std::printf("level_colors_groups=%ld level_colors_fnv1a32=%08x\n", colors_sink->groups(), colors_sink->hash());
+  }
+  if (contours_sink) {
+    std::printf("level_contours_count=%ld level_contours_fnv1a32=%08x\n", contours_sink->contours(),
+                contours_sink->hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

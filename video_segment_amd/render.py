@@ -110,6 +110,15 @@ class VsgRenderColorStats(_capi.Structure):
     ]
 
 
+class VsgRenderContourStats(_capi.Structure):
+    _fields_ = [
+        ("cracks", C.c_int64), ("vertices", C.c_int64), ("contours", C.c_int64), ("holes", C.c_int64),
+        ("largest_contour_cracks", C.c_int64),
+        ("plane_us", C.c_float), ("classify_us", C.c_float), ("trace_us", C.c_float), ("table_us", C.c_float),
+        ("rounds", C.c_int), ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -192,6 +201,16 @@ LEVEL_COLOR_DTYPE = np.dtype([
 assert LEVEL_COLOR_DTYPE.itemsize == 72
 LEVEL_COLOR_WORDS = 18
 
+# vsg_render_level_contour: 48 bytes, no padding
+LEVEL_CONTOUR_DTYPE = np.dtype([
+    ("id", np.int32), ("component", np.int32), ("group", np.int32),
+    ("first_vertex", np.int32), ("num_vertices", np.int32), ("length", np.int32),
+    ("min_x", np.int32), ("min_y", np.int32), ("max_x", np.int32), ("max_y", np.int32),
+    ("area2", np.int64),
+])
+assert LEVEL_CONTOUR_DTYPE.itemsize == 48
+LEVEL_CONTOUR_WORDS = 12
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -210,6 +229,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_persistence_image", "vsg_render_persistence_frame", "vsg_render_persistence_graph",
     "vsg_render_last_persistence_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
+    "vsg_render_level_contours", "vsg_render_last_contour_stats",
 ]
 
 
@@ -273,6 +293,9 @@ def lib():
     L.vsg_render_mean_frame.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp,
                                         C.c_size_t, C.c_int]
     L.vsg_render_last_color_stats.argtypes = [vp, C.POINTER(VsgRenderColorStats)]
+    L.vsg_render_level_contours.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t,
+                                            C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_contour_stats.argtypes = [vp, C.POINTER(VsgRenderContourStats)]
     _handle = L
     return L
 
@@ -817,6 +840,54 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_color_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def level_contours(self, seg_bytes, level=0, connectedness=0, contours_out=None, vertices_out=None):
+        """The closed outlines of every region of hierarchy level `level` (connectedness 0) or of every connected
+        component of its regions (N4 or N8), traced along the pixel sides: (contours, vertices).  contours: a
+        LEVEL_CONTOUR_DTYPE array ordered by group, `group` being the index of the contour's region in
+        level_regions (component in level_components), within a group by the key of the first turn; the first
+        contour of a group is its outer one, holes have a negative area2.  vertices: (n, 2) int32 corners
+        {x, y} of [0, W] x [0, H], grouped by contour in that order, clockwise on screen around the group, no
+        three of them collinear.  Without outputs the counts are asked for first and both arrays are allocated
+        exactly.  contours_out / vertices_out: buffers to fill instead, both numpy (a LEVEL_CONTOUR_DTYPE array
+        and a (capacity, 2) int32 array) or both torch CUDA tensors ((capacity, 12) int32, area2 as two
+        words, and (capacity, 2) int32); the filled parts of them are returned."""
+        seg_bytes = bytes(seg_bytes)
+        nc, nv = C.c_size_t(), C.c_size_t()
+        if (contours_out is None) != (vertices_out is None):
+            raise ValueError("pass both outputs or neither")
+        if contours_out is None:
+            check(lib().vsg_render_level_contours(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                                  None, 0, C.byref(nc), None, 0, C.byref(nv), VSG_MEM_HOST))
+            contours_out = np.empty(nc.value, LEVEL_CONTOUR_DTYPE)
+            vertices_out = np.empty((nv.value, 2), np.int32)
+            if nc.value == 0:
+                return contours_out, vertices_out
+        if _capi.is_torch(contours_out) != _capi.is_torch(vertices_out):
+            raise ValueError("both outputs have to be numpy arrays or both torch tensors")
+        if _capi.is_torch(contours_out):
+            if (contours_out.dim() != 2 or contours_out.shape[1] != LEVEL_CONTOUR_WORDS
+                    or str(contours_out.dtype) != "torch.int32"):
+                raise ValueError("contours_out has to be (capacity, %d) int32" % LEVEL_CONTOUR_WORDS)
+        elif contours_out.dtype != LEVEL_CONTOUR_DTYPE or contours_out.ndim != 1:
+            raise ValueError("contours_out has to be a one-dimensional LEVEL_CONTOUR_DTYPE array")
+        if (len(vertices_out.shape) != 2 or vertices_out.shape[1] != 2
+                or str(vertices_out.dtype).replace("torch.", "") != "int32"):
+            raise ValueError("vertices_out has to be (capacity, 2) int32")
+        pc, mem = _capi.contiguous_ptr(contours_out)
+        pv, mem_v = _capi.contiguous_ptr(vertices_out)
+        if mem != mem_v:
+            raise ValueError("both outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_contours(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), pc,
+                                              contours_out.shape[0], C.byref(nc), pv, vertices_out.shape[0],
+                                              C.byref(nv), mem))
+        return contours_out[:nc.value], vertices_out[:nv.value]
+
+    def last_contour_stats(self):
+        """vsg_render_last_contour_stats of the last level_contours call, as a dict."""
+        s = VsgRenderContourStats()
+        check(lib().vsg_render_last_contour_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""
         s = VsgRenderVectorStats()
@@ -855,3 +926,14 @@ def color_moments(records):
     mean = records["sum"].astype(np.float64) / area
     variance = np.maximum(records["sum_sq"].astype(np.float64) / area - mean * mean, 0.0)
     return mean, variance
+
+
+def contour_polygons(contours, vertices):
+    """The host arrays of level_contours as polygons: a list with one entry per group, in group order, each the
+    list of that group's (n, 2) int32 vertex arrays (views of `vertices`), the outer contour first.  Host
+    numpy only."""
+    contours, vertices = np.asarray(contours), np.asarray(vertices)
+    groups = [[] for _ in range(int(contours["group"].max()) + 1 if len(contours) else 0)]
+    for c in contours:
+        groups[int(c["group"])].append(vertices[int(c["first_vertex"]):int(c["first_vertex"]) + int(c["num_vertices"])])
+    return groups

@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -391,6 +391,73 @@ void LaunchColorTable(const Interval* intervals, const uint32_t* rank, const uin
 // out[i] = interval i with the packed mean of its record as its value.
 void LaunchColorIntervals(const Interval* intervals, const uint32_t* rank, uint32_t n, const int32_t* records,
                           uint32_t capacity, Interval* out, hipStream_t stream);
+
+// ---- level contours (contours.hip): the traced closed contours of every group of an int32 plane --------
+
+constexpr int kLevelContourWords = 12;   // vsg_render_level_contour as int32 words
+
+enum ContourFlag {
+  CONTOUR_FLAG_OVERFLOW = 1,   // a contour had no slot: more than one contour per four cracks
+  CONTOUR_FLAG_RANGE = 2,      // a crack, a successor, a leader, a rank, a contour or a vertex was out of range
+};
+
+// Written by the contour kernels; read by the host after the count pass and at the end of a call.
+struct ContourStatus {
+  unsigned long long cracks;   // pixel sides the count pass found
+  uint32_t contours;           // cycles of the successor permutation
+  uint32_t vertices;           // turn cracks
+  uint32_t holes;              // contours with a negative area
+  uint32_t largest;            // most cracks of one contour
+  uint32_t flags, pad;
+};
+
+// Work space of the scans, the sort and LevelRank of a call (the largest of them): `pixels` mask bytes,
+// `contours` contour slots.
+size_t ContourTempBytes(uint32_t pixels, int64_t contours, int end_bit);
+// The count pass over the H x W plane (row pitch W; negative and everything outside the frame: no group):
+// mask[p] = bit s set when side s (0 top, 1 right, 2 bottom, 3 left) of pixel p is a crack, offset[p] = the
+// cracks of the pixels before p, status->cracks += their number.
+hipError_t ContourClassify(void* temp, size_t temp_bytes, const int32_t* plane, int width, int height, uint8_t* mask,
+                           uint32_t* offset, ContourStatus* status, hipStream_t stream);
+// The emit pass: for crack i = offset[p] + (set bits of mask[p] below s) its key 4 p + s with bit 31 set when
+// it is a turn crack, succ[i] = the crack the contour continues with, state[i] = {succ[i], i or ~0 (no turn)}.
+// n: status->cracks as the host read it; key, succ and state have n entries.
+void LaunchContourEmit(const int32_t* plane, int width, int height, const uint8_t* mask, const uint32_t* offset,
+                       uint32_t n, uint32_t* key, uint32_t* succ, uint2* state, ContourStatus* status,
+                       hipStream_t stream);
+// The rounds of either doubling: ceil(log2 n), made even (a launch does two).
+int ContourRounds(uint32_t n);
+// Both doublings, rounds + 1 launches between state_a (k_contour_emit's) and state_b: leader[i] = the turn
+// crack of smallest key of i's contour; returns the buffer (one of the two) whose .y is the number of turn
+// cracks in [i, leader) along the contour, 0 for the leader.  The other buffer is free afterwards.
+const uint2* LaunchContourTrace(const uint32_t* key, const uint32_t* succ, uint32_t n, int rounds, uint2* state_a,
+                                uint2* state_b, uint32_t* leader, ContourStatus* status, hipStream_t stream);
+// ckeys[slot] = group << 32 | leader of every contour, in no order; status->contours.  ckeys has `capacity`
+// entries, set to ~0 before so that unused slots sort last.
+void LaunchContourLeaders(const uint32_t* leader, const uint32_t* key, const int32_t* plane, uint32_t n,
+                          uint32_t capacity, unsigned long long* ckeys, ContourStatus* status, hipStream_t stream);
+// The library radix sort on bits [0, end_bit) of all `capacity` slots.
+hipError_t ContourSort(void* temp, size_t temp_bytes, const unsigned long long* ckeys, unsigned long long* ckeys_sorted,
+                       int64_t capacity, int end_bit, hipStream_t stream);
+// count[j] and first[j] of sorted contour j (capacity entries each, 0 beyond the contours), place[leader] = j
+// (n entries), then every turn crack's start corner at vertices[first + rank] and owner[that slot] = j
+// (n slots each).  Three launches.
+hipError_t ContourVertices(void* temp, size_t temp_bytes, const unsigned long long* ckeys_sorted, const uint32_t* key,
+                           const uint32_t* succ, const uint32_t* leader, const uint2* ranked, uint32_t n,
+                           uint32_t capacity, int width, uint32_t* place, uint32_t* count, uint32_t* first,
+                           int32_t* vertices, uint32_t* owner, ContourStatus* status, hipStream_t stream);
+// The records (capacity entries); status->vertices, ->holes and ->largest.  rank: LevelRank of the sorted
+// keys.  comp_table: null (id = group, component = -1, group = rank - 1), or the table of LaunchCompTable
+// the groups index.  Three launches.
+void LaunchContourTable(const unsigned long long* ckeys_sorted, const uint32_t* rank, const uint32_t* count,
+                        const uint32_t* first, const int32_t* vertices, const uint32_t* owner, uint32_t n,
+                        uint32_t capacity, uint32_t max_group, const int32_t* comp_table, int32_t* records,
+                        ContourStatus* status, hipStream_t stream);
+// Copies status->contours records and status->vertices vertices, or nothing when either list is longer than
+// its capacity or a flag is up.
+void LaunchContourCopy(const int32_t* records, const int32_t* vertices, uint32_t capacity, uint32_t n,
+                       uint32_t capacity_records, uint32_t capacity_vertices, int32_t* records_out,
+                       int32_t* vertices_out, const ContourStatus* status, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -22,6 +22,7 @@ using vsg_render_impl::AdjStatus;
 using vsg_render_impl::BoundStatus;
 using vsg_render_impl::ColorStatus;
 using vsg_render_impl::CompStatus;
+using vsg_render_impl::ContourStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
 using vsg_render_impl::OvlStatus;
@@ -40,6 +41,7 @@ enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_ST
 // PRS_WAIT: the source frame's upload between the two kernels of a picture; reported with no stage
 enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
+enum ContourStage { CNT_CLASSIFY = 0, CNT_TRACE, CNT_TABLE, CNT_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -338,7 +340,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock, tclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -385,6 +387,12 @@ struct vsg_render {
   // picture; the interval list with the means as values; the status words and the pinned block the status,
   // the number of records and a host table come back through
   Block d_color_partials, d_color_acc, d_color_records, d_color_intervals, d_color_status, h_color;
+  // level contours: the pixels' crack masks and offsets; what there is per crack (the two doubling states,
+  // key, successor, leader, place, the vertices' owners; the vertices take the doubling state that is free
+  // at the end); what there is per contour slot (unsorted and sorted keys, group ranks, vertex counts and
+  // offsets); the records; the status words and the pinned block the status and host outputs come back
+  // through
+  Block d_cont_mask, d_cont_offset, d_cont_cracks, d_cont_slots, d_cont_records, d_cont_status, h_cont;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
@@ -395,6 +403,7 @@ struct vsg_render {
   vsg_render_overlap_stats ostats;
   vsg_render_persistence_stats pstats;
   vsg_render_color_stats kstats;
+  vsg_render_contour_stats tstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -991,6 +1000,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->kclock.Create(CLR_STAGES + 1);
     h->h_color.pinned = true;
     std::memset(&h->kstats, 0, sizeof(h->kstats));
+    h->tclock.Create(CNT_STAGES + 1);
+    h->h_cont.pinned = true;
+    std::memset(&h->tstats, 0, sizeof(h->tstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -2495,6 +2507,215 @@ int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s) {
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->kstats;
+  });
+}
+
+int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                              vsg_render_level_contour* contours, size_t capacity_contours, size_t* num_contours,
+                              int32_t* vertices, size_t capacity_vertices, size_t* num_vertices, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_level_contour) == kLevelContourWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_contour_stats) == 64, "documented size");
+    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_contours || !num_vertices) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    *num_contours = *num_vertices = 0;
+    CheckMem(mem_out, "mem_out");
+    const bool count_only = !contours && !vertices && capacity_contours == 0 && capacity_vertices == 0;
+    const int W = h->W, H = h->H;
+    if ((uint64_t)W * (uint64_t)H * 4 > (1ull << 31)) {
+      Throw(VSG_ERR_INVALID, "the frame has more than 2^31 pixel sides: crack keys do not fit 32 bits");
+    }
+    const uint32_t pixels = (uint32_t)W * (uint32_t)H;
+    DeviceGuard guard(h->device);
+    vsg_render_contour_stats& ts = h->tstats;
+    std::memset(&ts, 0, sizeof(ts));
+    // the offsets' scan runs before the first synchronisation: its work space before anything is enqueued
+    const size_t scan_bytes = std::max<size_t>(ContourTempBytes(pixels, 1, 64), 16);
+    h->d_sort_temp.Reserve(scan_bytes, &h->allocations);
+
+    // ---- the plane: the level's ids, or the indices of its regions' components ----
+    const int32_t* plane = nullptr;
+    const int32_t* comp_table = nullptr;
+    uint32_t max_group = 0;
+    bool vector = false;
+    if (connectedness == 0) {
+      int32_t max_id = 0;
+      vector = PaintLevelPlane(h, seg, seg_len, level, &max_id);
+      plane = h->d_ids.As<int32_t>();
+      max_group = (uint32_t)max_id;
+      ts.launches = h->stats.launches;
+    } else {
+      size_t n_components = 0, n_intervals = 0;
+      LevelComponents(h, seg, seg_len, level, connectedness, nullptr, 0, &n_components, nullptr, 0, &n_intervals,
+                      nullptr, VSG_MEM_DEVICE, true);
+      plane = h->d_labels.As<int32_t>();
+      comp_table = h->d_comp_table.As<int32_t>();
+      max_group = n_components ? (uint32_t)(n_components - 1) : 0u;
+      const vsg_render_component_stats& cs = h->cstats;
+      ts.plane_us = h->stats.clear_us + h->stats.fill_us + cs.runs_us + cs.sort_us + cs.link_us + cs.order_us +
+                    cs.label_us;
+      ts.launches = h->stats.launches;
+    }
+
+    // ---- count: the number of cracks sizes everything below ----
+    h->d_cont_status.Reserve(sizeof(ContourStatus), &h->allocations);
+    h->h_cont.Reserve(2 * sizeof(ContourStatus), &h->allocations);
+    h->d_cont_mask.Reserve(pixels, &h->allocations);
+    h->d_cont_offset.Reserve((size_t)pixels * sizeof(uint32_t), &h->allocations);
+    ContourStatus* status = h->d_cont_status.As<ContourStatus>();
+    ContourStatus* seen = h->h_cont.As<ContourStatus>();   // [0] after the count, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(ContourStatus));
+    uint8_t* mask = h->d_cont_mask.As<uint8_t>();
+    uint32_t* offset = h->d_cont_offset.As<uint32_t>();
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(ContourStatus), h->stream));
+    h->tclock.Begin(h->stream);
+    VSG_HIP(ContourClassify(h->d_sort_temp.p, h->d_sort_temp.cap, plane, W, H, mask, offset, status, h->stream));
+    VSG_HIP(hipGetLastError());
+    h->tclock.Mark(CNT_CLASSIFY);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(ContourStatus), hipMemcpyDeviceToHost, h->stream));
+    int launches = 4;   // the clear, the masks, the scan counted as one, the status
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[CNT_STAGES];
+      h->tclock.Read(us, CNT_STAGES);
+      ts.classify_us = us[CNT_CLASSIFY];
+    }
+    if (connectedness == 0) {
+      float us[STAGE_COUNT];
+      h->clock.Read(us, STAGE_COUNT);
+      h->stats.clear_us = us[STAGE_CLEAR];
+      h->stats.fill_us = us[STAGE_FILL];
+      ts.plane_us = us[STAGE_CLEAR] + us[STAGE_FILL];
+      if (vector) h->CheckVector();
+    }
+    auto finish = [&] {
+      ts.launches += launches;
+      h->stats.launches += launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    if (seen[0].cracks > 4ull * pixels) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "more cracks than pixel sides");
+    }
+    const uint32_t n = (uint32_t)seen[0].cracks;
+    ts.cracks = n;
+    if (n == 0) return finish();   // no covered pixel: both lists are empty
+    if (n < 4) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "fewer cracks than one pixel has");
+    }
+
+    // ---- emit, trace, table ----
+    const int rounds = ContourRounds(n);
+    const uint32_t cap = n / 4;   // a contour has four cracks or more
+    int group_bits = 1;
+    while (group_bits < 32 && (max_group >> group_bits)) ++group_bits;
+    const int end_bit = 32 + group_bits;
+    const size_t temp_bytes = std::max<size_t>(ContourTempBytes(pixels, cap, end_bit), 16);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    h->d_cont_cracks.Reserve((size_t)n * 36, &h->allocations);
+    h->d_cont_slots.Reserve((size_t)cap * 28, &h->allocations);
+    h->d_cont_records.Reserve((size_t)cap * sizeof(vsg_render_level_contour), &h->allocations);
+    uint2* state_a = h->d_cont_cracks.As<uint2>();
+    uint2* state_b = state_a + n;
+    uint32_t* key = reinterpret_cast<uint32_t*>(state_b + n);
+    uint32_t* succ = key + n;
+    uint32_t* leader = succ + n;
+    uint32_t* place = leader + n;
+    uint32_t* owner = place + n;
+    unsigned long long* ckeys = h->d_cont_slots.As<unsigned long long>();
+    unsigned long long* ckeys_sorted = ckeys + cap;
+    uint32_t* crank = reinterpret_cast<uint32_t*>(ckeys_sorted + cap);
+    uint32_t* count = crank + cap;
+    uint32_t* first = count + cap;
+    int32_t* d_records = h->d_cont_records.As<int32_t>();
+    h->tclock.Begin(h->stream);
+    LaunchContourEmit(plane, W, H, mask, offset, n, key, succ, state_a, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->tclock.Mark(CNT_CLASSIFY);
+    const uint2* ranked = LaunchContourTrace(key, succ, n, rounds, state_a, state_b, leader, status, h->stream);
+    // the doubling state that is not the result holds the vertices: n pairs at the most
+    int32_t* d_vertices = reinterpret_cast<int32_t*>(ranked == state_a ? state_b : state_a);
+    VSG_HIP(hipMemsetAsync(ckeys, 0xff, (size_t)cap * sizeof(unsigned long long), h->stream));   // unused: last
+    LaunchContourLeaders(leader, key, plane, n, cap, ckeys, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    VSG_HIP(ContourSort(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cap, end_bit, h->stream));
+    VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, ckeys_sorted, crank, cap, h->stream));
+    VSG_HIP(ContourVertices(h->d_sort_temp.p, temp_bytes, ckeys_sorted, key, succ, leader, ranked, n, cap, W, place,
+                            count, first, d_vertices, owner, status, h->stream));
+    VSG_HIP(hipGetLastError());
+    h->tclock.Mark(CNT_TRACE);
+    LaunchContourTable(ckeys_sorted, crank, count, first, d_vertices, owner, n, cap, max_group, comp_table, d_records,
+                       status, h->stream);
+    VSG_HIP(hipGetLastError());
+    ts.rounds = 2 * rounds;
+    // emit, the rounds (two a launch) and the cut between them, the clear, leaders, the sort and the scan
+    // counted as one each, heads, the scan, vertices, table, measure, finish
+    launches += rounds + 12;
+    const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && contours && vertices;
+    if (to_device) {
+      // the lengths of both lists are on the device: the copy decides there whether they fit
+      LaunchContourCopy(d_records, d_vertices, cap, n, (uint32_t)std::min<size_t>(capacity_contours, cap),
+                        (uint32_t)std::min<size_t>(capacity_vertices, n), reinterpret_cast<int32_t*>(contours),
+                        vertices, status, h->stream);
+      VSG_HIP(hipGetLastError());
+      ++launches;
+    }
+    h->tclock.Mark(CNT_TABLE);
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(ContourStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    if (!count_only && mem_out == VSG_MEM_HOST) launches += 2;   // counted whether or not the lists fit
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[CNT_STAGES];
+      h->tclock.Read(us, CNT_STAGES);
+      ts.classify_us += us[CNT_CLASSIFY];
+      ts.trace_us = us[CNT_TRACE];
+      ts.table_us = us[CNT_TABLE];
+    }
+    finish();
+    if (seen[1].flags & CONTOUR_FLAG_OVERFLOW) Throw(VSG_ERR_INTERNAL, "more contours than a quarter of the cracks");
+    if ((seen[1].flags & CONTOUR_FLAG_RANGE) || seen[1].contours == 0 || seen[1].contours > cap ||
+        seen[1].vertices > n || (uint64_t)seen[1].vertices < 4ull * seen[1].contours) {
+      Throw(VSG_ERR_INTERNAL, "a crack, a contour or a vertex is out of range");
+    }
+    const size_t n_contours = seen[1].contours, n_vertices = seen[1].vertices;
+    *num_contours = n_contours;
+    *num_vertices = n_vertices;
+    ts.contours = (int64_t)n_contours;
+    ts.vertices = (int64_t)n_vertices;
+    ts.holes = seen[1].holes;
+    ts.largest_contour_cracks = seen[1].largest;
+    if (count_only) return;
+    if (n_contours > capacity_contours || n_vertices > capacity_vertices) {
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_contours) + " contours and " +
+                                 std::to_string(n_vertices) + " vertices, the capacities are " +
+                                 std::to_string(capacity_contours) + " and " + std::to_string(capacity_vertices));
+    }
+    if (!contours || !vertices) Throw(VSG_ERR_INVALID, "an output is null");
+    if (mem_out == VSG_MEM_HOST) {
+      // through the pinned block, now that the lengths are known
+      const size_t cb = n_contours * sizeof(vsg_render_level_contour), vb = n_vertices * 2 * sizeof(int32_t);
+      h->h_cont.Reserve(2 * sizeof(ContourStatus) + cb + vb, &h->allocations);
+      h->stats.device_allocations = h->allocations;
+      char* stage = reinterpret_cast<char*>(h->h_cont.As<ContourStatus>() + 2);
+      VSG_HIP(hipMemcpyAsync(stage, d_records, cb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(stage + cb, d_vertices, vb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      std::memcpy(contours, stage, cb);
+      std::memcpy(vertices, stage + cb, vb);
+    }
+  });
+}
+
+int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->tstats;
   });
 }
 
