@@ -53,7 +53,7 @@ for s, e, n, st in seg:
     per_kernel[n][1] += e - s
 print("per stream busy (ms):", {k: round(v / 1e6, 2) for k, v in per_stream.items()})
 print("top kernels:")
-for n, (c, t) in sorted(per_kernel.items(), key=lambda kv: -kv[1][1])[:28]:
+for n, (c, t) in sorted(per_kernel.items(), key=lambda kv: -kv[1][1])[:44]:
     print("  %-34s %5d  %8.2f ms  avg %7.1f us" % (n, c, t / 1e6, t / c / 1e3))
 # what precedes the largest gaps
 print("largest gaps (us) and the kernel that ended before them:")
@@ -61,7 +61,10 @@ gl = sorted(gaps, reverse=True)[:12]
 for g, at in gl:
     prev = max((r for r in seg if r[1] <= at), key=lambda r: r[1])
     nxt = min((r for r in seg if r[0] >= at + g), key=lambda r: r[0])
-    print("  %7.1f after %-28s before %s" % (g / 1e3, prev[2], nxt[2]))
+    print("  %7.1f after %-28s before %-28s (%.2f ms into the merge)" % (g / 1e3, prev[2], nxt[2], (at - t0) / 1e6))
+for n in ("copyBuffer", "k_backup_roots", "k_max_segment", "k_mail_post"):   # (what rarely makes the table above)
+    ks = [k for k in per_kernel if k.startswith(n)]
+    print("%s: %d launches, %.2f ms" % (n, sum(per_kernel[k][0] for k in ks), sum(per_kernel[k][1] for k in ks) / 1e6))
 print("per stream x kernel (ms):")
 psk = defaultdict(lambda: defaultdict(int))
 for s, e, n, st in seg:

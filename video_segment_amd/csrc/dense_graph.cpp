@@ -717,15 +717,24 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
       }
       off[kNumBuckets + 1] = acc_l;
     }
+    // (the bytes the table always had: 19 660 records; a stage with more segments searches the
+    // bucket table in global memory)
     const size_t cap = (size_t)3 * 65536;
     if (seg_table_dev_.size() < cap) seg_table_dev_.alloc(cap);
-    S.bucket_base_host = getenv("VSG_FILTER_SEGS") && atoi(getenv("VSG_FILTER_SEGS")) == 0 ? nullptr
-                                                                                          : bucket_base_host_.data();
+    // VSG_FILTER_SEGS: 0 the filter finds an edge's list through the tables in device memory, 1 every
+    // stage's records in device memory, 2 (default) in the kernel's arguments where they fit
+    S.filter_segs_mode = getenv("VSG_FILTER_SEGS") ? atoi(getenv("VSG_FILTER_SEGS")) : 2;
+    S.bucket_base_host = S.filter_segs_mode == 0 ? nullptr : bucket_base_host_.data();
+    S.lists_host = desc.data();
     S.list_off_host = list_off_host_.data();
     S.list_slot_base_host = list_slot_base_.data();
     S.seg_dev = seg_table_dev_.get();
     S.seg_cap = seg_table_dev_.size();
     S.seg_host = &seg_table_host_;
+    stage_ring_.ensure(kStageRingInts);
+    S.ring_host = stage_ring_.get();
+    S.ring_cap = stage_ring_.size();
+    S.ring_used = &stage_ring_used_;
   }
   if (++window_target_age_ > 8) {
     window_target_age_ = 0;

@@ -189,6 +189,8 @@ class DenseGraphHip {
   DevBuf<int32_t> hub_excl_;        // exclusion list of the hub regions (device_graph.h: kFlagHubExcluded)
   PinnedBuf<int32_t> iv_host_;      // read-out: the scan intervals on the host (label, frame|y, lx, rx)
   std::vector<int32_t> seg_table_host_, list_off_host_;
+  size_t stage_ring_used_ = 0;
+  PinnedBuf<int32_t> stage_ring_;   // pinned source of the merge's small uploads (MergeScratch::ring_host)
   Mailbox mail_;              // host-visible scalars (device_graph.h); mapped host memory
   void* mail_mem_ = nullptr;
   DevBuf<int32_t> zero_pool_mem_;

@@ -211,14 +211,26 @@ struct FilterMasks {
   unsigned long long* tentative;   // settled under an assumption (inert_mode 2)
   int32_t* block_cnt;
 };
-// The non-empty (bucket, list) segments of a stage's edge range (k_filter): start inside the stage,
-// list index, position of the segment's first edge in the list's sorted slots.
+// The non-empty (bucket, list) segments of a stage's edge range (k_filter), one finished record per
+// segment, built by the host from its copies of the bucket and list tables: start inside the stage,
+// position of the segment's first edge in the list's sorted slots, and what an edge needs from its
+// list.  A stage of at most kFilterArgSegs segments (every stage of the first buckets, where the
+// edges are) hands the records over in the kernel's arguments; a longer table lies in device memory.
+struct FilterSegRec {
+  const uint32_t* slots;
+  const int32_t* prev;   // temporal list: prev_idx; spatial list: the slots once more (read, not used)
+  int32_t start, pos0, type, base_a, base_b;
+  uint32_t slot_base;    // list_slot_base of the list
+};
+constexpr int kFilterArgSegs = 64;
+struct FilterSegArgs {
+  FilterSegRec r[kFilterArgSegs];
+};
 struct FilterSegs {
-  const int32_t* start;
-  const int32_t* list;
-  const int32_t* pos0;
+  const FilterSegRec* rec;   // table in device memory (null: records in the arguments, or no table)
   int n;
 };
+constexpr size_t kStageRingInts = (size_t)1 << 18;   // (the largest table is 196 608 ints)
 struct MergeScratch {
   // e_ra / e_rb / e_gpos, the masks and the block counts are sized for the largest bucket; everything
   // else holds active edges only: active_cap of them (grow_active enlarges those arrays -- all
@@ -262,7 +274,14 @@ struct MergeScratch {
   const int32_t* list_off_host;        // [L][kNumBuckets + 2]: start of every bucket in every list's slots
   int32_t* seg_dev;                    // device buffer of the stage's segment table (FilterSegs)
   size_t seg_cap;                      // ... its capacity in ints
-  std::vector<int32_t>* seg_host;      // staging
+  std::vector<int32_t>* seg_host;      // staging (where the pinned ring cannot hold the table)
+  const ListDesc* lists_host;          // host copy of the list table
+  int filter_segs_mode;                // VSG_FILTER_SEGS: 0 no table, 1 always in device memory, 2 arguments where they fit
+  // Ring of pinned host memory for the small tables the merge uploads (a stage's segment table, the
+  // component table of a tree replay): out of a pageable source the runtime stages the copy and
+  // blocks.  TakeStageRing hands out the next piece.
+  int32_t* ring_host;   // kStageRingInts
+  size_t ring_cap, *ring_used;   // (the position lives in the graph: it carries over from merge to merge)
   // Kruskal-tree replay of the large components (merge_spine.hip)
   int spine_min;         // components of at least this many replayed edges; 0: never
   int spine_off;             // the current stage is a replay without the tree replay
@@ -341,6 +360,11 @@ int32_t* TakeZeroed(MergeScratch& S, size_t n);
 
 // n zeroed ints that stay intact until the stage that took them (at its entry) has ended.
 int32_t* TakeStageScalars(MergeScratch& S, size_t n);
+
+// n ints of pinned host memory as the source of one asynchronous upload (null: more than the ring
+// holds).  When the ring wraps all three streams are drained first, so no piece is rewritten before
+// its copy has run.
+int32_t* TakeStageRing(MergeScratch& S, size_t n);
 
 // bucket_base[b * (L+1) + l] = number of bucket-b edges in lists < l; [.. + L] = total.
 void LaunchBuildBucketTable(const ListDesc* lists, int num_lists, int32_t* bucket_base,

@@ -1431,8 +1431,19 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
   int32_t* firstq = S.nmap[1];
   int32_t* childidx = S.nmap[2];
 
-  VSG_HIP(hipMemcpyAsync(d_base, base.data(), (K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
-  VSG_HIP(hipMemcpyAsync(d_off, off.data(), K * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  // base and off in one copy out of the pinned ring (d_off follows d_base in the pool, after the
+  // padding of take()); two pageable copies only where the ring cannot hold them
+  VSG_REQUIRE(d_off == d_base + (((size_t)K + 1 + 63) & ~(size_t)63), -4, "spine: off does not follow base in the pool");
+  const size_t off_at = (size_t)(d_off - d_base);
+  if (int32_t* src = TakeStageRing(S, off_at + K)) {
+    std::copy(base.begin(), base.end(), src);
+    std::fill(src + K + 1, src + off_at, 0);
+    std::copy(off.begin(), off.end(), src + off_at);
+    VSG_HIP(hipMemcpyAsync(d_base, src, (off_at + K) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  } else {
+    VSG_HIP(hipMemcpyAsync(d_base, base.data(), (K + 1) * sizeof(int32_t), hipMemcpyHostToDevice, s));
+    VSG_HIP(hipMemcpyAsync(d_off, off.data(), K * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  }
   hipLaunchKernelGGL(k_spine_gather, dim3(Blocks(mE)), dim3(256), 0, s, mE, K, d_base, d_off, wa.s_ra,
                      wa.s_rb, eu, ev, estate, cc, best);
   hipLaunchKernelGGL(k_spine_pick_root, dim3(Blocks((size_t)K + (mE + kRootStride - 1) / kRootStride)), dim3(256), 0,

@@ -32,7 +32,9 @@
 #include <algorithm>
 #include <atomic>
 #include <chrono>
+#include <cstring>
 #include <thread>
+#include <type_traits>
 #include <vector>
 
 #include "merge_common.h"
@@ -221,6 +223,18 @@ int32_t* TakeStageScalars(MergeScratch& S, size_t n) {
   return p;
 }
 
+int32_t* TakeStageRing(MergeScratch& S, size_t n) {
+  n = (n + 15) & ~(size_t)15;   // (pieces start on a 64-byte line)
+  if (!S.ring_host || n > S.ring_cap) return nullptr;
+  if (*S.ring_used + n > S.ring_cap) {
+    DrainStreams(S);
+    *S.ring_used = 0;
+  }
+  int32_t* p = S.ring_host + *S.ring_used;
+  *S.ring_used += n;
+  return p;
+}
+
 // ------------------------------------------------------------------------------------------
 // Stage step 1: filter.
 // ------------------------------------------------------------------------------------------
@@ -241,10 +255,23 @@ int32_t* TakeStageScalars(MergeScratch& S, size_t n) {
 // s_waitcnt at full occupancy), so the only parallelism left to add is inside the thread -- the
 // chains of a thread's edges advance together, every step one batch of independent loads.  The
 // bookkeeping downstream (masks, packed records, per-block counts) stays in units of 256 edges:
-// a workgroup simply covers kFilterPer such blocks.
+// a workgroup simply covers kFilterPer such blocks.  Three and four edges per thread were measured
+// once the segment table had left LDS (62 VGPRs / 8 wavefronts per SIMD and 82 / 5 against 42 / 8):
+// 10.4-10.7 and 10.7-11.0 ms per chunk against 10.6-10.9 -- no gain beyond the runs' spread.
+// The first hop of every root search stays in a register: a chain whose node is its root or points
+// at it (nearly all) issues no load in the compression, a deeper one starts it from that hop.
 constexpr int kFilterPer = 2;
 constexpr int kFilterEdges = 256 * kFilterPer;   // edges per workgroup
 
+// Where an edge lives: the host hands over one finished record per non-empty (bucket, list) segment
+// of the stage (FilterSegRec).  kArgs: at most kFilterArgSegs records, in the kernel's arguments --
+// a workgroup finds the one or two segments its edges overlap with a compare-and-ballot over the
+// starts (its first edge is uniform) and reads their records with scalar loads: no LDS, no barrier
+// and no dependent load in front of the first byte of an edge.  Otherwise the records lie in device
+// memory and the workgroup keeps those its edges can touch in LDS (one load per record; the table
+// of round 5 named the list and cost a second, dependent load of the 48-byte descriptor), or there
+// is no table (segs.rec null) and every thread searches the bucket table in global memory.
+template <bool kArgs>
 __global__ __launch_bounds__(256) void k_filter(int bucket, int bucket_hi, int j0, int n_b,
                                                  const ListDesc* __restrict__ lists,
                                                  const int32_t* __restrict__ bucket_base,
@@ -257,76 +284,104 @@ __global__ __launch_bounds__(256) void k_filter(int bucket, int bucket_hi, int j
                                                  int32_t* __restrict__ e_rb,
                                                  uint32_t* __restrict__ e_gpos,
                                                  FilterMasks M,
-                                                 int32_t* __restrict__ num_ti, FilterSegs segs, int hubs,
+                                                 int32_t* __restrict__ num_ti, FilterSegs segs,
+                                                 std::conditional_t<kArgs, FilterSegArgs, int> A, int hubs,
                                                  int32_t* __restrict__ num_hub, int32_t* __restrict__ hub_excl,
                                                  float split_s) {
+  constexpr int kSegCap = kArgs ? 1 : kFilterEdges;
   __shared__ int wave_cnt[kFilterPer][4], wave_kept[kFilterPer][4];
-  __shared__ int s_start[kFilterEdges], s_pos0[kFilterEdges];
-  // ... with what the edges of a segment need from its list (a 48-byte descriptor per thread
-  // otherwise: six loads of the 22 a wavefront issued)
-  __shared__ const uint32_t* s_slots[kFilterEdges];
-  __shared__ const int32_t* s_prev[kFilterEdges];
-  __shared__ int s_type[kFilterEdges], s_base_a[kFilterEdges], s_base_b[kFilterEdges];
-  __shared__ uint32_t s_slot_base[kFilterEdges];
+  __shared__ int s_start[kSegCap], s_pos0[kSegCap];
+  __shared__ const uint32_t* s_slots[kSegCap];
+  __shared__ const int32_t* s_prev[kSegCap];
+  __shared__ int s_type[kSegCap], s_base_a[kSegCap], s_base_b[kSegCap];
+  __shared__ uint32_t s_slot_base[kSegCap];
   const int jf = blockIdx.x * kFilterEdges;   // first edge of the workgroup inside the stage's window
-  // Where an edge lives: the host lists the stage's non-empty (bucket, list) segments (start inside
-  // the stage, list, position of the segment's first edge in the list's sorted slots).  A
-  // workgroup's edges touch at most kFilterEdges of them, found by the workgroup together and kept
-  // in LDS -- the two binary searches per thread over tables in global memory (up to fifteen
-  // dependent loads before the first byte of the edge itself) made the kernel latency bound.
+  const bool have_segs = kArgs || segs.rec != nullptr;
   int m_segs = 0;
-  if (segs.start) {
-    int first = 0;
-    if (segs.n > kFilterEdges) {   // the last segment that starts at or before the workgroup's first edge
-      const int stride = (segs.n + 255) / 256;
-      const int t1 = threadIdx.x * stride;
-      const int c1 = __syncthreads_count(t1 < segs.n && segs.start[t1] <= jf);
-      const int base = (c1 - 1) * stride;
-      const int t2 = base + threadIdx.x;
-      const int c2 = __syncthreads_count(threadIdx.x < stride && t2 < segs.n && segs.start[t2] <= jf);
-      first = base + c2 - 1;
+  if constexpr (!kArgs) {
+    // A workgroup's edges touch at most kFilterEdges segments, found by the workgroup together and
+    // kept in LDS -- the two binary searches per thread over tables in global memory (up to fifteen
+    // dependent loads before the first byte of the edge itself) made the kernel latency bound.
+    if (segs.rec) {
+      int first = 0;
+      if (segs.n > kFilterEdges) {   // the last segment that starts at or before the workgroup's first edge
+        const int stride = (segs.n + 255) / 256;
+        const int t1 = threadIdx.x * stride;
+        const int c1 = __syncthreads_count(t1 < segs.n && segs.rec[t1].start <= jf);
+        const int base = (c1 - 1) * stride;
+        const int t2 = base + threadIdx.x;
+        const int c2 = __syncthreads_count(threadIdx.x < stride && t2 < segs.n && segs.rec[t2].start <= jf);
+        first = base + c2 - 1;
+      }
+      m_segs = min(kFilterEdges, segs.n - first);
+      for (int i = threadIdx.x; i < m_segs; i += 256) {
+        const FilterSegRec R = segs.rec[first + i];
+        s_start[i] = R.start;
+        s_pos0[i] = R.pos0;
+        s_slots[i] = R.slots;
+        s_prev[i] = R.prev;
+        s_type[i] = R.type;
+        s_base_a[i] = R.base_a;
+        s_base_b[i] = R.base_b;
+        s_slot_base[i] = R.slot_base;
+      }
+      __syncthreads();
     }
-    m_segs = min(kFilterEdges, segs.n - first);
-    for (int i = threadIdx.x; i < m_segs; i += 256) {
-      s_start[i] = segs.start[first + i];
-      const int l = segs.list[first + i];
-      s_pos0[i] = segs.pos0[first + i];
-      const ListDesc L = lists[l];
-      s_slots[i] = L.slots;
-      // (a spatial list has no displaced pixels: the unconditional load below reads its slots instead)
-      s_prev[i] = L.type != 0 ? L.prev_idx : reinterpret_cast<const int32_t*>(L.slots);
-      s_type[i] = L.type;
-      s_base_a[i] = L.base_a;
-      s_base_b[i] = L.base_b;
-      s_slot_base[i] = list_slot_base[l];
-    }
-    __syncthreads();
   }
   bool valid[kFilterPer];
   int a[kFilterPer], b[kFilterPer], l_type[kFilterPer];
   uint32_t gpos[kFilterPer];
-  if (segs.start) {
+  if (have_segs) {
     // ---- decode: every step is one batch of independent loads over the thread's edges ------------------------
     const uint32_t* slots_p[kFilterPer];
     const int32_t* prev_p[kFilterPer];
     int pos[kFilterPer], base_a[kFilterPer], base_b[kFilterPer];
+    int jc[kFilterPer];
 #pragma unroll
     for (int e = 0; e < kFilterPer; ++e) {
       const int j = jf + e * 256 + threadIdx.x;
       valid[e] = j < n_b;
-      const int jc = valid[e] ? j : n_b - 1;   // (an edge past the end repeats the last one, without effects)
-      int lo = 0, hi = m_segs;   // the last loaded segment with start <= jc
-      while (hi - lo > 1) {
-        const int mid = (lo + hi) >> 1;
-        if (s_start[mid] <= jc) lo = mid; else hi = mid;
+      jc[e] = valid[e] ? j : n_b - 1;   // (an edge past the end repeats the last one, without effects)
+    }
+    if constexpr (kArgs) {
+      // The starts ascend and the first one is 0: the segments [first, end) are those that hold an edge
+      // of [jf, jf + kFilterEdges) -- every wavefront finds the same two numbers by itself.  An edge
+      // belongs to the last of them that starts at or before it.
+      const int lane = threadIdx.x & 63;
+      const int st = lane < segs.n ? A.r[lane].start : 0x7fffffff;
+      const int first = max(0, (int)__popcll(__ballot(st <= jf)) - 1);
+      const int end = max(first + 1, (int)__popcll(__ballot(st < min(jf + kFilterEdges, n_b))));
+      for (int k = first; k < end; ++k) {
+        const FilterSegRec R = A.r[k];   // (uniform index: scalar loads)
+#pragma unroll
+        for (int e = 0; e < kFilterPer; ++e) {
+          if (k == first || jc[e] >= R.start) {
+            pos[e] = R.pos0 + (jc[e] - R.start);
+            slots_p[e] = R.slots;
+            prev_p[e] = R.prev;
+            l_type[e] = R.type;
+            base_a[e] = R.base_a;
+            base_b[e] = R.base_b;
+            gpos[e] = R.slot_base + (uint32_t)pos[e];
+          }
+        }
       }
-      pos[e] = s_pos0[lo] + (jc - s_start[lo]);
-      slots_p[e] = s_slots[lo];
-      prev_p[e] = s_prev[lo];
-      l_type[e] = s_type[lo];
-      base_a[e] = s_base_a[lo];
-      base_b[e] = s_base_b[lo];
-      gpos[e] = s_slot_base[lo] + (uint32_t)pos[e];
+    } else {
+#pragma unroll
+      for (int e = 0; e < kFilterPer; ++e) {
+        int lo = 0, hi = m_segs;   // the last loaded segment with start <= jc
+        while (hi - lo > 1) {
+          const int mid = (lo + hi) >> 1;
+          if (s_start[mid] <= jc[e]) lo = mid; else hi = mid;
+        }
+        pos[e] = s_pos0[lo] + (jc[e] - s_start[lo]);
+        slots_p[e] = s_slots[lo];
+        prev_p[e] = s_prev[lo];
+        l_type[e] = s_type[lo];
+        base_a[e] = s_base_a[lo];
+        base_b[e] = s_base_b[lo];
+        gpos[e] = s_slot_base[lo] + (uint32_t)pos[e];
+      }
     }
     uint32_t slot[kFilterPer];
 #pragma unroll
@@ -387,9 +442,18 @@ __global__ __launch_bounds__(256) void k_filter(int bucket, int bucket_hi, int j
     x0[2 * e] = a[e];
     x0[2 * e + 1] = b[e];
   }
+  // The first hop of every chain stays in a register: the compression below starts from it instead
+  // of loading parent[x0] a second time.
+  int hop[kChains];
 #pragma unroll
-  for (int c = 0; c < kChains; ++c) root[c] = x0[c];
-  for (bool any = true; any;) {
+  for (int c = 0; c < kChains; ++c) hop[c] = nodes.parent[x0[c]];
+  bool any = false;
+#pragma unroll
+  for (int c = 0; c < kChains; ++c) {
+    root[c] = hop[c];
+    any = any || (hop[c] != x0[c]);
+  }
+  while (any) {
     int p[kChains];
 #pragma unroll
     for (int c = 0; c < kChains; ++c) p[c] = nodes.parent[root[c]];
@@ -405,11 +469,21 @@ __global__ __launch_bounds__(256) void k_filter(int bucket, int bucket_hi, int j
   {
     // compression: every node on the path that does not point at the root yet (concurrent callers
     // may race on parent[] writes; every value ever written is an ancestor of the node, so any
-    // interleaving leaves a valid forest with the same roots -- FindCompress, merge_common.h)
+    // interleaving leaves a valid forest with the same roots -- FindCompress, merge_common.h).
+    // A chain whose node is the root or points at it -- nearly all of them -- has nothing to write
+    // and issues no load; a deeper one writes parent[x0] = root and goes on from its first hop (read
+    // before the root search: still an ancestor of x0, so the forest argument holds unchanged).
     int cur[kChains];
 #pragma unroll
-    for (int c = 0; c < kChains; ++c) cur[c] = x0[c];
-    for (bool any = true; any;) {
+    for (int c = 0; c < kChains; ++c) {
+      cur[c] = root[c];
+      if (x0[c] != root[c] && hop[c] != root[c]) {
+        nodes.parent[x0[c]] = root[c];
+        cur[c] = hop[c];
+        any = true;
+      }
+    }
+    while (any) {
       int nx[kChains];
 #pragma unroll
       for (int c = 0; c < kChains; ++c) nx[c] = cur[c] != root[c] ? nodes.parent[cur[c]] : root[c];
@@ -697,10 +771,17 @@ __global__ __launch_bounds__(256) void k_reset_cc(int n, const int32_t* __restri
                                                    const int32_t* __restrict__ a_rb,
                                                    int32_t* __restrict__ cc,
                                                    const int32_t* __restrict__ violation,
-                                                   unsigned long long* __restrict__ mail, unsigned mail_seq) {
+                                                   unsigned long long* __restrict__ mail, unsigned mail_seq,
+                                                   const int32_t* __restrict__ decomp) {
   const int i = blockIdx.x * 256 + threadIdx.x;
   // (the workers of the stage are done: this kernel follows the join of their streams)
-  if (i == 0 && mail) MailPost(mail, mail_seq, 0, *violation);
+  if (i == 0 && mail) {
+    MailPost(mail, mail_seq, 0, *violation);
+    if (decomp) {   // how the stage decomposed (k_gather_sorted) rides on the same slot
+      MailPost(mail, mail_seq, 1, decomp[1]);
+      MailPost(mail, mail_seq, 2, decomp[0]);
+    }
+  }
   if (i >= n) return;
   const int ra = a_ra[i], rb = a_rb[i];
   cc[ra] = ra;
@@ -714,13 +795,28 @@ __global__ __launch_bounds__(256) void k_gather_sorted(int n, const uint32_t* __
                                                         const uint32_t* __restrict__ a_gpos,
                                                         int32_t* __restrict__ s_ra,
                                                         int32_t* __restrict__ s_rb,
-                                                        uint32_t* __restrict__ s_gpos) {
+                                                        uint32_t* __restrict__ s_gpos,
+                                                        const int32_t* __restrict__ num_segs,
+                                                        const int32_t* __restrict__ seg_cnt, int below,
+                                                        int32_t* __restrict__ decomp) {
   const int p = blockIdx.x * 256 + threadIdx.x;
-  if (p >= n) return;
-  const uint32_t i = s_idx[p];
-  s_ra[p] = a_ra[i];
-  s_rb[p] = a_rb[i];
-  s_gpos[p] = a_gpos[i];
+  if (p < n) {
+    const uint32_t i = s_idx[p];
+    s_ra[p] = a_ra[i];
+    s_rb[p] = a_rb[i];
+    s_gpos[p] = a_gpos[i];
+  }
+  // decomp (optional): [0] the largest component, in replayed edges, below `below` (k_max_segment),
+  // [1] the number of components -- final before the workers start, and kept apart from the
+  // arrays the hub path reuses after them
+  if (decomp) {
+    const int m = *num_segs;
+    int v = p < n && p < m ? seg_cnt[p] : 0;
+    if (v >= below) v = 0;
+    for (int off = 32; off > 0; off >>= 1) v = max(v, __shfl_xor(v, off));
+    if ((threadIdx.x & 63) == 0 && v > decomp[0]) atomicMax(decomp, v);   // (a stale read only costs an atomic)
+    if (p == 0) decomp[1] = m;
+  }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1286,13 +1382,14 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   if (S.hub_attempt == 0 && S.hub_split_depth == 0) S.hub_splits_left = S.hub_max_splits;
   int32_t* d_num_leaders = S.num_active + 5;
   // The stage's non-empty (bucket, list) segments, from the host copy of the bucket table.
-  FilterSegs segs = {nullptr, nullptr, nullptr, 0};
-  if (S.bucket_base_host && S.list_off_host && S.seg_dev) {
+  FilterSegs segs = {nullptr, 0};
+  FilterSegArgs seg_args;
+  bool segs_in_args = false;
+  if (S.bucket_base_host && S.list_off_host && S.lists_host && S.list_slot_base_host && S.seg_dev) {
     const int L = P.num_lists;
-    std::vector<int32_t>& h = *S.seg_host;
-    h.clear();
+    constexpr size_t kRecInts = sizeof(FilterSegRec) / sizeof(int32_t);
     const int64_t g0 = (int64_t)S.bucket_prefix_host[bucket] + j0, g1 = g0 + n_b;
-    std::vector<int32_t> st, li, po;
+    std::vector<FilterSegRec> recs;
     for (int b = bucket; b < bucket_hi; ++b) {
       const int32_t* row = S.bucket_base_host + (size_t)b * (L + 1);
       const int64_t bstart = S.bucket_prefix_host[b];
@@ -1304,30 +1401,51 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
         const int64_t s0 = bstart + row[l], s1 = s0 + cnt;
         if (s1 <= g0 || s0 >= g1) continue;
         const int64_t first = std::max(s0, g0);
-        st.push_back((int32_t)(first - g0));
-        li.push_back(l);
-        po.push_back(S.list_off_host[(size_t)l * (kNumBuckets + 2) + b] + (int32_t)(first - s0));
+        const ListDesc& D = S.lists_host[l];
+        FilterSegRec R;
+        R.slots = D.slots;
+        // (a spatial list has no displaced pixels: the filter's unconditional load reads its slots instead)
+        R.prev = D.type != 0 ? D.prev_idx : reinterpret_cast<const int32_t*>(D.slots);
+        R.start = (int32_t)(first - g0);
+        R.pos0 = S.list_off_host[(size_t)l * (kNumBuckets + 2) + b] + (int32_t)(first - s0);
+        R.type = D.type;
+        R.base_a = D.base_a;
+        R.base_b = D.base_b;
+        R.slot_base = S.list_slot_base_host[l];
+        recs.push_back(R);
       }
     }
-    const int nseg = (int)st.size();
-    if (nseg > 0 && nseg <= 65536 && (size_t)3 * nseg <= S.seg_cap) {
-      h.reserve((size_t)3 * nseg);
-      h.insert(h.end(), st.begin(), st.end());
-      h.insert(h.end(), li.begin(), li.end());
-      h.insert(h.end(), po.begin(), po.end());
-      VSG_HIP(hipMemcpyAsync(S.seg_dev, h.data(), h.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
-      segs.start = S.seg_dev;
-      segs.list = S.seg_dev + nseg;
-      segs.pos0 = S.seg_dev + 2 * (size_t)nseg;
+    const int nseg = (int)recs.size();
+    if (nseg > 0 && nseg <= kFilterArgSegs && S.filter_segs_mode != 1) {
+      std::copy(recs.begin(), recs.end(), seg_args.r);
+      segs.n = nseg;
+      segs_in_args = true;
+    } else if (nseg > 0 && nseg <= 65536 && kRecInts * nseg <= S.seg_cap) {
+      // (out of the pinned ring; the pageable vector only where the ring cannot hold the table)
+      int32_t* src = TakeStageRing(S, kRecInts * nseg);
+      if (!src) {
+        S.seg_host->resize(kRecInts * nseg);
+        src = S.seg_host->data();
+      }
+      std::memcpy(src, recs.data(), (size_t)nseg * sizeof(FilterSegRec));
+      VSG_HIP(hipMemcpyAsync(S.seg_dev, src, (size_t)nseg * sizeof(FilterSegRec), hipMemcpyHostToDevice, s));
+      segs.rec = reinterpret_cast<const FilterSegRec*>(S.seg_dev);
       segs.n = nseg;
     }
   }
   const float split_s = ((float)bucket * P.inv_scale < P.force_merge_weight) ? P.s_lt_02 : P.s_le_015;   // (StageThr::split_s)
   const int ef0 = NextEvent(S);
   if (ef0 >= 0) VSG_HIP(hipEventRecord((*S.ev_pool)[ef0], s));
-  hipLaunchKernelGGL(k_filter, dim3((unsigned)((n_b + kFilterEdges - 1) / kFilterEdges)), dim3(256), 0, s, bucket, bucket_hi, j0, n_b, lists,
-                     bucket_base, S.bucket_prefix, list_slot_base, kept_all, nodes, P, inert_mode, S.cc, S.e_ra, S.e_rb, S.e_gpos,
-                     S.masks, d_num_ti, segs, try_hubs ? 1 : 0, d_num_hub, S.hub_excl, split_s);
+  const dim3 filter_grid((unsigned)((n_b + kFilterEdges - 1) / kFilterEdges));
+  if (segs_in_args) {
+    hipLaunchKernelGGL(k_filter<true>, filter_grid, dim3(256), 0, s, bucket, bucket_hi, j0, n_b, lists, bucket_base,
+                       S.bucket_prefix, list_slot_base, kept_all, nodes, P, inert_mode, S.cc, S.e_ra, S.e_rb, S.e_gpos,
+                       S.masks, d_num_ti, segs, seg_args, try_hubs ? 1 : 0, d_num_hub, S.hub_excl, split_s);
+  } else {
+    hipLaunchKernelGGL(k_filter<false>, filter_grid, dim3(256), 0, s, bucket, bucket_hi, j0, n_b, lists, bucket_base,
+                       S.bucket_prefix, list_slot_base, kept_all, nodes, P, inert_mode, S.cc, S.e_ra, S.e_rb, S.e_gpos,
+                       S.masks, d_num_ti, segs, 0, try_hubs ? 1 : 0, d_num_hub, S.hub_excl, split_s);
+  }
   const int ef1 = NextEvent(S);
   if (ef1 >= 0) {
     VSG_HIP(hipEventRecord((*S.ev_pool)[ef1], s));
@@ -1547,7 +1665,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   if (hubs_used && ((h[2] & 6) != 0 || ((h[2] & 16) != 0 && can_cut(n_active, (long long)(h[2] >> 8))))) {
     // The filter itself found a hub whose exact state an edge needs: nothing has been replayed yet.
     hipLaunchKernelGGL(k_reset_cc, dim3(Blocks(n_active)), dim3(256), 0, s, n_active, S.a_ra, S.a_rb, S.cc,
-                       d_violation, nullptr, 0u);
+                       d_violation, nullptr, 0u, nullptr);
     hipLaunchKernelGGL(k_clear_kept, dim3(Blocks(n_b)), dim3(256), 0, s, n_b, S.masks, S.e_gpos, kept_all);
     clear_marks();
     clear_hub_marks();
@@ -1624,8 +1742,12 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   int32_t* s_ra = reinterpret_cast<int32_t*>(S.a_comp);
   int32_t* s_rb = reinterpret_cast<int32_t*>(S.a_idx);
   uint32_t* s_gpos = reinterpret_cast<uint32_t*>(S.e_apos);
+  // An optimistic stage that reports its decomposition sends it with the violation word (one wait
+  // instead of two); the others ask for it after the workers (k_max_segment below).
+  const bool report = info && info->want_components && (info->want_components > 1 || n_work > 16384);
+  int32_t* d_decomp = report && optimistic ? d_num_ti + 5 : nullptr;   // ([5], [6] of the stage's scalars)
   hipLaunchKernelGGL(k_gather_sorted, dim3(Blocks(n_work)), dim3(256), 0, s, n_work, S.s_idx, w_ra,
-                     w_rb, w_gpos, s_ra, s_rb, s_gpos);
+                     w_rb, w_gpos, s_ra, s_rb, s_gpos, S.num_segs, S.seg_cnt, spine ? spine_thr : 0x7fffffff, d_decomp);
   const int small_seg = S.small_seg;
   auto WaveGrid = [small_seg](int n) {
     const int g = n / (small_seg + 1);
@@ -1748,11 +1870,15 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   MailSlot m_vio = {nullptr, nullptr, 0};
   if (optimistic) m_vio = NextMail(*S.mail);
   hipLaunchKernelGGL(k_reset_cc, dim3(Blocks(n_work)), dim3(256), 0, s, n_work, w_ra, w_rb, S.cc, d_violation,
-                     m_vio.dev, m_vio.seq);
+                     m_vio.dev, m_vio.seq, d_decomp);
   VSG_HIP(hipGetLastError());
+  int decomp[2] = {0, 0};   // components, largest ordinary one
   if (optimistic) {
-    int violated = 0;
-    MailWait(m_vio, 1, &violated, s);
+    int vio[3] = {0, 0, 0};
+    MailWait(m_vio, d_decomp ? 3 : 1, vio, s);
+    const int violated = vio[0];
+    decomp[0] = vio[1];
+    decomp[1] = vio[2];
     ++*S.optimistic_stages;
     if (violated || S.force_rollback) {
       // Undo the stage and replay it without any tentatively settled edge, every edge on its own.
@@ -1825,7 +1951,10 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     info->replayed = n_work;
     // (a component above the window threshold needs that many replayed edges: small stages are
     // not worth the synchronisation)
-    if (info->want_components && (info->want_components > 1 || n_work > 16384)) {
+    if (d_decomp) {
+      info->components = decomp[0];
+      info->max_wave_segment = decomp[1];
+    } else if (report) {
       int32_t* d_max = TakeZeroed(S, 1);
       hipLaunchKernelGGL(k_max_segment, dim3(Blocks(n_work)), dim3(256), 0, s, n_work, S.num_segs, S.seg_cnt,
                          spine ? spine_thr : 0x7fffffff, d_max);
