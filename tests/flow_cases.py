@@ -81,9 +81,93 @@ def driver_model():
     return tuple(flows), tuple(infos)
 
 
+# ---- test_gpu_flow_edges.py: shapes, content and options the cases above do not reach ----------------
+# name -> (group, frames() -> list of gray frames, iterations, warps); one flow per case unless the
+# maker says otherwise
+EDGE = {}
+FAST = (12, -9)   # (dx, dy) of the fast-motion case
+
+
+def _edge(group, name, maker, iterations=10, warps=2):
+    assert name not in EDGE
+    EDGE[name] = (group, maker, iterations, warps)
+
+
+def _translated(W, H, **kw):
+    return lambda: fm.translated_pattern(W, H, 2, SEED, **kw)
+
+
+def _block(W, H, row, col, n=2):
+    return lambda: fm.block_pattern(W, H, n, SEED, row, col)
+
+
+# workgroups of the iteration kernel at the finest level: below, at and far above 256
+for _W, _H in [(480, 136), (544, 136), (545, 137), (1056, 200), (16384, 16), (16, 2056)]:
+    _edge("tiles", "translated-%dx%d" % (_W, _H), _translated(_W, _H))
+# the only changed pixels lie in a tile of index 256 or above (271 and 288 of 289, 791 and 824 of 825) ...
+_edge("late", "late-block-544x136", _block(544, 136, 126, 524, n=3))   # 3 frames: also fed to two handles
+_edge("late", "late-block-1056x200", _block(1056, 200, 190, 1036))
+# ... and in tile 0, as the counterpart
+_edge("first", "first-block-544x136", _block(544, 136, 2, 2))
+_edge("first", "first-block-1056x200", _block(1056, 200, 2, 2))
+for _W, _H in [(1, 1), (2, 2), (1, 40), (40, 1), (31, 7), (33, 9)]:
+    _edge("tiny", "translated-%dx%d" % (_W, _H), _translated(_W, _H))
+_edge("pyramid", "translated-131x75", _translated(131, 75))
+_edge("pyramid", "translated-75x131", _translated(75, 131))
+_edge("pyramid", "translated-512x512-i3-w1", _translated(512, 512), 3, 1)
+_edge("content", "constant-same", lambda: fm.constant_pattern(67, 45, (128, 128)))
+_edge("content", "constant-128-129", lambda: fm.constant_pattern(67, 45, (128, 129)))
+_edge("content", "letterbox-96x64", lambda: fm.letterbox_pattern(96, 64, 2, SEED))
+_edge("content", "checker-96x64", lambda: fm.checker_pattern(96, 64, 2))
+_edge("content", "fast-160x120", _translated(160, 120, dx=FAST[0], dy=FAST[1]))
+_edge("options", "translated-67x45-i30-w3", _translated(67, 45), 30, 3)
+_edge("options", "translated-33x31-i1-w64", _translated(33, 31), 1, 64)
+_edge("options", "block-15x9-i1000-w1", lambda: fm.block_pattern(15, 9, 2, SEED), 1000, 1)
+
+
+def edge_names(*groups):
+    return [n for n, e in EDGE.items() if e[0] in groups]
+
+
+@functools.lru_cache(maxsize=None)
+def edge_frames(name):
+    out = EDGE[name][1]()
+    for f in out:
+        f.setflags(write=False)
+    return tuple(out)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_model(name):
+    """(flows, infos) of the case's backward flows, as model()."""
+    _, _, iterations, warps = EDGE[name]
+    flows, infos = fm.backward_flows(list(edge_frames(name)), iterations, warps)
+    for f in flows[1:]:
+        f.setflags(write=False)
+    return tuple(flows), tuple(infos)
+
+
+@functools.lru_cache(maxsize=None)
+def edge_forward_model(name):
+    """The same for the forward flows: calc(previous, current)."""
+    _, _, iterations, warps = EDGE[name]
+    fr = edge_frames(name)
+    res = [fm.tvl1(fr[k - 1], fr[k], iterations, warps) for k in range(1, len(fr))]
+    for f, _ in res:
+        f.setflags(write=False)
+    return (None,) + tuple(f for f, _ in res), (None,) + tuple(i for _, i in res)
+
+
+BOTH_EDGE = "late-block-544x136"   # flow_type both is run on these frames
+
+
 def all_infos():
     """(label, info) of every flow the GPU tests compare."""
     out = []
+    for name in EDGE:
+        out += [(name + "/%d" % k, i) for k, i in enumerate(edge_model(name)[1]) if i is not None]
+    out += [(BOTH_EDGE + "/forward/%d" % k, i) for k, i in enumerate(edge_forward_model(BOTH_EDGE)[1])
+            if i is not None]
     for c in SEQUENCE_CASES + OPTION_CASES + STOP_CASES:
         out += [(case_id(c) + "/%d" % k, i) for k, i in enumerate(model(*c)[1]) if i is not None]
     out += [("e2e/%d" % k, i) for k, i in enumerate(e2e_model()[1]) if i is not None]

@@ -98,8 +98,10 @@ def _cubic_weights(t):
     return w0, w1, w2, w3
 
 
-def warp3(planes, u1, u2):
-    """Bicubic samples of each plane at (x + u1, y + u2); the planes share addresses and weights."""
+def warp3(planes, u1, u2, counters=None):
+    """Bicubic samples of each plane at (x + u1, y + u2); the planes share addresses and weights.
+    counters, if given, receives "outside_taps" (taps of the 4 x 4 footprints that fell outside the
+    plane) and "clamped" (pixels whose gather index the [-4, W + 4] / [-4, H + 4] clamp changed)."""
     H, W = u1.shape
     fx = np.arange(W, dtype=F)[None, :] + u1
     fy = np.arange(H, dtype=F)[:, None] + u2
@@ -107,6 +109,11 @@ def warp3(planes, u1, u2):
     wx, wy = _cubic_weights(fx - fxf), _cubic_weights(fy - fyf)
     ix = np.minimum(np.maximum(fxf, F(-4)), F(W + 4)).astype(np.int64)
     iy = np.minimum(np.maximum(fyf, F(-4)), F(H + 4)).astype(np.int64)
+    if counters is not None:
+        xs, ys = ix[..., None] + np.arange(-1, 3), iy[..., None] + np.arange(-1, 3)
+        xin, yin = ((xs >= 0) & (xs < W)).sum(-1), ((ys >= 0) & (ys < H)).sum(-1)
+        counters["outside_taps"] = int(16 * W * H - (xin * yin).sum())
+        counters["clamped"] = int(((ix != fxf) | (iy != fyf)).sum())
     out = []
     for I in planes:
         rows = []
@@ -161,6 +168,18 @@ def _fwd_y(a):
     return d
 
 
+TILE_W, TILE_H = 32, 8     # the tile of the library's iteration kernel
+
+
+def tile_sums(err):
+    """The f64 sum of err over each TILE_W x TILE_H tile, tiles in row-major order."""
+    H, W = err.shape
+    tw, th = -(-W // TILE_W), -(-H // TILE_H)
+    e = np.zeros((th * TILE_H, tw * TILE_W), np.float64)
+    e[:H, :W] = err
+    return e.reshape(th, TILE_H, tw, TILE_W).sum(axis=(1, 3)).ravel()
+
+
 def one_scale(I0, I1, u1, u2, iterations, warps, info):
     H, W = I0.shape
     thr = 0.01 * 0.01 * float(W * H)
@@ -169,7 +188,9 @@ def one_scale(I0, I1, u1, u2, iterations, warps, info):
     I1x, I1y = centered_gradient(I1)
     p11, p12, p21, p22 = (np.zeros((H, W), F) for _ in range(4))
     for _ in range(warps):
-        I1w, I1wx, I1wy = warp3((I1, I1x, I1y), u1, u2)
+        wc = {"size": (W, H)}
+        I1w, I1wx, I1wy = warp3((I1, I1x, I1y), u1, u2, wc)
+        info["warps"].append(wc)
         grad = I1wx * I1wx + I1wy * I1wy
         rho_c = ((I1w - I1wx * u1) - I1wy * u2) - I0
         n = 0
@@ -197,6 +218,10 @@ def one_scale(I0, I1, u1, u2, iterations, warps, info):
             info["iterations_run"] += 1
             error = float(np.sum(err, dtype=np.float64))
             info["margin"] = min(info["margin"], abs(error - thr) / thr)
+            info["tests"].append({"size": (W, H), "threshold": thr, "error": error, "tiles": tile_sums(err),
+                                  "lo": int(lo.sum()), "hi": int((hi & ~lo).sum()), "mid": int(mid.sum()),
+                                  "flat": int((~lo & ~hi & ~mid).sum()),
+                                  "gradless": int((~(grad > FLT_EPSILON)).sum())})
             if not error > thr:
                 break
     assert u1.dtype == F and u2.dtype == F and p11.dtype == F
@@ -205,10 +230,15 @@ def one_scale(I0, I1, u1, u2, iterations, warps, info):
 
 def tvl1(I0_u8, I1_u8, iterations=10, warps=2):
     """OpticalFlowDual_TVL1::calc(I0, I1): H x W x 2 f32 (x, y) flow and
-    {"scales", "iterations_run", "margin"}; margin is the smallest |error - thr| / thr over all stop
-    tests evaluated."""
+    {"scales", "iterations_run", "margin", "tests", "warps"}; margin is the smallest
+    |error - thr| / thr over all stop tests evaluated.  tests and warps are counters beside the
+    arithmetic, in execution order: one entry per evaluated stop test (level size, threshold, error,
+    the error per tile, and how many pixels took each branch of the thresholding step: lo, else hi,
+    else mid, else flat; gradless counts the pixels with grad <= FLT_EPSILON whichever branch they
+    took: lo and hi come first, and with grad = 0 their step is as zero as flat's) and one per warp
+    (level size, outside_taps, clamped: see warp3)."""
     p0, p1 = pyramid(I0_u8), pyramid(I1_u8)
-    info = {"scales": len(p0), "iterations_run": 0, "margin": float("inf")}
+    info = {"scales": len(p0), "iterations_run": 0, "margin": float("inf"), "tests": [], "warps": []}
     s = len(p0) - 1
     u1, u2 = np.zeros(p0[s].shape, F), np.zeros(p0[s].shape, F)
     while True:
@@ -269,16 +299,39 @@ def split_pattern(W, H, n, seed):
     return out
 
 
-def block_pattern(W, H, n, seed):
-    """n nearly static gray frames: frame k differs from frame 0 in one small block only."""
+def block_pattern(W, H, n, seed, row=None, col=None):
+    """n nearly static gray frames: frame k differs from frame 0 in one small block only, 4 rows from
+    `row` (H / 3) and 5 columns from `col` (W / 3) + k, cut off at the frame's border."""
     base = value_noise(W, H, seed)
+    row = H // 3 if row is None else row
+    col = W // 3 if col is None else col
     out = []
     for k in range(n):
         f = base.copy()
         if k:
-            f[H // 3:H // 3 + 4, W // 3 + k:W // 3 + k + 5] = 255 - f[H // 3:H // 3 + 4, W // 3 + k:W // 3 + k + 5]
+            f[row:row + 4, col + k:col + k + 5] = 255 - f[row:row + 4, col + k:col + k + 5]
         out.append(f)
     return out
+
+
+def letterbox_pattern(W, H, n, seed, bar=12, level=16):
+    """translated_pattern with the top and bottom `bar` rows set to `level`: exactly flat areas."""
+    out = []
+    for f in translated_pattern(W, H, n, seed):
+        f[:bar, :] = level
+        f[H - bar:, :] = level
+        out.append(f)
+    return out
+
+
+def checker_pattern(W, H, n, cell=6, shift=2):
+    """n gray frames of a 0 / 255 checkerboard of `cell` pixels that moves left by `shift` per frame."""
+    y = np.arange(H)[:, None] // cell
+    return [(((np.arange(W)[None, :] + shift * k) // cell + y) % 2 * 255).astype(np.uint8) for k in range(n)]
+
+
+def constant_pattern(W, H, values):
+    return [np.full((H, W), v, np.uint8) for v in values]
 
 
 def gray_to_bgr(g):

@@ -1,6 +1,8 @@
 """CPU-side checks of the dense flow unit: the numpy model that defines it (tests/flow_model.py),
 the host-only luminance hook, and the C ABI's symbols.  The GPU comparison is test_gpu_flow.py."""
 import ctypes as C
+import hashlib
+import json
 import os
 import re
 
@@ -132,7 +134,176 @@ def test_stop_cases_stop_mid_loop():
         assert any(i["scales"] * c[4] < i["iterations_run"] < i["scales"] * c[4] * c[3] for i in infos[1:]), c
 
 
-# ---- 6. C ABI ----------------------------------------------------------------------------------------
+# ---- 6. the model's arithmetic is pinned; its counters stand beside it --------------------------------
+def test_model_flows_equal_their_pins():
+    """tests/golden/flow_model_pins.json holds SHA-256 sums of the model's flows for one case of each
+    list, taken before the counters of info["tests"] and info["warps"] were added."""
+    pins = json.load(open(os.path.join(ROOT, "tests", "golden", "flow_model_pins.json")))["cases"]
+    cases = [tuple(p["case"]) for p in pins]
+    assert [sum(c in l for c in cases) for l in (fc.SEQUENCE_CASES, fc.OPTION_CASES, fc.STOP_CASES)] == [1, 1, 1]
+    for p, c in zip(pins, cases):
+        flows, infos = fc.model(*c)
+        h = hashlib.sha256()
+        for f in flows[1:]:
+            assert f.dtype == np.float32 and f.shape == (c[2], c[1], 2)
+            h.update(f.tobytes())
+        assert h.hexdigest() == p["sha256"], c
+        assert [i["iterations_run"] for i in infos[1:]] == p["iterations_run"], c
+
+
+def test_counters_by_hand():
+    # tile sums: 33 x 9 is 2 x 2 tiles, the second column and row one pixel wide
+    err = np.arange(33 * 9, dtype=np.float32).reshape(9, 33)
+    t = fm.tile_sums(err)
+    assert t.dtype == np.float64 and t.tolist() == [float(err[:8, :32].sum()), float(err[:8, 32].sum()),
+                                                   float(err[8, :32].sum()), float(err[8, 32])]
+    # warp counters on a 20 x 10 plane.  u = 0: the footprint x - 1 .. x + 2 leaves the plane at
+    # x = 0 (1 column), x = W - 2 (1) and x = W - 1 (2), rows alike
+    z = np.zeros((10, 20), np.float32)
+    c = {}
+    fm.warp3((z,), z, z, c)
+    cols_in, rows_in = 20 * 4 - 4, 10 * 4 - 4
+    assert c == {"outside_taps": 16 * 200 - cols_in * rows_in, "clamped": 0}
+    # u1 = +30 puts every floor(x + u1) past W + 4 = 24
+    fm.warp3((z,), z + np.float32(30), z, c)
+    assert c == {"outside_taps": 16 * 200, "clamped": 200}
+    u = z.copy()
+    u[:, 0] = -4.5                  # floor = -5: clamped to -4
+    u[:, 1] = -4.5                  # floor(1 - 4.5) = -4: not clamped
+    fm.warp3((z,), u, z, c)
+    assert c["clamped"] == 10
+
+
+def test_every_stop_test_is_recorded():
+    for name in ("late-block-544x136", "letterbox-96x64", "translated-33x9"):
+        for info in fc.edge_model(name)[1][1:]:
+            assert len(info["tests"]) == info["iterations_run"]
+            assert len(info["warps"]) == info["scales"] * fc.EDGE[name][3]
+            for t in info["tests"]:
+                W, H = t["size"]
+                assert t["lo"] + t["hi"] + t["mid"] + t["flat"] == W * H
+                assert len(t["tiles"]) == -(-W // 32) * -(-H // 8)
+                assert abs(t["tiles"].sum() - t["error"]) <= 1e-9 * t["error"]
+                assert t["threshold"] == 0.01 * 0.01 * (W * H)
+
+
+# ---- 7. the inputs of test_gpu_flow_edges.py reach what they are there for -----------------------------
+def _tiles(W, H):
+    return -(-W // 32) * -(-H // 8)
+
+
+def test_edge_shapes_have_their_tile_counts():
+    got = {n: _tiles(*fc.edge_frames(n)[0].shape[::-1]) for n in fc.edge_names("tiles")}
+    assert got == {"translated-480x136": 255, "translated-544x136": 289, "translated-545x137": 324,
+                   "translated-1056x200": 825, "translated-16384x16": 1024, "translated-16x2056": 257}
+    assert [_tiles(*s) for s in fm.pyramid_sizes(545, 137)] == [324, 81, 25, 9]
+    assert 545 % 32 == 1 and 137 % 8 == 1    # the last tile column and row are one pixel
+    assert fm.pyramid_sizes(545, 137) == [(545, 137), (273, 69), (137, 35), (69, 18)]   # odd but one side
+
+
+@pytest.mark.parametrize("name,row,col,tile", [("late-block-544x136", 126, 524, 271),
+                                               ("late-block-1056x200", 190, 1036, 791)])
+def test_late_block_decides_behind_tile_256(name, row, col, tile):
+    """The frames differ only inside two tiles of index >= 256, and at the finest level a stop test
+    exists that a sum over the first 256 partial sums alone would decide the other way.  The sum of
+    the first 256 tiles may be exactly 0, so it is asked to lie below 0.9 x threshold, not at 1e-6
+    of it; the total keeps the 1e-6 margin."""
+    frames = fc.edge_frames(name)
+    H, W = frames[0].shape
+    tw = -(-W // 32)
+    assert (row // 8) * tw + col // 32 == tile >= 256
+    _, infos = fc.edge_model(name)
+    _, _, iterations, warps = fc.EDGE[name]
+    for k in range(1, len(frames)):
+        ys, xs = np.nonzero(frames[k] != frames[0])
+        assert len(ys) > 0 and set(((ys // 8) * tw + xs // 32).tolist()) == {tile, tile + tw}   # 4 rows from `row`
+        info = infos[k]
+        assert info["margin"] >= 1e-6
+        fine = [t for t in info["tests"] if t["size"] == (W, H)]
+        assert fine and len(fine[0]["tiles"]) > 256
+        wrong = [t for t in fine if t["tiles"][:256].sum() <= t["threshold"] < t["error"]]
+        assert wrong, "no stop test that the first 256 tiles would decide differently"
+        assert any(t["tiles"][:256].sum() < 0.9 * t["threshold"] for t in wrong)
+        print("%s/%d: %d of %d finest stop tests, first %.2f <= %.2f < %.2f, %d iterations" % (
+            name, k, len(wrong), len(fine), wrong[0]["tiles"][:256].sum(), wrong[0]["threshold"],
+            wrong[0]["error"], info["iterations_run"]))
+        # stops inside a loop: later than each warp's first iteration, earlier than all of them
+        assert info["scales"] * warps < info["iterations_run"] < info["scales"] * warps * iterations
+
+
+def test_late_block_figures():
+    info = fc.edge_model("late-block-544x136")[1][1]
+    assert info["iterations_run"] == 38 and info["scales"] == 4
+    assert 1.3e-3 < info["margin"] < 1.5e-3
+    t = next(t for t in info["tests"] if t["size"] == (544, 136) and t["tiles"][:256].sum() <= t["threshold"] < t["error"])
+    assert (round(t["tiles"][:256].sum(), 2), round(t["threshold"], 2), round(t["error"], 2)) == (6.53, 7.40, 21.47)
+    t = next(t for t in fc.edge_model("late-block-1056x200")[1][1]["tests"] if t["size"] == (1056, 200))
+    assert t["tiles"][:256].sum() == 0.0 and t["threshold"] < t["error"]
+    for name in fc.edge_names("first"):     # the counterpart: everything happens in tile 0
+        frames = fc.edge_frames(name)
+        ys, xs = np.nonzero(frames[1] != frames[0])
+        assert len(ys) > 0 and ys.max() < 8 and xs.max() < 32
+
+
+def test_tiny_frames_run():
+    runs = {n: fc.edge_model(n)[1][1]["iterations_run"] for n in fc.edge_names("tiny")}
+    assert runs.pop("translated-1x1") == 2
+    assert len(runs) == 5 and set(runs.values()) == {20}
+
+
+def test_content_cases_reach_every_branch():
+    def branches(name):
+        tests = [t for i in fc.edge_model(name)[1][1:] for t in i["tests"]]
+        return {b: sum(t[b] for t in tests) for b in ("lo", "hi", "mid", "flat", "gradless")}, tests
+
+    reached = {b for name in fc.edge_names("content") for b, v in branches(name)[0].items() if v > 0}
+    assert reached == {"lo", "hi", "mid", "flat", "gradless"}
+
+    for name in fc.edge_names("content"):
+        flows, _ = fc.edge_model(name)
+        b, tests = branches(name)
+        print(name, b)
+        if name.startswith("constant"):
+            assert not flows[1].any() and not np.signbit(flows[1]).any()
+            # grad is 0 at every pixel of every test, so the step is zero whichever branch is taken
+            assert all(t["gradless"] == t["size"][0] * t["size"][1] for t in tests) and b["mid"] == 0
+    assert all(v > 0 for v in branches("letterbox-96x64")[0].values())
+    b, tests = branches("constant-same")
+    assert b["lo"] == b["hi"] == b["mid"] == 0 and b["flat"] == b["gradless"] > 0
+    # 128 then 129: rho = -1 < -l_t * 0, so the model (and the kernel) take lo with a step of l_t * 0
+    b, _ = branches("constant-128-129")
+    assert b["hi"] == b["mid"] == b["flat"] == 0 and b["lo"] == b["gradless"] > 0
+    # one test of the letterbox frames reaches all four at once
+    assert any(min(t["lo"], t["hi"], t["mid"], t["flat"]) > 0 for t in branches("letterbox-96x64")[1])
+
+
+def test_fast_motion_reaches_the_clamp():
+    flows, infos = fc.edge_model("fast-160x120")
+    assert fc.FAST == (12, -9)
+    warps = infos[1]["warps"]
+    print("clamped", [w["clamped"] for w in warps], "outside taps", [w["outside_taps"] for w in warps])
+    assert sum(w["clamped"] for w in warps) > 0 and all(w["outside_taps"] > 0 for w in warps)
+    assert np.abs(flows[1]).max() > 12
+
+
+@pytest.mark.parametrize("W,H,sizes", [
+    (131, 75, [(131, 75), (66, 38), (33, 19)]),            # the height ends it: (17, 10) is not built
+    (75, 131, [(75, 131), (38, 66), (19, 33)]),
+    (512, 512, [(512, 512), (256, 256), (128, 128), (64, 64), (32, 32)]),   # NSCALES alone ends it
+    (544, 136, [(544, 136), (272, 68), (136, 34), (68, 17)]),
+    (1056, 200, [(1056, 200), (528, 100), (264, 50), (132, 25)]),
+    (16384, 16, [(16384, 16)]),
+    (16, 2056, [(16, 2056)]),
+    (1, 1, [(1, 1)]), (1, 40, [(1, 40)]), (40, 1, [(40, 1)]), (31, 7, [(31, 7)]), (33, 9, [(33, 9)]),
+])
+def test_pyramid_sizes_of_edge_shapes(W, H, sizes):
+    assert fm.pyramid_sizes(W, H) == sizes
+    if (W, H) == (512, 512):
+        assert len(sizes) == fm.NSCALES and min((W >> 5, H >> 5)) >= 16   # a sixth level would pass the side rule
+        assert fc.edge_model("translated-512x512-i3-w1")[1][1]["scales"] == 5
+
+
+# ---- 8. C ABI ----------------------------------------------------------------------------------------
 def test_header_symbols_exported(library):
     header = open(os.path.join(ROOT, "include", "vsg_flow.h")).read()
     declared = set(re.findall(r"\b(vsg_flow_[a-z0-9_]+)\s*\(", header))
@@ -165,6 +336,23 @@ def test_no_cpu_fallback(library):
     assert b"no usable HIP device" in library.vsg_flow_last_error()
     with pytest.raises(flow.VsgError):
         flow.DenseFlow(64, 48)
+
+
+def test_frames_one_pixel_wide_or_high_are_taken():
+    """numpy leaves any stride on an axis of length 1 (a slice's, here): such a frame is packed."""
+    from video_segment_amd import _capi
+    canvas = np.arange(15 * 54, dtype=np.uint8).reshape(15, 54)
+    for H, W in [(1, 1), (1, 9), (9, 1)]:
+        f = np.ascontiguousarray(canvas[3:3 + H, 5:5 + W])
+        p, stride, mem = _capi.frame_ptr(f, H, W, 1, "frame")
+        assert (p.value, mem) == (f.ctypes.data, 0) and stride >= W
+        assert stride == (W if H == 1 else f.strides[0])
+    bgr = np.zeros((5, 8, 3), np.uint8)[1:2, 2:3]
+    assert _capi.frame_ptr(bgr, 1, 1, 3, "frame")[1] == 3
+    with pytest.raises(ValueError):
+        _capi.frame_ptr(canvas[:, ::2], 15, 27, 1, "frame")     # pixels 2 bytes apart
+    with pytest.raises(ValueError):
+        _capi.frame_ptr(np.zeros((4, 1, 4), np.uint8)[..., ::2], 4, 1, 2, "frame")
 
 
 def test_bad_options_are_refused(library):

@@ -81,11 +81,12 @@ def frame_ptr(x, rows, width, channels, what, expected=None, unpacked="pixels ha
     if str(x.dtype).replace("torch.", "") != "uint8":
         raise TypeError("%s has to be uint8" % what)
     ptr, strides, mem = _memory(x)
-    packed = strides[1] == channels and (channels == 1 or strides[2] == 1)
+    # the stride of an axis of length 1 says nothing (numpy leaves a slice's there): it is not looked at
+    packed = (width == 1 or strides[1] == channels) and (channels == 1 or strides[2] == 1)
     if not packed or (rows > 1 and strides[0] < channels * width):
         raise ValueError("%s: %s" % (what, unpacked))
     _drain(x)
-    return C.c_void_p(ptr), strides[0], mem
+    return C.c_void_p(ptr), strides[0] if rows > 1 else channels * width, mem
 
 
 def contiguous_ptr(out):
