@@ -53,6 +53,10 @@
  * map they are functions of is: vsg_render_persistence_image, vsg_render_persistence_frame and
  * vsg_render_persistence_graph return, for every pixel side and for every pair of touching level-0
  * regions, the number of hierarchy levels at which the two sides are still different regions.
+ * What a boundary benchmark counts within a distance tolerance is offered as integers:
+ * vsg_render_boundary_distance is the exact squared distance transform of a level's edges, and
+ * vsg_render_boundary_benchmark the matched boundary pixels of every level against a ground-truth label
+ * image; the quotients (precision, recall, F) are left to the caller.
  * Appearance descriptors (Lab histograms, the hierarchical stage's) are not offered; the exact colour sums
  * of every group of a level and the mean-colour picture are: vsg_render_level_colors and
  * vsg_render_mean_frame.
@@ -750,6 +754,81 @@ typedef struct vsg_render_contour_stats {
   int rounds, launches;
 } vsg_render_contour_stats;               /* 64 bytes */
 int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s);
+
+/* ---- Boundary distance: the exact distance transform of a level's edges, boundary scores of all levels ----
+ *
+ * Boundary precision and recall over all levels are functions of the persistence plane only at tolerance zero;
+ * every published benchmark matches boundaries within a distance.  These calls give the distance, and the
+ * matched counts of every hierarchy level at a tolerance, in integers.
+ *
+ * Edge set of a plane.  E(P) = { (x, y) : P(x, y) != P(x+1, y) with x+1 < W, or P(x, y) != P(x, y+1) with
+ * y+1 < H }, -1 counting as a value: the reference's edge rule, the pixels highlight_edges blackens.
+ * The squared distance.  D(x, y) = min over (u, v) in E of (x - u)^2 + (y - v)^2, an int32; it is 0 exactly on
+ * E.  D is VSG_RENDER_DISTANCE_NONE everywhere when E is empty.  A handle is at most 32768 x 32768, so every
+ * finite D is at most 2 * 32767^2 = 2147352578, below VSG_RENDER_DISTANCE_NONE.  There are no floats in it
+ * and no approximation: D is the exact Euclidean distance transform, squared.
+ *
+ * vsg_render_boundary_distance.  P is the plane of vsg_render_id_image(level): the same decode, hierarchy
+ * bookkeeping, level rules, refusals and vector-only handling.  E = E(P), which is exactly Q > level of the
+ * persistence plane.  D is written as W * H int32 with rows W apart to out_int32 in mem_out memory.  A null
+ * handle, a null output or an unknown memory kind is VSG_ERR_INVALID, answered before the handle is
+ * dereferenced.  On every refusal the output is untouched.
+ *
+ * vsg_render_boundary_benchmark.  `other` is a label plane B with the rules of vsg_render_level_overlap: H
+ * rows of W int32 in mem_other memory, other_pitch values apart (0 means W), every int32 legal.
+ * B' = max(B, -1): all negative values are one "void" value.  G = E(B').  L, the hierarchy and Q are those of
+ * the persistence calls, the L > 65535 refusal and the ancestor table's refusals included.  With
+ * T = tolerance_sq the call returns one record per l in [0, L):
+ *   seg_edges[l]   = #{ p : Q(p) > l }                        the edge pixels of level l
+ *   seg_matched[l] = #{ p : Q(p) > l and D_G(p) <= T }        of those, the ones within sqrt(T) of G
+ *   gt_edges[l]    = |G|                                      the same at every level
+ *   gt_matched[l]  = #{ p in G : D_l(p) <= T }                D_l the distance to { Q > l }
+ * so that precision = seg_matched / seg_edges and recall = gt_matched / gt_edges.  Two identities make the
+ * work independent of L: seg_matched[l] counts Q > l over the pixels with D_G <= T, one distance transform and
+ * one histogram of Q; and D_l(p) <= T holds exactly when M(p) > l with M(p) = max{ Q(q) : |p - q|^2 <= T },
+ * the disc maximum of Q, taken at the pixels of G only.  The number of launches of a call does not depend on L.
+ * tolerance_sq outside [0, VSG_RENDER_MAX_TOLERANCE_SQ] is VSG_ERR_INVALID, answered without a device.
+ * *num_levels is always set on VSG_OK and when capacity_levels is too small; in that case the call fails with
+ * VSG_ERR_INVALID and touches no output.  scores == NULL with capacity_levels 0 asks for the count only
+ * (VSG_OK; needs the device).  A null handle, a null count pointer, a null `other`, an unknown memory kind or
+ * a pitch below W is VSG_ERR_INVALID, answered before the handle is used for device work.  The call paints
+ * the persistence plane internally: vsg_render_last_persistence_stats then describes that.
+ *
+ * When an edge set is empty the call stops after counting it: D is filled with VSG_RENDER_DISTANCE_NONE, or
+ * both matched counts are 0.  Vector-only descs are scan converted at the handle's size first.  Every call
+ * returns after its stream work has finished. */
+#define VSG_RENDER_DISTANCE_NONE 0x7fffffff
+#define VSG_RENDER_MAX_TOLERANCE_SQ 4096
+int vsg_render_boundary_distance(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
+                                 int32_t* out_int32, int mem_out);
+
+typedef struct vsg_render_boundary_score {   /* 32 bytes, no padding */
+  int64_t seg_edges;     /* pixels with Q > l                                                          */
+  int64_t seg_matched;   /* of those, pixels whose squared distance to the nearest pixel of G is
+                          * <= tolerance_sq                                                            */
+  int64_t gt_edges;      /* |G|; the same at every level                                               */
+  int64_t gt_matched;    /* pixels of G whose squared distance to the nearest pixel with Q > l is
+                          * <= tolerance_sq                                                            */
+} vsg_render_boundary_score;
+int vsg_render_boundary_benchmark(vsg_render* h, const uint8_t* seg, size_t seg_len,
+                                  const int32_t* other, size_t other_pitch, int mem_other, int tolerance_sq,
+                                  vsg_render_boundary_score* scores, size_t capacity_levels, size_t* num_levels,
+                                  int mem_out);
+
+/* What the last boundary distance or boundary benchmark call of the handle did.  levels: L for the benchmark
+ * call, 0 for the distance call.  edge_pixels: |E| for the distance call, #{Q > 0} for the benchmark call.
+ * other_edge_pixels: |G|, or 0.  max_distance: the largest finite D the distance call wrote, or 0.  Device
+ * times are HIP events around the stages, and a stage that did not run reports 0: plane_us, making the plane
+ * (clear and fill; with the persistence plane and the upload of a host B for the benchmark call);
+ * classify_us, k_dist_classify; columns_us, k_dist_columns; rows_us, k_dist_rows; match_us, k_dist_match,
+ * k_dist_disc and k_dist_scores.  launches is a function of where the buffers are, of how the plane is made
+ * and of whether the classified edge set is empty, not of L. */
+typedef struct vsg_render_distance_stats {
+  int64_t levels, edge_pixels, other_edge_pixels, max_distance;
+  float plane_us, classify_us, columns_us, rows_us, match_us;
+  int launches;
+} vsg_render_distance_stats;                /* 56 bytes */
+int vsg_render_last_distance_stats(vsg_render* h, vsg_render_distance_stats* s);
 
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */

@@ -55,6 +55,20 @@
 // components, for every frame and prints
 // level_contours_count=<sum> level_contours_fnv1a32=<hash of every frame's records, then its vertices' bytes>.
 //
+//   --boundary_distance <level>
+// asks vsg_render_boundary_distance for the exact squared distance of every pixel to that level's nearest
+// edge pixel, for every frame, and prints a line
+// boundary_distance_level=<level> boundary_distance_edge_pixels=<sum> boundary_distance_max=<largest finite
+// distance of any frame> boundary_distance_fnv1a32=<hash of every frame's plane bytes>.
+//
+//   --boundary_benchmark <tolerance_sq>
+// asks vsg_render_boundary_benchmark, for every frame after the first, for the boundary records of every
+// hierarchy level against the previous frame's level-0 id image (fetched with vsg_render_id_image into host
+// memory), boundaries matching within sqrt(tolerance_sq) pixels, and prints a line
+// boundary_benchmark_levels=<L of the last frame> boundary_seg_edges=<sum> boundary_seg_matched=<sum>
+// boundary_gt_edges=<sum> boundary_gt_matched=<sum> boundary_benchmark_fnv1a32=<hash of every compared
+// frame's records>.
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -727,6 +741,100 @@ class LevelOverlapSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --boundary_distance and --boundary_benchmark: the squared distance to a level's edges of every frame
+// (vsg_render_boundary_distance), and the boundary records of all levels of every frame after the first
+// against the previous frame's level-0 id image (vsg_render_boundary_benchmark).  level < 0 or
+// tolerance_sq < 0: that half is off.
+class BoundaryDistanceSinkUnit : public VideoUnit {
+ public:
+  BoundaryDistanceSinkUnit(int level, int tolerance_sq, int device)
+      : level_(level), tolerance_sq_(tolerance_sq), device_(device) {}
+  ~BoundaryDistanceSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    plane_.resize((size_t)s.frame_width() * s.frame_height());
+    previous_.resize(plane_.size());
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    if (level_ >= 0) {
+      VF_CHECK(vsg_render_boundary_distance(render_, seg, desc.wire.size(), level_, plane_.data(), VSG_MEM_HOST) ==
+                   VSG_OK,
+               vsg_render_last_error());
+      vsg_render_distance_stats st;
+      VF_CHECK(vsg_render_last_distance_stats(render_, &st) == VSG_OK, vsg_render_last_error());
+      edge_pixels_ += (long)st.edge_pixels;
+      max_distance_ = std::max(max_distance_, (long)st.max_distance);
+      Hash(&distance_hash_, plane_.data(), plane_.size() * sizeof(int32_t));
+    }
+    if (tolerance_sq_ >= 0) {
+      if (have_previous_) {
+        // one call while the records fit: a call whose capacity is too small has done most of its work
+        // already, and says how many levels there are
+        size_t nl = 0;
+        if (scores_.size() < 32) scores_.resize(32);
+        int rc = vsg_render_boundary_benchmark(render_, seg, desc.wire.size(), previous_.data(), 0, VSG_MEM_HOST,
+                                               tolerance_sq_, scores_.data(), scores_.size(), &nl, VSG_MEM_HOST);
+        if (rc != VSG_OK && nl > scores_.size()) {
+          scores_.resize(nl);
+          rc = vsg_render_boundary_benchmark(render_, seg, desc.wire.size(), previous_.data(), 0, VSG_MEM_HOST,
+                                             tolerance_sq_, scores_.data(), scores_.size(), &nl, VSG_MEM_HOST);
+        }
+        VF_CHECK(rc == VSG_OK, vsg_render_last_error());
+        for (size_t l = 0; l < nl; ++l) {
+          sums_[0] += (long)scores_[l].seg_edges;
+          sums_[1] += (long)scores_[l].seg_matched;
+          sums_[2] += (long)scores_[l].gt_edges;
+          sums_[3] += (long)scores_[l].gt_matched;
+        }
+        levels_ = (int)nl;
+        Hash(&benchmark_hash_, scores_.data(), nl * sizeof(vsg_render_boundary_score));
+      }
+      VF_CHECK(vsg_render_id_image(render_, seg, desc.wire.size(), 0, previous_.data(), VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+      have_previous_ = true;
+    }
+    output->push_back(input);
+  }
+  int level() const { return level_; }
+  int tolerance_sq() const { return tolerance_sq_; }
+  int levels() const { return levels_; }
+  long edge_pixels() const { return edge_pixels_; }
+  long max_distance() const { return max_distance_; }
+  const long* sums() const { return sums_; }
+  uint32_t distance_hash() const { return distance_hash_; }
+  uint32_t benchmark_hash() const { return benchmark_hash_; }
+
+ private:
+  static void Hash(uint32_t* hash, const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      *hash ^= b[k];
+      *hash *= 16777619u;
+    }
+  }
+  int level_, tolerance_sq_, device_, seg_idx_ = -1, levels_ = 0;
+  vsg_render* render_ = nullptr;
+  bool have_previous_ = false;
+  std::vector<int32_t> plane_, previous_;
+  std::vector<vsg_render_boundary_score> scores_;
+  long edge_pixels_ = 0, max_distance_ = 0, sums_[4] = {0, 0, 0, 0};
+  uint32_t distance_hash_ = 2166136261u, benchmark_hash_ = 2166136261u;
+};
+
 // --level_colors: the colour table of a level's regions, or of their connected components, in the video's
 // frame (vsg_render_level_colors) and the level painted in mean colours (vsg_render_mean_frame): the
 // records, then the 3 * width pixel bytes of every picture row, of every frame.
@@ -922,6 +1030,11 @@ struct Flags {
   // (N4, or N8 with --components_n8) with --contours_components
   int level_contours = -1;
   bool contours_components = false;
+  // vsg_render_boundary_distance at this level for every frame; < 0: off
+  int boundary_distance = -1;
+  // vsg_render_boundary_benchmark with this tolerance_sq for every frame after the first, against the
+  // previous frame's level-0 id image; < 0: off
+  int boundary_benchmark = -1;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -1016,6 +1129,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_colors") f->level_colors = atoi(v.c_str());
     else if (a == "colors_components") f->colors_components = bv;
     else if (a == "level_contours") f->level_contours = atoi(v.c_str());
+    else if (a == "boundary_distance") f->boundary_distance = atoi(v.c_str());
+    else if (a == "boundary_benchmark") f->boundary_benchmark = atoi(v.c_str());
     else if (a == "contours_components") f->contours_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
@@ -1276,6 +1391,12 @@ int main(int argc, char** argv) {
     contours_sink->AttachTo(input);
     input = contours_sink.get();
   }
+  std::unique_ptr<BoundaryDistanceSinkUnit> distance_sink;
+  if (FLAGS.boundary_distance >= 0 || FLAGS.boundary_benchmark >= 0) {
+    distance_sink.reset(new BoundaryDistanceSinkUnit(FLAGS.boundary_distance, FLAGS.boundary_benchmark, FLAGS.device));
+    distance_sink->AttachTo(input);
+    input = distance_sink.get();
+  }
 
   std::unique_ptr<SegmentationRenderUnit> render_unit;   // seg_tree.cpp:254-294
   RenderHashSinkUnit render_sink;
@@ -1350,6 +1471,18 @@ int main(int argc, char** argv) {
   if (contours_sink) {
     std::printf("level_contours_count=%ld level_contours_fnv1a32=%08x\n", contours_sink->contours(),
                 contours_sink->hash());
+  }
+  if (distance_sink && distance_sink->level() >= 0) {
+    std::printf("boundary_distance_level=%d boundary_distance_edge_pixels=%ld boundary_distance_max=%ld "
+                "boundary_distance_fnv1a32=%08x\n",
+                distance_sink->level(), distance_sink->edge_pixels(), distance_sink->max_distance(),
+                distance_sink->distance_hash());
+  }
+  if (distance_sink && distance_sink->tolerance_sq() >= 0) {
+    const long* sums = distance_sink->sums();
+    std::printf("boundary_benchmark_levels=%d boundary_seg_edges=%ld boundary_seg_matched=%ld boundary_gt_edges=%ld "
+                "boundary_gt_matched=%ld boundary_benchmark_fnv1a32=%08x\n",
+                distance_sink->levels(), sums[0], sums[1], sums[2], sums[3], distance_sink->benchmark_hash());
   }
   std::fprintf(stderr, "__SEGMENTATION_FINISHED__\n");
   return sink.frames() == frames ? 0 : 3;

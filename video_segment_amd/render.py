@@ -119,6 +119,16 @@ class VsgRenderContourStats(_capi.Structure):
     ]
 
 
+class VsgRenderDistanceStats(_capi.Structure):
+    _fields_ = [
+        ("levels", C.c_int64), ("edge_pixels", C.c_int64), ("other_edge_pixels", C.c_int64),
+        ("max_distance", C.c_int64),
+        ("plane_us", C.c_float), ("classify_us", C.c_float), ("columns_us", C.c_float), ("rows_us", C.c_float),
+        ("match_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 # vsg_render_level_region: 56 bytes, no padding
 LEVEL_REGION_DTYPE = np.dtype([
     ("id", np.int32), ("first_interval", np.int32), ("num_intervals", np.int32), ("area", np.int32),
@@ -211,6 +221,17 @@ LEVEL_CONTOUR_DTYPE = np.dtype([
 assert LEVEL_CONTOUR_DTYPE.itemsize == 48
 LEVEL_CONTOUR_WORDS = 12
 
+# vsg_render_boundary_score: 32 bytes, no padding
+BOUNDARY_SCORE_DTYPE = np.dtype([
+    ("seg_edges", np.int64), ("seg_matched", np.int64), ("gt_edges", np.int64), ("gt_matched", np.int64),
+])
+assert BOUNDARY_SCORE_DTYPE.itemsize == 32
+BOUNDARY_SCORE_WORDS = 4
+
+# VSG_RENDER_DISTANCE_NONE, VSG_RENDER_MAX_TOLERANCE_SQ
+DISTANCE_NONE = 0x7fffffff
+MAX_TOLERANCE_SQ = 4096
+
 # VSG_RENDER_CONNECT_N4 / _N8 (SegmentationDesc::N4_CONNECT / N8_CONNECT)
 N4 = 1
 N8 = 2
@@ -230,6 +251,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_last_persistence_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
     "vsg_render_level_contours", "vsg_render_last_contour_stats",
+    "vsg_render_boundary_distance", "vsg_render_boundary_benchmark", "vsg_render_last_distance_stats",
 ]
 
 
@@ -296,6 +318,10 @@ def lib():
     L.vsg_render_level_contours.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t,
                                             C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_contour_stats.argtypes = [vp, C.POINTER(VsgRenderContourStats)]
+    L.vsg_render_boundary_distance.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_int]
+    L.vsg_render_boundary_benchmark.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp,
+                                                C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_distance_stats.argtypes = [vp, C.POINTER(VsgRenderDistanceStats)]
     _handle = L
     return L
 
@@ -888,6 +914,62 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_contour_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def boundary_distance(self, seg_bytes, level=0, out=None):
+        """The exact squared Euclidean distance from every pixel to the nearest edge pixel of hierarchy level
+        `level`: H x W int32, 0 exactly where id_image(seg, level) differs from its right or below neighbour,
+        DISTANCE_NONE everywhere when the level has no edge.  out: a contiguous int32 numpy array or torch CUDA
+        tensor to fill instead of a new numpy array."""
+        if out is None:
+            out = np.empty((self.H, self.W), np.int32)
+        if tuple(out.shape) != (self.H, self.W) or str(out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("out has to be %d x %d int32" % (self.H, self.W))
+        p, mem = _capi.contiguous_ptr(out)
+        seg_bytes = bytes(seg_bytes)
+        check(lib().vsg_render_boundary_distance(self.h, seg_bytes, len(seg_bytes), int(level), p, mem))
+        return out
+
+    def boundary_benchmark(self, seg_bytes, other, tolerance_sq, out=None):
+        """What a boundary benchmark counts at every level of the desc's hierarchy against the label plane
+        `other` (as in level_overlap; all negative values are one void label), boundaries matching within
+        sqrt(tolerance_sq) pixels: a BOUNDARY_SCORE_DTYPE array with one record per level, seg_edges and
+        seg_matched (the level's edge pixels, and those near an edge of `other`), gt_edges and gt_matched (the
+        edge pixels of `other`, and those near an edge of the level).  tolerance_sq: an integer in
+        [0, MAX_TOLERANCE_SQ].  out: a buffer to fill instead, a BOUNDARY_SCORE_DTYPE array or a (capacity, 4)
+        int64 torch CUDA tensor; the filled part of it is returned.  See boundary_scores."""
+        if other is None:
+            raise ValueError("other is needed")
+        seg_bytes = bytes(seg_bytes)
+        po, pitch, mem_other = self._other_ptr(other)
+        nl = C.c_size_t()
+        if out is None:
+            # one call when the guess holds: a call that finds its capacity too small has already painted the
+            # persistence plane and classified `other`, most of its cost, and says how many levels there are
+            guess = np.empty(max(getattr(self, "_benchmark_levels", 0), 32), BOUNDARY_SCORE_DTYPE)
+            p, mem = _capi.contiguous_ptr(guess)
+            rc = lib().vsg_render_boundary_benchmark(self.h, seg_bytes, len(seg_bytes), po, pitch, mem_other,
+                                                     int(tolerance_sq), p, guess.shape[0], C.byref(nl), mem)
+            if rc == VSG_OK or nl.value <= guess.shape[0]:
+                check(rc)
+                self._benchmark_levels = nl.value
+                return guess[:nl.value].copy()
+            self._benchmark_levels = nl.value
+            out = np.empty(nl.value, BOUNDARY_SCORE_DTYPE)
+        if _capi.is_torch(out):
+            if out.dim() != 2 or out.shape[1] != BOUNDARY_SCORE_WORDS or str(out.dtype) != "torch.int64":
+                raise ValueError("out has to be (capacity, %d) int64" % BOUNDARY_SCORE_WORDS)
+        elif out.dtype != BOUNDARY_SCORE_DTYPE or out.ndim != 1:
+            raise ValueError("out has to be a one-dimensional BOUNDARY_SCORE_DTYPE array")
+        p, mem = _capi.contiguous_ptr(out)
+        check(lib().vsg_render_boundary_benchmark(self.h, seg_bytes, len(seg_bytes), po, pitch, mem_other,
+                                                  int(tolerance_sq), p, out.shape[0], C.byref(nl), mem))
+        return out[:nl.value]
+
+    def last_distance_stats(self):
+        """vsg_render_last_distance_stats of the last boundary_distance / boundary_benchmark call, as a dict."""
+        s = VsgRenderDistanceStats()
+        check(lib().vsg_render_last_distance_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""
         s = VsgRenderVectorStats()
@@ -916,6 +998,24 @@ def overlap_scores(rows, pairs):
     ue_sum = int(np.minimum(count, inside - count).sum())
     return {"n": n, "asa_sum": asa_sum, "ue_sum": ue_sum,
             "asa": asa_sum / n if n else None, "ue": ue_sum / n if n else None}
+
+
+def boundary_scores(scores):
+    """Boundary precision, recall and F of every level from the host array of boundary_benchmark: a dict of the
+    float64 arrays precision = seg_matched / seg_edges, recall = gt_matched / gt_edges and
+    f = 2 precision recall / (precision + recall), each 0 where its denominator is 0, and best_level, the
+    lowest level with the largest f (None without a level).  Host numpy only."""
+    scores = np.asarray(scores)
+
+    def quotient(a, b):
+        a, b = a.astype(np.float64), b.astype(np.float64)
+        return np.divide(a, b, out=np.zeros(a.shape, np.float64), where=b != 0)
+
+    precision = quotient(scores["seg_matched"], scores["seg_edges"])
+    recall = quotient(scores["gt_matched"], scores["gt_edges"])
+    f = quotient(2 * precision * recall, precision + recall)
+    return {"precision": precision, "recall": recall, "f": f,
+            "best_level": int(np.argmax(f)) if len(f) else None}
 
 
 def color_moments(records):

@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip, distance.hip),
 // called by render_capi.cpp.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -458,6 +458,53 @@ void LaunchContourTable(const unsigned long long* ckeys_sorted, const uint32_t* 
 void LaunchContourCopy(const int32_t* records, const int32_t* vertices, uint32_t capacity, uint32_t n,
                        uint32_t capacity_records, uint32_t capacity_vertices, int32_t* records_out,
                        int32_t* vertices_out, const ContourStatus* status, hipStream_t stream);
+
+// ---- boundary distance (distance.hip): the squared distance to an edge set, the boundary benchmark ------
+
+constexpr int kDistChunkRows = 32;        // rows of a column that one word of the edge set holds
+constexpr int kBoundaryScoreWords = 4;    // vsg_render_boundary_score as int64 words
+constexpr int32_t kDistanceNone = 0x7fffffff;
+
+enum DistFlag {
+  DIST_FLAG_RANGE = 1,   // a value of the persistence plane was outside [0, levels]
+};
+
+// Written by the distance kernels; read by the host after the classify pass and at the end of a call.
+struct DistStatus {
+  unsigned long long edge_pixels;   // pixels of the classified plane's edge set
+  uint32_t max_distance;            // the largest finite value k_dist_rows wrote
+  uint32_t flags;
+};
+
+// Chunks of kDistChunkRows rows in a frame of `height` rows; floor(sqrt(tolerance_sq)).
+int DistChunks(int height);
+int DistRadius(int tolerance_sq);
+// The edge set of the H x W plane (rows `pitch` values apart): the pixels that differ from their in-frame
+// right or below neighbour, every value counting (clamp: all negative values as one).  words[c * W + x] has
+// bit r set when (x, kDistChunkRows * c + r) is one, DistChunks(height) x W words, every one written;
+// status->edge_pixels += their number.
+void LaunchDistClassify(const int32_t* plane, size_t pitch, int width, int height, bool clamp, uint32_t* words,
+                        DistStatus* status, hipStream_t stream);
+// gsq[y * W + x] = the square of the vertical distance from (x, y) to the nearest pixel of the edge set in
+// column x, kDistanceNone when the column has none.
+void LaunchDistColumns(const uint32_t* words, int width, int height, int32_t* gsq, hipStream_t stream);
+// out[y * W + x] = min over u of (x - u)^2 + gsq[y * W + u], kDistanceNone when the row of gsq has nothing
+// else; status->max_distance = the largest finite one.  The row is staged in dynamic LDS: width * 4 bytes and
+// 4 for every 32 columns.
+hipError_t LaunchDistRows(const int32_t* gsq, int width, int height, int32_t* out, DistStatus* status,
+                          hipStream_t stream);
+// hist_all[v] += 1 for every pixel of q (rows W apart) with v = q > 0, hist_near[v] += 1 for those with
+// d <= tolerance_sq as well (d null: none, hist_near is not looked at).  levels + 1 entries each.
+void LaunchDistMatch(const int32_t* q, const int32_t* d, int width, int height, int levels, int tolerance_sq,
+                     uint32_t* hist_all, uint32_t* hist_near, DistStatus* status, hipStream_t stream);
+// hist[m] += 1 for every pixel of the edge set `words` with m = max of q over the pixels at most
+// sqrt(tolerance_sq) away > 0.  tolerance_sq in [0, 4096].
+void LaunchDistDisc(const int32_t* q, const uint32_t* words, int width, int height, int levels, int tolerance_sq,
+                    uint32_t* hist, DistStatus* status, hipStream_t stream);
+// scores[l] = {sum over p > l of hist_all[p], of hist_near[p], status->edge_pixels, sum of hist_disc[p]} as
+// int64, l in [0, levels).
+void LaunchDistScores(const uint32_t* hist_all, const uint32_t* hist_near, const uint32_t* hist_disc, int levels,
+                      const DistStatus* status, long long* scores, hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -23,6 +23,7 @@ using vsg_render_impl::BoundStatus;
 using vsg_render_impl::ColorStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::ContourStatus;
+using vsg_render_impl::DistStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
 using vsg_render_impl::OvlStatus;
@@ -42,6 +43,8 @@ enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_ST
 enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
 enum ContourStage { CNT_CLASSIFY = 0, CNT_TRACE, CNT_TABLE, CNT_STAGES };
+// DST_PLANE: the upload of a host label plane
+enum DistStage { DST_PLANE = 0, DST_CLASSIFY, DST_COLUMNS, DST_ROWS, DST_MATCH, DST_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -340,7 +343,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock, tclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock, tclock, dclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -393,6 +396,10 @@ struct vsg_render {
   // offsets); the records; the status words and the pinned block the status and host outputs come back
   // through
   Block d_cont_mask, d_cont_offset, d_cont_cracks, d_cont_slots, d_cont_records, d_cont_status, h_cont;
+  // boundary distance: the edge set's words; the columns' squared distances; D of a host output or of the
+  // other plane's edge set; the three histograms; the records of a host output; the status words and the
+  // pinned block they come back through
+  Block d_dist_words, d_dist_gsq, d_dist_out, d_dist_hist, d_dist_scores, d_dist_status, h_dist;
   int64_t allocations = 0;
   vsg_render_stats stats;
   vsg_render_vector_stats vstats;
@@ -404,6 +411,7 @@ struct vsg_render {
   vsg_render_persistence_stats pstats;
   vsg_render_color_stats kstats;
   vsg_render_contour_stats tstats;
+  vsg_render_distance_stats dstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -1003,6 +1011,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->tclock.Create(CNT_STAGES + 1);
     h->h_cont.pinned = true;
     std::memset(&h->tstats, 0, sizeof(h->tstats));
+    h->dclock.Create(DST_STAGES + 1);
+    h->h_dist.pinned = true;
+    std::memset(&h->dstats, 0, sizeof(h->dstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -2716,6 +2727,227 @@ int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s) {
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->tstats;
+  });
+}
+
+int vsg_render_boundary_distance(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int32_t* out,
+                                 int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(VSG_RENDER_DISTANCE_NONE == kDistanceNone, "the kernels' none is the header's");
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!out) Throw(VSG_ERR_INVALID, "out is null");
+    CheckMem(mem_out, "out");
+    const int W = h->W, H = h->H;
+    const size_t n = (size_t)W * H, bytes = n * sizeof(int32_t);
+    DeviceGuard guard(h->device);
+    vsg_render_distance_stats& ds = h->dstats;
+    std::memset(&ds, 0, sizeof(ds));
+
+    // ---- P, as vsg_render_id_image paints it, and its edge set ----
+    h->d_ids.Reserve(bytes, &h->allocations);
+    const bool vector = PaintIds(h, seg, seg_len, level, h->d_ids.As<uint32_t>(),
+                                 [](int mapped) { return (uint32_t)mapped; });
+    h->d_dist_words.Reserve((size_t)DistChunks(H) * W * sizeof(uint32_t), &h->allocations);
+    h->d_dist_status.Reserve(sizeof(DistStatus), &h->allocations);
+    h->h_dist.Reserve(2 * sizeof(DistStatus), &h->allocations);
+    uint32_t* words = h->d_dist_words.As<uint32_t>();
+    DistStatus* status = h->d_dist_status.As<DistStatus>();
+    DistStatus* seen = h->h_dist.As<DistStatus>();   // [0] after the classify pass, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(DistStatus));
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(DistStatus), h->stream));
+    h->dclock.Begin(h->stream);
+    LaunchDistClassify(h->d_ids.As<int32_t>(), (size_t)W, W, H, false, words, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->dclock.Mark(DST_CLASSIFY);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(DistStatus), hipMemcpyDeviceToHost, h->stream));
+    int launches = 3;
+    h->FinishStats();   // the number of edge pixels decides what runs below
+    if (vector) h->CheckVector();
+    float us[DST_STAGES];
+    h->dclock.Read(us, DST_STAGES);
+    ds.plane_us = h->stats.clear_us + h->stats.fill_us;
+    ds.classify_us = us[DST_CLASSIFY];
+    ds.edge_pixels = (int64_t)seen[0].edge_pixels;
+
+    if (ds.edge_pixels == 0) {
+      // ---- no edge: none everywhere ----
+      if (mem_out == VSG_MEM_HOST) {
+        std::fill(out, out + n, (int32_t)VSG_RENDER_DISTANCE_NONE);
+      } else {
+        VSG_HIP(hipMemsetD32Async(reinterpret_cast<hipDeviceptr_t>(out), VSG_RENDER_DISTANCE_NONE, n, h->stream));
+        VSG_HIP(hipStreamSynchronize(h->stream));
+        ++launches;
+      }
+    } else {
+      // ---- columns, then rows ----
+      h->d_dist_gsq.Reserve(bytes, &h->allocations);
+      int32_t* d = out;   // device output: written in place
+      if (mem_out == VSG_MEM_HOST) {
+        h->d_dist_out.Reserve(bytes, &h->allocations);
+        d = h->d_dist_out.As<int32_t>();
+      }
+      h->dclock.Begin(h->stream);
+      LaunchDistColumns(words, W, H, h->d_dist_gsq.As<int32_t>(), h->stream);
+      VSG_HIP(hipGetLastError());
+      h->dclock.Mark(DST_COLUMNS);
+      VSG_HIP(LaunchDistRows(h->d_dist_gsq.As<int32_t>(), W, H, d, status, h->stream));
+      h->dclock.Mark(DST_ROWS);
+      launches += 3;
+      if (mem_out == VSG_MEM_HOST) {
+        VSG_HIP(hipMemcpyAsync(out, d, bytes, hipMemcpyDeviceToHost, h->stream));
+        ++launches;
+      }
+      VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(DistStatus), hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      h->dclock.Read(us, DST_STAGES);
+      ds.columns_us = us[DST_COLUMNS];
+      ds.rows_us = us[DST_ROWS];
+      ds.max_distance = (int64_t)seen[1].max_distance;
+    }
+    h->stats.launches += launches;
+    h->stats.device_allocations = h->allocations;
+    ds.launches = h->stats.launches;
+  });
+}
+
+int vsg_render_boundary_benchmark(vsg_render* h, const uint8_t* seg, size_t seg_len, const int32_t* other,
+                                  size_t other_pitch, int mem_other, int tolerance_sq,
+                                  vsg_render_boundary_score* scores, size_t capacity_levels, size_t* num_levels,
+                                  int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_boundary_score) == kBoundaryScoreWords * sizeof(int64_t), "moved as int64 words");
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_levels) Throw(VSG_ERR_INVALID, "the count pointer is null");
+    if (!other) Throw(VSG_ERR_INVALID, "other is null");
+    if (mem_other != VSG_MEM_HOST && mem_other != VSG_MEM_DEVICE) {
+      Throw(VSG_ERR_INVALID, "mem_other is neither VSG_MEM_HOST nor VSG_MEM_DEVICE");
+    }
+    CheckMem(mem_out, "scores");
+    if (tolerance_sq < 0 || tolerance_sq > VSG_RENDER_MAX_TOLERANCE_SQ) {
+      Throw(VSG_ERR_INVALID, "tolerance_sq " + std::to_string(tolerance_sq) + " is outside [0, " +
+                                 std::to_string(VSG_RENDER_MAX_TOLERANCE_SQ) + "]");
+    }
+    if (!scores && capacity_levels != 0) Throw(VSG_ERR_INVALID, "scores is null");
+    const int W = h->W, H = h->H;
+    if (other_pitch != 0 && other_pitch < (size_t)W) {
+      Throw(VSG_ERR_INVALID, "the pitch of other, " + std::to_string(other_pitch) + ", is below the width " +
+                                 std::to_string(W));
+    }
+    const size_t pitch = other_pitch ? other_pitch : (size_t)W;
+    const size_t n = (size_t)W * H, bytes = n * sizeof(int32_t);
+    DeviceGuard guard(h->device);
+    vsg_render_distance_stats& ds = h->dstats;
+    std::memset(&ds, 0, sizeof(ds));
+    std::memset(&h->pstats, 0, sizeof(h->pstats));
+
+    // ---- Q, as vsg_render_persistence_image makes it ----
+    h->d_pq.Reserve(bytes, &h->allocations);
+    const int32_t* q = h->d_pq.As<int32_t>();
+    int launches = 0, levels = 0;
+    const bool vector = PaintPersistence(h, seg, seg_len, h->d_pq.As<int32_t>(), (size_t)W, &levels, &launches);
+    const size_t L = (size_t)levels, bins = L + 1;
+
+    // ---- B: where it is, or through the pinned block to the device, rows packed; G ----
+    h->d_dist_words.Reserve((size_t)DistChunks(H) * W * sizeof(uint32_t), &h->allocations);
+    h->d_dist_status.Reserve(sizeof(DistStatus), &h->allocations);
+    h->h_dist.Reserve(2 * sizeof(DistStatus), &h->allocations);
+    h->d_dist_hist.Reserve(3 * bins * sizeof(uint32_t), &h->allocations);
+    uint32_t* words = h->d_dist_words.As<uint32_t>();
+    uint32_t* hist = h->d_dist_hist.As<uint32_t>();   // all, near, disc
+    DistStatus* status = h->d_dist_status.As<DistStatus>();
+    DistStatus* seen = h->h_dist.As<DistStatus>();   // [0] after the classify pass, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(DistStatus));
+    const int32_t* label_plane = other;
+    size_t label_pitch = pitch;
+    h->dclock.Begin(h->stream);
+    if (mem_other == VSG_MEM_HOST) {
+      h->h_other.Reserve(bytes, &h->allocations);
+      h->d_other.Reserve(bytes, &h->allocations);
+      for (int y = 0; y < H; ++y) {
+        std::memcpy(h->h_other.As<int32_t>() + (size_t)y * W, other + (size_t)y * pitch, (size_t)W * sizeof(int32_t));
+      }
+      VSG_HIP(hipMemcpyAsync(h->d_other.p, h->h_other.p, bytes, hipMemcpyHostToDevice, h->stream));
+      label_plane = h->d_other.As<int32_t>();
+      label_pitch = (size_t)W;
+      ++launches;
+    }
+    h->dclock.Mark(DST_PLANE);
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(DistStatus), h->stream));
+    VSG_HIP(hipMemsetAsync(hist, 0, 3 * bins * sizeof(uint32_t), h->stream));
+    LaunchDistClassify(label_plane, label_pitch, W, H, true, words, status, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->dclock.Mark(DST_CLASSIFY);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(DistStatus), hipMemcpyDeviceToHost, h->stream));
+    launches += 4;
+    FinishPersistence(h, vector, launches);   // the size of G decides what runs below
+    float us[DST_STAGES];
+    h->dclock.Read(us, DST_STAGES);
+    ds.plane_us = h->pstats.plane_us + h->pstats.persist_us + us[DST_PLANE];
+    ds.classify_us = us[DST_CLASSIFY];
+    ds.levels = (int64_t)L;
+    ds.edge_pixels = h->pstats.edge_pixels;
+    ds.other_edge_pixels = (int64_t)seen[0].edge_pixels;
+    ds.launches = h->stats.launches;
+    h->stats.device_allocations = h->allocations;
+    *num_levels = L;
+    if (!scores && capacity_levels == 0) return;   // the count only
+    if (capacity_levels < L) {
+      Throw(VSG_ERR_INVALID, "the hierarchy has " + std::to_string(L) + " levels, scores has room for " +
+                                 std::to_string(capacity_levels));
+    }
+
+    // ---- D_G where G has a pixel; the histograms; the records ----
+    const bool any = seen[0].edge_pixels != 0;
+    const int32_t* dist = nullptr;
+    long long* records = reinterpret_cast<long long*>(scores);   // device output: written in place
+    if (mem_out == VSG_MEM_HOST) {
+      h->d_dist_scores.Reserve(L * sizeof(vsg_render_boundary_score), &h->allocations);
+      records = h->d_dist_scores.As<long long>();
+    }
+    launches = 0;
+    h->dclock.Begin(h->stream);
+    if (any) {
+      h->d_dist_gsq.Reserve(bytes, &h->allocations);
+      h->d_dist_out.Reserve(bytes, &h->allocations);
+      LaunchDistColumns(words, W, H, h->d_dist_gsq.As<int32_t>(), h->stream);
+      VSG_HIP(hipGetLastError());
+      h->dclock.Mark(DST_COLUMNS);
+      VSG_HIP(LaunchDistRows(h->d_dist_gsq.As<int32_t>(), W, H, h->d_dist_out.As<int32_t>(), status, h->stream));
+      h->dclock.Mark(DST_ROWS);
+      dist = h->d_dist_out.As<int32_t>();
+      launches += 2;
+    }
+    LaunchDistMatch(q, dist, W, H, levels, tolerance_sq, hist, hist + bins, status, h->stream);
+    if (any) LaunchDistDisc(q, words, W, H, levels, tolerance_sq, hist + 2 * bins, status, h->stream);
+    LaunchDistScores(hist, hist + bins, hist + 2 * bins, levels, status, records, h->stream);
+    VSG_HIP(hipGetLastError());
+    h->dclock.Mark(DST_MATCH);
+    launches += any ? 3 : 2;
+    if (mem_out == VSG_MEM_HOST) {
+      VSG_HIP(hipMemcpyAsync(scores, records, L * sizeof(vsg_render_boundary_score), hipMemcpyDeviceToHost,
+                             h->stream));
+      ++launches;
+    }
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(DistStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    h->dclock.Read(us, DST_STAGES);
+    ds.columns_us = us[DST_COLUMNS];
+    ds.rows_us = us[DST_ROWS];
+    ds.match_us = us[DST_MATCH];
+    h->stats.launches += launches;
+    h->stats.device_allocations = h->allocations;
+    ds.launches = h->stats.launches;
+    if (seen[1].flags) Throw(VSG_ERR_INTERNAL, "the persistence plane holds a value outside [0, L]");
+  });
+}
+
+int vsg_render_last_distance_stats(vsg_render* h, vsg_render_distance_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->dstats;
   });
 }
 
