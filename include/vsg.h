@@ -135,6 +135,43 @@ typedef struct vsg_merge_paths {
   int64_t conservative_replays;       /* failed stages replayed edge by edge (inert_mode 0)            */
 } vsg_merge_paths;
 
+/* Which branches of the tree replay (csrc/merge_spine.hip RunSpineComponents and what the stage driver
+ * does around it) the last SegmentFullGraph call of a handle took.  Host counts, incremented where the
+ * host already branches: no launch, copy, wait or synchronisation of their own.  A struct beside
+ * vsg_merge_paths so that that one keeps its size.  DESIGN 4.21. */
+typedef struct vsg_spine_paths {
+  int64_t replays;                   /* RunSpineComponents calls that got past the first pool check   */
+  int64_t components;                /* components they were given (sum of K)                         */
+  int64_t nested_replays;            /* ... of them one or more levels down (side clusters)           */
+  int64_t deepest_level;             /* deepest level of the call (0: top level only)                 */
+  int64_t forest_rounds;             /* rounds of the spanning forest launched                        */
+  int64_t forest_rounds_ahead;       /* ... launched before the round in front of them was answered   */
+  int64_t forest_compactions_ahead;  /* edge list compacted, rounds one ahead of the host             */
+  int64_t forest_compactions_sync;   /* edge list compacted, every round answered first               */
+  int64_t forest_lists_refused;      /* a compaction was due but the pool had no room for the lists   */
+  int64_t ranked_by_sampling;        /* Euler tours ranked through the sampled list                   */
+  int64_t ranked_plain;              /* ... by pointer jumping over every arc                         */
+  int64_t rank_sampling_refused;     /* sampling was due but the pool had no room: ranked plain       */
+  int64_t jump_loops_ended_early;    /* the path-maximum loop ended on the device's answer            */
+  int64_t streamed_passes;           /* passes of the streamed spine (prep / scan / chain / verify)   */
+  int64_t streamed_refused;          /* replays whose streamed spine found no room in the pool        */
+  int64_t pool_fallbacks[4];         /* replays given up for lack of pool: at entry, for the edge     */
+                                     /* arrays, for the tour's arrays, for the side clusters' arrays  */
+  int64_t top_level_fallbacks;       /* ... whose components the stage handed to the wave worker      */
+  int64_t nested_fallbacks;          /* ... whose side clusters the level above handed to it          */
+  int64_t assumption_reruns;         /* stages rerun without the replay: only its assumption failed   */
+  int64_t limit_bucket_moves;        /* ... which lowered the bucket from which the replay is skipped */
+  int64_t low_bucket_failures[2];    /* ... in bucket 0 / 1                                           */
+  int64_t low_bucket_skips[2];       /* bucket 0 / 1 went without the replay in this call (cool-down) */
+  int64_t zero_pool_flips;           /* the pool of zeroed counters changed halves                    */
+  int64_t windows_run;               /* stages that are a rank window of a bucket split into several  */
+  int64_t rle_stages;                /* stages that replayed run leaders only                         */
+  int64_t wide_launches;             /* launches of the wide worker (merge_wide.hip)                  */
+  int64_t group_stages;              /* stages over a group of several buckets                        */
+  int64_t sorts_hand;                /* sorts of the merge path done by the hand-written radix sort   */
+  int64_t sorts_library;             /* ... by the library's                                          */
+} vsg_spine_paths;
+
 /* Device memory of the library, per device.  A closed handle leaves its blocks in a process-wide
  * cache and the next handle adopts them (no hipMalloc / hipFree after the first window of a caller
  * that creates a graph per window, dense_seg_graph_interface.h:58-98); the cached, unused bytes are
@@ -197,6 +234,7 @@ int vsg_stream_last_merge_stats(const vsg_stream* s, int64_t* forced_regular_sma
 int vsg_stream_last_timings(const vsg_stream* s, vsg_timings* t);
 int vsg_stream_last_diagnostics(const vsg_stream* s, vsg_diagnostics* d);
 int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out);
+int vsg_stream_last_spine_paths(const vsg_stream* s, vsg_spine_paths* out);
 /* Parity hook: smoothed feature planes of the most recently added frame, W*H*3 f32 BGR
  * interleaved, host memory (PreprocessFeatures output, cpp:164-198). */
 int vsg_stream_last_smoothed(vsg_stream* s, float* out);
@@ -365,6 +403,7 @@ int vsg_graph_merge_stats(const vsg_graph* g, int64_t* forced_regular_small);
 int vsg_graph_timings(const vsg_graph* g, vsg_timings* t);
 int vsg_graph_diagnostics(const vsg_graph* g, vsg_diagnostics* d);
 int vsg_graph_merge_paths(const vsg_graph* g, vsg_merge_paths* out);
+int vsg_graph_spine_paths(const vsg_graph* g, vsg_spine_paths* out);
 
 /* Test hook: the merge path's stable radix sort of (key, value) pairs by the low `end_bit` bits of
  * the keys (csrc/radix_sort.hip), on host arrays of n elements, run on `device`.  The reference sorts
@@ -377,6 +416,17 @@ int vsg_debug_sort_pairs(const uint32_t* keys, const uint32_t* values, int n, in
 int vsg_debug_sort_pairs_timed(const uint32_t* keys, const uint32_t* values, int n, int end_bit,
                                uint32_t* keys_out, uint32_t* values_out, int device, int impl, int reps,
                                double* avg_us);
+/* Test hooks: the merge path's fused scan (csrc/scan_device.h) on host arrays of n elements, with scratch
+ * and a stream of their own, on the caller's current device.  n == 0 launches nothing and leaves the
+ * outputs as they are.
+ *   exclusive_sum       : out[i] = in[0] + ... + in[i - 1] (FusedScan; out may be in), *total = the sum
+ *                         of all, as the scan's finish() receives it.
+ *   runs_of_sorted_keys : RunsOfSortedKeys -- seg_off[r] / seg_cnt[r] = first position / length of run
+ *                         r of equal keys, *num_runs = their number; seg_off and seg_cnt hold n entries,
+ *                         the ones from *num_runs on are left as they are. */
+int vsg_debug_exclusive_sum(const int32_t* in, int n, int32_t* out, int64_t* total);
+int vsg_debug_runs_of_sorted_keys(const uint32_t* keys, int n, int32_t* seg_off, int32_t* seg_cnt,
+                                  int32_t* num_runs);
 
 #ifdef __cplusplus
 }

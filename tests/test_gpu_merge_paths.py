@@ -82,9 +82,8 @@ CASES = [
     # the hub absorptions stay in the stages without a replay, byte-identical.
     ("tree_replay_and_hubs", {"VSG_SPINE_MIN": "32", "VSG_CUT_RATIO": "1"},
      ("bench", 192, 144, 30, 10), ["hub_stages", "hub_absorbed", "spine_launches", "hub_cuts"]),
-    # (no case for the tree replay's side-cluster cuts, spine_side_cuts: with VSG_SPINE_MIN=32 / 48 and
-    # VSG_CUT_RATIO=1 no stage of buckets 0 / 1 failed with that assumption alone on any input tried --
-    # DESIGN 4.19)
+    # (the tree replay's side-cluster cuts, spine_side_cuts: none of these inputs reaches them; a noisy
+    # gradient does -- test_gpu_spine_paths.py, side_cluster_cuts_and_cool_down)
 ]
 
 

@@ -34,6 +34,73 @@ def test_chain_self_check_is_silent(vsg, monkeypatch, capfd):
     assert "self check" not in err, err
 
 
+def variant_proofs(env):
+    """[(description, predicate over the summed counters)]: what shows that the variant `env` of
+    test_stage_decomposition_variants ran its mechanism -- vsg_spine_paths, the merge paths,
+    diagnostics.rollbacks / slab_growths and the kernel launch counts, as test_gpu_spine_paths.add_paths
+    sums them."""
+    def positive(k):
+        return ("%s > 0" % k, lambda t: t[k] > 0)
+
+    def none(k):
+        return ("%s == 0" % k, lambda t: t[k] == 0)
+
+    out = []
+    spine_min = int(env.get("VSG_SPINE_MIN", "-1"))
+    if env.get("VSG_RLE") == "0":
+        out += [none("rle_stages"), positive("stages")]
+    if "VSG_WINDOWS" in env:
+        out += [none("windows_run") if env["VSG_WINDOWS"] == "1" else positive("windows_run"), positive("stages")]
+    if "VSG_FORCE_ROLLBACK" in env:
+        out += [positive("rollbacks")]
+    if env.get("VSG_GROUP_BUCKETS") == "0":
+        out += [none("group_stages"), positive("stages")]
+    if spine_min == 0:
+        out += [none("replays"), none("spine_kernel_launches"), positive("wave_kernel_launches")]
+    if spine_min > 0:
+        out += [positive("replays"), positive("components"), positive("spine_kernel_launches")]
+    if "VSG_SPINE_MAX_EDGES" in env:
+        out += [("a replay gave up for lack of pool", lambda t: sum(t["pool_fallbacks"]) > 0),
+                positive("top_level_fallbacks"), positive("nested_fallbacks"),
+                ("... and its caller took over",
+                 lambda t: t["top_level_fallbacks"] + t["nested_fallbacks"] == sum(t["pool_fallbacks"]))]
+    if "VSG_SPINE_FAST_MIN" in env or "VSG_SPINE_FAST" in env:
+        passes = int(env.get("VSG_SPINE_FAST", "2"))
+        if "VSG_SPINE_FAST_MIN" in env and passes > 0:
+            out += [positive("streamed_passes"),
+                    ("%d streamed passes per replay" % passes, lambda t: t["streamed_passes"] == passes * (
+                        t["replays"] - sum(t["pool_fallbacks"][1:]) - t["streamed_refused"]))]
+        else:
+            out += [none("streamed_passes")]
+    if "VSG_ZERO_POOL" in env:
+        out += [positive("zero_pool_flips")]
+    if "VSG_RANK_SPLIT_MIN" in env:
+        out += [positive("ranked_by_sampling"),
+                ("plain ranking only where sampling found no room", lambda t: t["ranked_plain"] == t["rank_sampling_refused"])]
+    if env.get("VSG_BOR_AHEAD") == "0":
+        out += [positive("forest_rounds"), none("forest_rounds_ahead"), none("forest_compactions_ahead")]
+    if "VSG_BOR_COMPACT_MIN" in env:
+        out += [positive("forest_compactions_sync" if env.get("VSG_BOR_AHEAD") == "0" else "forest_compactions_ahead")]
+        if env.get("VSG_BOR_AHEAD") != "0":
+            out += [none("forest_compactions_sync"), positive("forest_rounds_ahead")]
+    if "VSG_ACTIVE_CAP" in env:
+        out += [positive("slab_growths")]
+    if env.get("VSG_HUBS") == "0":
+        out += [none("hub_stages"), positive("stages")]   # (stages are still cut where an assumption of the filter fails)
+    if "VSG_HUB_SPLITS" in env:
+        if env["VSG_HUB_SPLITS"] == "0":
+            out += [none("hub_cuts"), positive("stages")]
+        else:   # (at most that many cuts per top-level stage)
+            out += [("at most %s cuts per stage" % env["VSG_HUB_SPLITS"],
+                     lambda t: 0 < t["hub_cuts"] <= int(env["VSG_HUB_SPLITS"]) * t["stages"])]
+    if "VSG_SORT_HAND" in env:
+        hand = env["VSG_SORT_HAND"].startswith("0:")
+        out += [positive("sorts_hand" if hand else "sorts_library"), none("sorts_library" if hand else "sorts_hand")]
+    if "VSG_WIDE_MIN" in env:
+        out += [positive("wide_launches")]
+    return out
+
+
 @pytest.mark.parametrize("env", [{"VSG_RLE": "0"}, {"VSG_WINDOWS": "1"},
                                  {"VSG_WINDOWS": "5", "VSG_WINDOW_MIN": "1"},
                                  {"VSG_WINDOWS": "3", "VSG_WINDOW_MIN": "1", "VSG_RLE": "0"},
@@ -91,8 +158,21 @@ def test_stage_decomposition_variants(vsg, monkeypatch, env):
     sequential replay on the host, with a scratch pool that is too small, with forced rollbacks)."""
     for k, v in env.items():
         monkeypatch.setenv(k, v)
-    for (W, H, N, kind, chunk) in CASES + [(256, 144, 44, "bench", 20)]:
-        run_streams(vsg, W, H, N, kind, True, chunk)
+    from test_gpu_spine_paths import add_paths
+    total = {}
+    streams = CASES + [(256, 144, 44, "bench", 20)]
+    if "VSG_SPINE_MAX_EDGES" in env:
+        # (the four streams make one replay give up for lack of pool, a nested one; this one eight, of both kinds)
+        streams = streams + [(320, 240, 24, "smooth", 8)]
+    for (W, H, N, kind, chunk) in streams:
+        run_streams(vsg, W, H, N, kind, True, chunk, on_chunk=lambda stream: add_paths(total, stream))
+    # ... and the variant ran the mechanism it is named for: the library's host counters, summed over
+    # the four streams
+    print("%s: %s" % (env, total))
+    proofs = variant_proofs(env)
+    assert proofs, "no counter proves that %s ran" % (env,)
+    for what, holds in proofs:
+        assert holds(total), "%s: %s does not hold: %s" % (env, what, total)
     import sys
     sys.path.insert(0, os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "tools"))
     import stress_parity as sp

@@ -89,6 +89,27 @@ class VsgMergePaths(C.Structure):
         return {k: (list(getattr(self, k)) if k == "hub_reasons" else getattr(self, k)) for k, _ in self._fields_}
 
 
+class VsgSpinePaths(C.Structure):
+    """vsg_spine_paths (include/vsg.h), field for field: tests/test_capi_spine_paths.py compares the two."""
+    _fields_ = [
+        ("replays", C.c_int64), ("components", C.c_int64), ("nested_replays", C.c_int64),
+        ("deepest_level", C.c_int64),
+        ("forest_rounds", C.c_int64), ("forest_rounds_ahead", C.c_int64), ("forest_compactions_ahead", C.c_int64),
+        ("forest_compactions_sync", C.c_int64), ("forest_lists_refused", C.c_int64),
+        ("ranked_by_sampling", C.c_int64), ("ranked_plain", C.c_int64), ("rank_sampling_refused", C.c_int64),
+        ("jump_loops_ended_early", C.c_int64), ("streamed_passes", C.c_int64), ("streamed_refused", C.c_int64),
+        ("pool_fallbacks", C.c_int64 * 4), ("top_level_fallbacks", C.c_int64), ("nested_fallbacks", C.c_int64),
+        ("assumption_reruns", C.c_int64), ("limit_bucket_moves", C.c_int64),
+        ("low_bucket_failures", C.c_int64 * 2), ("low_bucket_skips", C.c_int64 * 2),
+        ("zero_pool_flips", C.c_int64),
+        ("windows_run", C.c_int64), ("rle_stages", C.c_int64), ("wide_launches", C.c_int64),
+        ("group_stages", C.c_int64), ("sorts_hand", C.c_int64), ("sorts_library", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: (list(getattr(self, k)) if issubclass(t, C.Array) else getattr(self, k)) for k, t in self._fields_}
+
+
 class VsgMemoryStats(C.Structure):
     _fields_ = [
         ("bytes_in_use", C.c_int64), ("bytes_in_use_peak", C.c_int64), ("bytes_cached", C.c_int64),
@@ -120,7 +141,8 @@ EXPORTED_SYMBOLS = [
     "vsg_vectorize_id_image",
     "vsg_stream_create", "vsg_stream_destroy", "vsg_stream_process_frame", "vsg_stream_chunk_size",
     "vsg_stream_result_bytes", "vsg_stream_result_id_image", "vsg_stream_last_merge_stats",
-    "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_merge_paths", "vsg_stream_last_smoothed", "vsg_stream_export_halo",
+    "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_merge_paths", "vsg_stream_last_spine_paths",
+    "vsg_stream_last_smoothed", "vsg_stream_export_halo",
     "vsg_stream_import_halo", "vsg_stream_expect_halo", "vsg_stream_restart",
     "vsg_chain_create", "vsg_chain_destroy", "vsg_chain_info", "vsg_chain_send_halo",
     "vsg_chain_recv_halo", "vsg_chain_exchange_halo",
@@ -134,7 +156,8 @@ EXPORTED_SYMBOLS = [
     "vsg_graph_get_intervals", "vsg_graph_smoothed",
     "vsg_graph_spatial_buckets", "vsg_graph_temporal_buckets", "vsg_graph_node_roots",
     "vsg_graph_merge_stats", "vsg_graph_timings", "vsg_graph_diagnostics", "vsg_graph_merge_paths",
-    "vsg_debug_sort_pairs", "vsg_debug_sort_pairs_timed",
+    "vsg_graph_spine_paths",
+    "vsg_debug_sort_pairs", "vsg_debug_sort_pairs_timed", "vsg_debug_exclusive_sum", "vsg_debug_runs_of_sorted_keys",
 ]
 
 
@@ -183,6 +206,7 @@ def lib():
     L.vsg_stream_last_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_stream_last_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
     L.vsg_stream_last_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
+    L.vsg_stream_last_spine_paths.argtypes = [vp, C.POINTER(VsgSpinePaths)]
     L.vsg_stream_last_smoothed.argtypes = [vp, vp]
     L.vsg_stream_export_halo.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp]
     L.vsg_stream_import_halo.argtypes = [vp, vp, vp, C.c_int, vp]
@@ -230,6 +254,9 @@ def lib():
     L.vsg_graph_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_graph_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
     L.vsg_graph_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
+    L.vsg_graph_spine_paths.argtypes = [vp, C.POINTER(VsgSpinePaths)]
+    L.vsg_debug_exclusive_sum.argtypes = [vp, C.c_int, vp, C.POINTER(C.c_int64)]
+    L.vsg_debug_runs_of_sorted_keys.argtypes = [vp, C.c_int, vp, vp, C.POINTER(C.c_int32)]
     _lib = L
     return L
 

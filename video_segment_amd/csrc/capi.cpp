@@ -14,6 +14,7 @@
 
 #include "../../include/vsg.h"
 #include "region_segmentation.h"
+#include "scan_device.h"
 #include "stream.h"
 
 namespace {
@@ -130,6 +131,41 @@ static void FillMergePaths(const vsg::MergePaths& mp, vsg_merge_paths* o) {
   o->hub_off_reruns = mp.hub_off_reruns;
   o->group_halvings = mp.group_halvings;
   o->conservative_replays = mp.conservative_replays;
+}
+
+static void FillSpinePaths(const vsg::SpinePaths& sp, vsg_spine_paths* o) {
+  std::memset(o, 0, sizeof(*o));
+  o->replays = sp.replays;
+  o->components = sp.components;
+  o->nested_replays = sp.nested_replays;
+  o->deepest_level = sp.deepest_level;
+  o->forest_rounds = sp.forest_rounds;
+  o->forest_rounds_ahead = sp.forest_rounds_ahead;
+  o->forest_compactions_ahead = sp.forest_compactions_ahead;
+  o->forest_compactions_sync = sp.forest_compactions_sync;
+  o->forest_lists_refused = sp.forest_lists_refused;
+  o->ranked_by_sampling = sp.ranked_by_sampling;
+  o->ranked_plain = sp.ranked_plain;
+  o->rank_sampling_refused = sp.rank_sampling_refused;
+  o->jump_loops_ended_early = sp.jump_loops_ended_early;
+  o->streamed_passes = sp.streamed_passes;
+  o->streamed_refused = sp.streamed_refused;
+  o->top_level_fallbacks = sp.top_level_fallbacks;
+  o->nested_fallbacks = sp.nested_fallbacks;
+  o->assumption_reruns = sp.assumption_reruns;
+  o->limit_bucket_moves = sp.limit_bucket_moves;
+  o->zero_pool_flips = sp.zero_pool_flips;
+  o->windows_run = sp.windows_run;
+  o->rle_stages = sp.rle_stages;
+  o->wide_launches = sp.wide_launches;
+  o->group_stages = sp.group_stages;
+  o->sorts_hand = sp.sorts_hand;
+  o->sorts_library = sp.sorts_library;
+  for (int q = 0; q < 4; ++q) o->pool_fallbacks[q] = sp.pool_fallbacks[q];
+  for (int q = 0; q < 2; ++q) {
+    o->low_bucket_failures[q] = sp.low_bucket_failures[q];
+    o->low_bucket_skips[q] = sp.low_bucket_skips[q];
+  }
 }
 
 static void FillDiagnostics(const vsg::GraphTimings& gt, vsg_diagnostics* d) {
@@ -351,6 +387,13 @@ int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out) {
   return Guard([&] {
     VSG_REQUIRE(s && out, VSG_ERR_INVALID, "null argument");
     FillMergePaths(s->impl->last_graph_timings().paths, out);
+  });
+}
+
+int vsg_stream_last_spine_paths(const vsg_stream* s, vsg_spine_paths* out) {
+  return Guard([&] {
+    VSG_REQUIRE(s && out, VSG_ERR_INVALID, "null argument");
+    FillSpinePaths(s->impl->last_graph_timings().spine_paths, out);
   });
 }
 
@@ -715,6 +758,55 @@ int vsg_debug_sort_pairs(const uint32_t* keys, const uint32_t* values, int n, in
   return vsg_debug_sort_pairs_timed(keys, values, n, end_bit, keys_out, values_out, device, 0, 1, nullptr);
 }
 
+namespace {
+// a stream of the call's own, destroyed with it
+struct DebugStream {
+  hipStream_t s = nullptr;
+  DebugStream() { VSG_HIP(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
+  ~DebugStream() { (void)hipStreamDestroy(s); }
+};
+}  // namespace
+
+int vsg_debug_exclusive_sum(const int32_t* in, int n, int32_t* out, int64_t* total) {
+  return Guard([&] {
+    VSG_REQUIRE(in && out && total && n >= 0, VSG_ERR_INVALID, "bad argument");
+    RequireDevice(-1);
+    if (n == 0) return;
+    vsg::DevBuf<int32_t> d_in((size_t)n), d_out(in == out ? (size_t)1 : (size_t)n), sums(vsg::kScanMaxTiles), d_total(1);
+    int32_t* o = in == out ? d_in.get() : d_out.get();   // (in place on the device as well)
+    DebugStream st;
+    VSG_HIP(hipMemcpyAsync(d_in.get(), in, (size_t)n * 4, hipMemcpyHostToDevice, st.s));
+    vsg::DebugExclusiveSum(vsg::ScanScratch{sums.get(), nullptr}, d_in.get(), o, n, d_total.get(), st.s);
+    int32_t t = 0;
+    VSG_HIP(hipMemcpyAsync(out, o, (size_t)n * 4, hipMemcpyDeviceToHost, st.s));
+    VSG_HIP(hipMemcpyAsync(&t, d_total.get(), 4, hipMemcpyDeviceToHost, st.s));
+    VSG_HIP(hipStreamSynchronize(st.s));
+    *total = t;
+  });
+}
+
+int vsg_debug_runs_of_sorted_keys(const uint32_t* keys, int n, int32_t* seg_off, int32_t* seg_cnt,
+                                  int32_t* num_runs) {
+  return Guard([&] {
+    VSG_REQUIRE(keys && seg_off && seg_cnt && num_runs && n >= 0, VSG_ERR_INVALID, "bad argument");
+    RequireDevice(-1);
+    if (n == 0) return;
+    vsg::DevBuf<uint32_t> d_keys((size_t)n);
+    vsg::DevBuf<int32_t> d_off((size_t)n), d_cnt((size_t)n), sums(vsg::kScanMaxTiles), d_runs(1);
+    DebugStream st;
+    VSG_HIP(hipMemcpyAsync(d_keys.get(), keys, (size_t)n * 4, hipMemcpyHostToDevice, st.s));
+    // (the caller's arrays go in as well: what the scan leaves alone comes back as it was)
+    VSG_HIP(hipMemcpyAsync(d_off.get(), seg_off, (size_t)n * 4, hipMemcpyHostToDevice, st.s));
+    VSG_HIP(hipMemcpyAsync(d_cnt.get(), seg_cnt, (size_t)n * 4, hipMemcpyHostToDevice, st.s));
+    vsg::RunsOfSortedKeys(vsg::ScanScratch{sums.get(), nullptr}, d_keys.get(), n, d_off.get(), d_cnt.get(), d_runs.get(),
+                          st.s);
+    VSG_HIP(hipMemcpyAsync(seg_off, d_off.get(), (size_t)n * 4, hipMemcpyDeviceToHost, st.s));
+    VSG_HIP(hipMemcpyAsync(seg_cnt, d_cnt.get(), (size_t)n * 4, hipMemcpyDeviceToHost, st.s));
+    VSG_HIP(hipMemcpyAsync(num_runs, d_runs.get(), 4, hipMemcpyDeviceToHost, st.s));
+    VSG_HIP(hipStreamSynchronize(st.s));
+  });
+}
+
 // ---- graph -------------------------------------------------------------------------------
 int vsg_graph_create(int width, int height, int max_frames, int l1, int device, vsg_graph** out) {
   return Guard([&] {
@@ -1066,6 +1158,13 @@ int vsg_graph_merge_paths(const vsg_graph* g, vsg_merge_paths* out) {
   return Guard([&] {
     VSG_REQUIRE(g && out, VSG_ERR_INVALID, "null argument");
     FillMergePaths(g->g->timings().paths, out);
+  });
+}
+
+int vsg_graph_spine_paths(const vsg_graph* g, vsg_spine_paths* out) {
+  return Guard([&] {
+    VSG_REQUIRE(g && out, VSG_ERR_INVALID, "null argument");
+    FillSpinePaths(g->g->timings().spine_paths, out);
   });
 }
 

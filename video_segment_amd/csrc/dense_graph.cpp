@@ -546,6 +546,12 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
   // (re-tuned in round 4, once the tree machinery had got cheaper: 4096 -> 2048, nested levels from
   // the same size on)
   S.spine_min = getenv("VSG_SPINE_MIN") ? atoi(getenv("VSG_SPINE_MIN")) : 2048;
+  // The lane worker (k_merge_small) replays every component of up to small_seg edges whatever else
+  // takes components of that size: a tree replay from fewer edges on (VSG_SPINE_MIN=8, or a large
+  // VSG_SMALL_SEG) replayed those twice, and nothing matched the reference any more.  From two above the
+  // lane worker's limit: a replay that finds no room hands its components back with wave_min = its
+  // threshold - 1, and wave_min == small_seg is how the workers know a first launch (the lane worker again).
+  if (S.spine_min > 0) S.spine_min = std::max(S.spine_min, S.small_seg + 2);
   {
     // (the handle's capacity, not this chunk's N.  Round 6 measured 0.55 N: 1.7 GB less at 1080p and
     // the same time on the bench input, but a stage that then wants more makes the pool grow by the
@@ -570,6 +576,7 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
     if (spine_low_cooldown_[b] > 0) {
       --spine_low_cooldown_[b];
       spine_low_skip[b] = 1;
+      ++S.sp.low_bucket_skips[b];
     }
   }
   S.spine_low_failed = spine_low_failed;
@@ -812,6 +819,8 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
       StageInfo info;
       info.want_components = debug_stages ? 2 : measure;
       ++diag_stages;
+      if (windows > 1) ++S.sp.windows_run;
+      if (hi > b + 1) ++S.sp.group_stages;
       RunStageDebug(b, w, windows, j0, n, P, inert_mode, S, debug_stages, &info);
       diag_hub_stages += info.hub_stages;
       diag_hub_absorbed += info.hub_absorbed;
@@ -1029,6 +1038,7 @@ void DenseGraphHip::SegmentLists(int min_region_size, bool force_constraints, in
     mp.hub_off_reruns = S.hub_off_reruns;
     mp.group_halvings = S.group_halvings;
     mp.conservative_replays = S.conservative_replays;
+    timings_.spine_paths = S.sp;
     timings_.slab_growths = diag_slab_growths;
     timings_.slab_growth_ms = diag_slab_ms;
     timings_.spine_growths = diag_spine_growths;

@@ -40,6 +40,7 @@ struct GraphTimings {
   int mail_mode = 0;
   double segment_wall_ms = 0, prepare_ms = 0, constrained_merge_ms = 0;
   MergePaths paths;
+  SpinePaths spine_paths = {};   // (vsg_spine_paths: the tree replay's branches in the same call)
 };
 
 class DenseGraphHip {

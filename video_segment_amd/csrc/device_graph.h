@@ -125,6 +125,11 @@ struct ScanScratch {
   hipStream_t owner = nullptr;   // the one stream whose scans may use `sums` (null: not checked)
 };
 
+// (merge_stage.hip) out[i] = in[0] + ... + in[i - 1] through the fused scan of scan_device.h, *total =
+// the sum of all as the scan's finish() receives it (device memory): the test hook behind
+// vsg_debug_exclusive_sum.  RunsOfSortedKeys is declared in scan_device.h.
+void DebugExclusiveSum(const ScanScratch& sc, const int32_t* in, int32_t* out, int n, int32_t* total, hipStream_t s);
+
 // ---- radix_sort.hip: the stable (key, value) sort of the merge path, hand-written ----------------------
 // (sort_scan.hip: the rocPRIM 64-bit sort / unique of the read-out)
 // SortPairsU32 = the hand-written sort inside its window of sizes, the library outside (measured, radix_sort.hip).
@@ -137,6 +142,8 @@ void SortPairsU32Lib(void* temp, size_t temp_bytes, const uint32_t* keys_in, uin
 size_t SortPairsU32TempBytes(int n);
 void SortPairsU32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
                   const uint32_t* vals_in, uint32_t* vals_out, int n, int end_bit, hipStream_t s);
+// Whether SortPairsU32 sorts n pairs with the hand-written sort (n inside its window).
+bool SortPairsU32TakesHand(int n);
 size_t SortKeysU64TempBytes(int n);
 void SortKeysU64(void* temp, size_t temp_bytes, const unsigned long long* in,
                  unsigned long long* out, int n,
@@ -231,6 +238,19 @@ struct FilterSegs {
   int n;
 };
 constexpr size_t kStageRingInts = (size_t)1 << 18;   // (the largest table is 196 608 ints)
+// Which branches of the tree replay and of the stage driver around it ran in this Segment call
+// (vsg_spine_paths, include/vsg.h, field for field): plain host counts, incremented where the host
+// branches anyway -- no launch, copy, wait or synchronisation of their own.
+struct SpinePaths {
+  int64_t replays, components, nested_replays, deepest_level;
+  int64_t forest_rounds, forest_rounds_ahead, forest_compactions_ahead, forest_compactions_sync, forest_lists_refused;
+  int64_t ranked_by_sampling, ranked_plain, rank_sampling_refused;
+  int64_t jump_loops_ended_early, streamed_passes, streamed_refused;
+  int64_t pool_fallbacks[4], top_level_fallbacks, nested_fallbacks;
+  int64_t assumption_reruns, limit_bucket_moves, low_bucket_failures[2], low_bucket_skips[2];
+  int64_t zero_pool_flips;
+  int64_t windows_run, rle_stages, wide_launches, group_stages, sorts_hand, sorts_library;
+};
 struct MergeScratch {
   // e_ra / e_rb / e_gpos, the masks and the block counts are sized for the largest bucket; everything
   // else holds active edges only: active_cap of them (grow_active enlarges those arrays -- all
@@ -332,6 +352,7 @@ struct MergeScratch {
   long long conservative_replays;        // failed stages replayed with inert_mode 0
   long long hub_cut_ratio;               // a stage is cut only above this many edges per violation (VSG_CUT_RATIO)
   int hub_check;                         // VSG_HUB_CHECK: host check of the list head and of every cut position
+  SpinePaths sp;                         // (vsg_spine_paths: the tree replay's branches, counted the same way)
   int wave_debug;        // use the instrumented build of the wave worker (counters, self checks)
   int wave_dbg;          // debug hook (bit mask): 1 no chain, 4 no hot region, 8 one generic lane per round,
                          // 16 chain self check, 32 no jumping over pending lanes, 64 one chain lane per round

@@ -1410,7 +1410,15 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
     tph[i] = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch()).count();
   };
   Mark(0);
-  if (pool_used >= S.spine_pool_ints) return false;
+  SpinePaths& sp = S.sp;   // (host counts of the branches taken: vsg_spine_paths)
+  if (pool_used >= S.spine_pool_ints) {
+    ++sp.pool_fallbacks[0];
+    return false;
+  }
+  ++sp.replays;
+  sp.components += K;
+  if (depth >= 1) ++sp.nested_replays;
+  sp.deepest_level = std::max<int64_t>(sp.deepest_level, depth);
   Pool pool{S.spine_pool + pool_used, S.spine_pool_ints - pool_used};
   int32_t* d_base = pool.take(K + 1);
   int32_t* d_off = pool.take(K);
@@ -1425,7 +1433,10 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
   int32_t* scan = pool.take(mE);
   int32_t* side_key = pool.take(mE);
   int32_t* spine_flag = pool.take(mE);
-  if (!pool.ok) return false;
+  if (!pool.ok) {
+    ++sp.pool_fallbacks[1];
+    return false;
+  }
   int32_t* cc = S.cc;
   uint32_t* best = reinterpret_cast<uint32_t*>(S.nmap[0]);
   int32_t* firstq = S.nmap[1];
@@ -1485,6 +1496,7 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
     for (int round = 0;; ++round) {
       dbg_rounds = round;
       VSG_REQUIRE(round < 32, -4, "spine: the spanning forest did not converge");
+      ++sp.forest_rounds;
       int32_t* d_ctr = TakeZeroed(S, 16 * kAliveSlots + 4);   // edges alive in this round (spread), then the round's total
       int32_t* d_next_len = len_words + (len_cur ^ 1);
       // ecu / ecv (the components of the round) live in the side_key / spine_flag arrays, which are
@@ -1501,6 +1513,7 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
       gate = gate_words + (round & 1);
       waiting[n_waiting++] = m_alive;
       const int depth = n_list <= ahead_max ? 1 : 0;   // rounds that may stay unanswered
+      if (depth == 1) ++sp.forest_rounds_ahead;
       const double tr0 = dbg_big ? NowMs() : 0;
       int alive = -1;
       bool complete = false;
@@ -1531,12 +1544,14 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
         lists[0] = pool.take(cap);
         lists[1] = pool.take(cap);
         if (!pool.ok) {   // without room the rounds simply keep the longer list
+          ++sp.forest_lists_refused;
           pool.ok = true;
           pool.release(m);
           lists[0] = lists[1] = nullptr;
         }
       }
       if (!lists[0]) continue;
+      ++(depth == 1 ? sp.forest_compactions_ahead : sp.forest_compactions_sync);
       hipLaunchKernelGGL(k_bor_compact, dim3(Blocks(((size_t)n_list + kBorCompactPer - 1) / kBorCompactPer)),
                          dim3(256), 0, s, n_list, list, list_len, estate, lists[which], d_next_len);
       list = lists[which];
@@ -1574,9 +1589,13 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
   int32_t* pos_arc = pool.take(na);
   int32_t* succ[2] = {pool.take(na), pool.take(na)};
   int32_t* dist[2] = {pool.take(na), pool.take(na)};
-  if (!pool.ok) return false;
+  if (!pool.ok) {
+    ++sp.pool_fallbacks[2];
+    return false;
+  }
   hipLaunchKernelGGL(k_compact_tree, dim3(Blocks(mE)), dim3(256), 0, s, mE, flag, scan, te_e);
   hipLaunchKernelGGL(k_arc_keys, dim3(Blocks(na)), dim3(256), 0, s, mt, te_e, eu, ev, ak_in, av_in);
+  ++(SortPairsU32TakesHand(na) ? sp.sorts_hand : sp.sorts_library);
   SortPairsU32(S.cub_temp, S.cub_temp_bytes, ak_in, ak, av_in, av, na, S.node_key_bits, s);
   hipLaunchKernelGGL(k_arc_first, dim3(Blocks(na)), dim3(256), 0, s, na, ak, av, firstq, pos_arc);
   hipLaunchKernelGGL(k_arc_succ, dim3(Blocks(na)), dim3(256), 0, s, na, ak, av, firstq, pos_arc, te_e, d_base, K,
@@ -1603,12 +1622,15 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
       hipLaunchKernelGGL(k_rank_finish, dim3(Blocks(na)), dim3(256), 0, s, na, owner, local, r_len[rc], dist[1]);
       cur = 1;
       ranked = true;
+      ++sp.ranked_by_sampling;
     } else {
+      ++sp.rank_sampling_refused;
       pool.ok = true;
     }
     pool.release(rmark);
   }
   if (!ranked) {
+    ++sp.ranked_plain;
     for (int span = 1; span < na; span *= 2) {
       hipLaunchKernelGGL(k_rank_step, dim3(Blocks(na)), dim3(256), 0, s, na, succ[cur], dist[cur], succ[cur ^ 1],
                          dist[cur ^ 1]);
@@ -1641,7 +1663,10 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
         if (have_asked) {
           int more = 0;
           MailWait(asked, 1, &more, s);
-          if (!more) break;
+          if (!more) {
+            ++sp.jump_loops_ended_early;
+            break;
+          }
         }
         asked = m;
         have_asked = true;
@@ -1672,7 +1697,10 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
   int32_t* o_ra = pool.take(ns);
   int32_t* o_rb = pool.take(ns);
   uint32_t* o_gpos = reinterpret_cast<uint32_t*>(pool.take(ns));
-  if (!pool.ok) return false;
+  if (!pool.ok) {
+    ++sp.pool_fallbacks[3];
+    return false;
+  }
   hipLaunchKernelGGL(k_compact_side, dim3(Blocks(mE)), dim3(256), 0, s, mE, flag, scan, side_key, sk_in, si_in);
   // spine edges (the scan buffer is reused once the side positions are consumed)
   FusedScan(S.scan, StateFlagValue{spine_flag, 1}, SpineEmit{eu, ev, childidx, te_e, scan, sp_child, sp_is_a, d_base, d_off, K},
@@ -1689,6 +1717,7 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
   if (n_side > 0) {
     int side_bits = 1;   // the keys are tree-edge indices
     while (side_bits < 32 && (1ll << side_bits) < (long long)mt) ++side_bits;
+    ++(SortPairsU32TakesHand(n_side) ? sp.sorts_hand : sp.sorts_library);
     SortPairsU32(S.cub_temp, S.cub_temp_bytes, sk_in, sk, si_in, si, n_side, side_bits, s);
     int32_t* d_nseg = scalars + 3;
     RunsOfSortedKeys(S.scan, sk, n_side, seg_off, seg_cnt, d_nseg, s);
@@ -1732,6 +1761,7 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
         run_workers(w2, n_side, s);
       }
       if (!RunSpineComponents(nested, w2, S, s, run_workers, pool_used + pool.used, depth + 1)) {
+        ++sp.nested_fallbacks;
         WorkerArgs w3 = w2;   // no room: the wave worker replays them
         w3.wave_min = w2.wave_max - 1;
         w3.wave_max = 0x7fffffff;
@@ -1767,6 +1797,7 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
     if (pool.ok) {
       start_pos = F.start_pos;
       for (int pass = 0; pass < S.spine_fast; ++pass) {
+        ++sp.streamed_passes;
         if (pass > 0) LaunchSpine(64);
         hipLaunchKernelGGL(k_spine_fast_init, dim3((K + 63) / 64), dim3(64), 0, s, K, comp_spine, F, pass == 0 ? 1 : 0);
         hipLaunchKernelGGL(k_spine_prep, dim3(Blocks((size_t)mt + 1)), dim3(256), 0, s, mt, K, comp_spine,
@@ -1802,6 +1833,8 @@ bool RunSpineComponents(const SpineInput& in, const WorkerArgs& wa, MergeScratch
                        "cluster)\n", pass, fast, total, longest, stopped, K, failed);
         }
       }
+    } else {
+      ++sp.streamed_refused;
     }
   }
   LaunchSpine(0x7fffffff);

@@ -197,6 +197,7 @@ int32_t* TakeZeroed(MergeScratch& S, size_t n) {
     DrainStreams(S);
     z.second_half = !z.second_half;
     z.used = 0;
+    ++S.sp.zero_pool_flips;
     VSG_HIP(hipMemsetAsync(z.base + kZeroArenaInts + (z.second_half ? half : 0), 0, half * sizeof(int32_t),
                            S.main_stream));
   }
@@ -1684,6 +1685,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
   int n_work = n_active;
   int32_t* lead = S.e_active;       // free after the compaction
   if (rle) {
+    ++S.sp.rle_stages;
     const MailSlot m_lead = NextMail(*S.mail);
     FusedScan(S.scan, LeaderValue{S.a_ra, S.a_rb},
               LeaderEmit{S.a_ra, S.a_rb, S.a_gpos, lead, S.lead_pos, S.l_ra, S.l_rb, S.l_gpos},
@@ -1696,6 +1698,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
 
   hipLaunchKernelGGL(k_component_ids, dim3(Blocks(n_work)), dim3(256), 0, s, n_work, w_ra, S.cc,
                      S.a_comp, S.a_idx);
+  ++(SortPairsU32TakesHand(n_work) ? S.sp.sorts_hand : S.sp.sorts_library);
   SortPairsU32(S.cub_temp, S.cub_temp_bytes, S.a_comp, S.s_comp, S.a_idx, S.s_idx, n_work, S.node_key_bits, s);
   // the components = the runs of equal keys: first position and length of every run
   RunsOfSortedKeys(S.scan, S.s_comp, n_work, S.seg_off, S.seg_cnt, S.num_segs, s);
@@ -1805,6 +1808,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     const bool wide = w.work_list != nullptr && w.wide_min > 0 && w.wide_min < w.wave_max &&
                       small_threads >= w.wide_min && w.wave_min == w.small_seg;
     if (wide) {
+      ++S.sp.wide_launches;
       WorkerArgs narrow = w;
       narrow.wave_max = w.wide_min;
       LaunchMergeWave(grid, narrow, S.wave_debug != 0, S.wave_dbg, s);
@@ -1832,6 +1836,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
       general_workers(w, n, WaveGrid(n), st);
     }, 0, 0);
     if (!done) {   // no room in the scratch pool: the wave worker replays them
+      ++S.sp.top_level_fallbacks;
       WorkerArgs w3 = wa;
       w3.wave_min = spine_thr - 1;
       w3.wave_max = 0x7fffffff;
@@ -1855,6 +1860,7 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
     int n_abs = 0;
     MailWait(m_hub, 1, &n_abs, s);
     if (n_abs > 0) {
+      ++(SortPairsU32TakesHand(n_abs) ? S.sp.sorts_hand : S.sp.sorts_library);
       SortPairsU32(S.cub_temp, S.cub_temp_bytes, key_list, key_sorted, seq_list, seq_sorted, n_abs, S.node_key_bits, s);
       RunsOfSortedKeys(S.scan, key_sorted, n_abs, run_off, run_cnt, d_hub_runs, s);
       hipLaunchKernelGGL(k_hub_apply, dim3((unsigned)((n_abs + 63) / 64)), dim3(64), 0, s, d_hub_runs, run_off,
@@ -1902,8 +1908,15 @@ void RunBucketStage(int bucket, int j0, int n_b, const ListDesc* lists, const in
         // Only the tree replay's assumption failed (an edge of a large component was kept): the
         // same stage again with the ordinary workers.  From the third bucket on that is the rule
         // rather than the exception, so the later buckets (of this and the next chunks) skip it.
-        if (bucket >= 2 && bucket < *S.spine_limit_bucket) *S.spine_limit_bucket = bucket;
-        if (bucket < 2) S.spine_low_failed[bucket] = 1;   // the first two buckets: see SegmentLists
+        ++S.sp.assumption_reruns;
+        if (bucket >= 2 && bucket < *S.spine_limit_bucket) {
+          *S.spine_limit_bucket = bucket;
+          ++S.sp.limit_bucket_moves;
+        }
+        if (bucket < 2) {
+          S.spine_low_failed[bucket] = 1;   // the first two buckets: see SegmentLists
+          ++S.sp.low_bucket_failures[bucket];
+        }
         const int off = S.spine_off;
         S.spine_off = 1;
         RunBucketStage(bucket, j0, n_b, lists, bucket_base, list_slot_base, kept_all, nodes, P, inert_mode, S,
@@ -1992,6 +2005,15 @@ void RunsOfSortedKeys(const ScanScratch& sc, const uint32_t* keys, int n, int32_
   // (the number of runs is only known on the device: one thread per position, most return at once)
   hipLaunchKernelGGL(k_run_counts, dim3(Blocks(n)), dim3(256), 0, s, n, num_runs, seg_off, seg_cnt);
   VSG_HIP(hipGetLastError());
+}
+
+// Test hook (vsg_debug_exclusive_sum): the plain exclusive sum with a finish() that stores the total.
+struct ScanTotalStore {
+  int32_t* total;
+  __device__ void operator()(int t) const { *total = t; }
+};
+void DebugExclusiveSum(const ScanScratch& sc, const int32_t* in, int32_t* out, int n, int32_t* total, hipStream_t s) {
+  FusedScan(sc, ScanLoadI32{in}, ScanStoreI32{out}, ScanTotalStore{total}, n, s);
 }
 
 // Largest component (in replayed edges) below `below`.

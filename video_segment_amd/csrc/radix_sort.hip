@@ -304,11 +304,15 @@ size_t SortPairsU32TempBytes(int n) {
   return std::max(SortPairsU32HandTempBytes(n), SortPairsU32LibTempBytes(n));
 }
 
-void SortPairsU32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
-                  const uint32_t* vals_in, uint32_t* vals_out, int n, int end_bit, hipStream_t s) {
+bool SortPairsU32TakesHand(int n) {
   int lo, hi;
   SortHandWindow(lo, hi);
-  if (n >= lo && n <= hi) {
+  return n >= lo && n <= hi;
+}
+
+void SortPairsU32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
+                  const uint32_t* vals_in, uint32_t* vals_out, int n, int end_bit, hipStream_t s) {
+  if (SortPairsU32TakesHand(n)) {
     SortPairsU32Hand(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, s);
   } else {
     SortPairsU32Lib(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, end_bit, s);

@@ -14,7 +14,7 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import VsgDiagnostics, VsgMergePaths, VsgOptions, VsgTimings, check, lib
+from ._lib import VsgDiagnostics, VsgMergePaths, VsgOptions, VsgSpinePaths, VsgTimings, check, lib
 
 
 def default_options(**kw):
@@ -147,6 +147,13 @@ class DenseSegmentation:
         ran), as a dict."""
         m = VsgMergePaths()
         check(lib().vsg_stream_last_merge_paths(self.h, C.byref(m)))
+        return m.as_dict()
+
+    def last_spine_paths(self):
+        """vsg_stream_last_spine_paths of the last segmented chunk (which branches of the tree replay
+        ran), as a dict."""
+        m = VsgSpinePaths()
+        check(lib().vsg_stream_last_spine_paths(self.h, C.byref(m)))
         return m.as_dict()
 
     def last_smoothed(self):
@@ -370,4 +377,10 @@ class DenseSegGraph:
         """vsg_graph_merge_paths of the last segment() call, as a dict."""
         m = VsgMergePaths()
         check(lib().vsg_graph_merge_paths(self.h, C.byref(m)))
+        return m.as_dict()
+
+    def last_spine_paths(self):
+        """vsg_graph_spine_paths of the last segment() call, as a dict."""
+        m = VsgSpinePaths()
+        check(lib().vsg_graph_spine_paths(self.h, C.byref(m)))
         return m.as_dict()
