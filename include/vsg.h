@@ -231,6 +231,17 @@ int vsg_stream_result_bytes(vsg_stream* s, int i, const uint8_t** data, size_t* 
  * out is W*H int32 in host memory. */
 int vsg_stream_result_id_image(vsg_stream* s, int i, int32_t* out);
 int vsg_stream_last_merge_stats(const vsg_stream* s, int64_t* forced_regular_small);
+/* Parity hook: the state the ordered merge computes.  With keeping on (off by default; off adds no
+ * launch, copy or allocation), every call that segments a chunk copies the chunk graph's per-node
+ * state to host memory between the merge and the read-out.  n = W*H*slices of that graph (virtual
+ * and constrained slices included); entry i is the state of the representative of node i: root (its
+ * node id), mean (3 f32 per node), size, constraint id (-1: none) and the flags byte, bit 0 "region
+ * finalized", bit 1 "no descriptor" (a virtual region: its mean is indeterminate).  The higher bits are
+ * marks of a merge stage and are clear after a segment call.  The pointers stay valid until the next
+ * call that segments a chunk. */
+int vsg_stream_keep_node_states(vsg_stream* s, int on);
+int vsg_stream_last_node_states(const vsg_stream* s, int64_t* n, const int32_t** root, const float** mean,
+                                const int32_t** size, const int32_t** constraint, const uint8_t** flags);
 int vsg_stream_last_timings(const vsg_stream* s, vsg_timings* t);
 int vsg_stream_last_diagnostics(const vsg_stream* s, vsg_diagnostics* d);
 int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out);
@@ -399,6 +410,11 @@ int vsg_graph_spatial_buckets(vsg_graph* g, int t, uint16_t* out /* 4*W*H, plane
 int vsg_graph_temporal_buckets(vsg_graph* g, int t, uint16_t* out /* 9*W*H */, int32_t* prev_idx);
 /* Union-find representative (node id) of every node after segment(); n = W*H*frames. */
 int vsg_graph_node_roots(vsg_graph* g, int32_t* out);
+/* ... and the state of that representative, as of the last segment / segment_spatially call (see
+ * vsg_stream_last_node_states): root, size, constraint n int32; mean 3n f32; flags n bytes.  May be
+ * called before or after obtain_results; it leaves the results alone. */
+int vsg_graph_node_states(vsg_graph* g, int32_t* root, float* mean, int32_t* size, int32_t* constraint,
+                          uint8_t* flags);
 int vsg_graph_merge_stats(const vsg_graph* g, int64_t* forced_regular_small);
 int vsg_graph_timings(const vsg_graph* g, vsg_timings* t);
 int vsg_graph_diagnostics(const vsg_graph* g, vsg_diagnostics* d);

@@ -1125,6 +1125,21 @@ class DenseGraph {
   void NodeRoots(int32_t* out) {
     for (int i = 0, n = (int)regions_.size(); i < n; ++i) out[i] = GetRegion(i)->my_id;
   }
+  // The state the ordered merge computes, per node: entry i is the state of node i's
+  // representative.  flags: bit 0 region_finalized, bit 1 virtual_no_desc.
+  int num_nodes() const { return (int)regions_.size(); }
+  void NodeStates(int32_t* root, float* mean, int32_t* size, int32_t* constraint, uint8_t* flags) {
+    for (int i = 0, n = (int)regions_.size(); i < n; ++i) {
+      const Region* r = GetRegion(i);
+      root[i] = r->my_id;
+      mean[3 * (size_t)i + 0] = r->descriptor[0];
+      mean[3 * (size_t)i + 1] = r->descriptor[1];
+      mean[3 * (size_t)i + 2] = r->descriptor[2];
+      size[i] = r->sz;
+      constraint[i] = r->constraint_id;
+      flags[i] = (uint8_t)((r->region_finalized ? 1 : 0) | (r->virtual_no_desc ? 2 : 0));
+    }
+  }
 
   // DenseSegmentationGraph::ObtainResults, dense_segmentation_graph.h:468-579.
   // flows: per slice W*H*2 f32 (null entries allowed for slices without flow) or null.
@@ -1276,9 +1291,25 @@ class DenseGraph {
       const float denom = 1.0f / (float)(other->sz + merged->sz);
       const float a = (float)other->sz * denom;
       const float b = (float)merged->sz * denom;
+#if defined(VSO_MUTANT_FUSED_MEAN)
+      // (test mutant, oracle/Makefile: the mean as a fused multiply-add -- what contraction gives)
+      for (int c = 0; c < 3; ++c) {
+        merged->descriptor[c] = std::fmaf(a, other->descriptor[c], b * merged->descriptor[c]);
+      }
+#elif defined(VSO_MUTANT_SUMDIV_MEAN)
+      // (test mutant: sum first, divide once -- a re-associated mean)
+      (void)a;
+      (void)b;
+      for (int c = 0; c < 3; ++c) {
+        merged->descriptor[c] = ((float)other->sz * other->descriptor[c] +
+                                 (float)merged->sz * merged->descriptor[c]) /
+                                (float)(other->sz + merged->sz);
+      }
+#else
       merged->descriptor[0] = a * other->descriptor[0] + b * merged->descriptor[0];
       merged->descriptor[1] = a * other->descriptor[1] + b * merged->descriptor[1];
       merged->descriptor[2] = a * other->descriptor[2] + b * merged->descriptor[2];
+#endif
     } else if (merged->virtual_no_desc && !other->virtual_no_desc) {
       // Only reachable with sz(other) <= sz(merged) == 0, i.e. two size-0 regions; descriptor
       // indeterminate in the reference and never read afterwards.
@@ -1660,6 +1691,22 @@ struct SegOptions {
   bool enforce_spatial_connectedness = true;
 };
 
+// Per-node state of the last segmented chunk, kept on request (vso_stream_keep_node_states).
+struct NodeStateSnapshot {
+  std::vector<int32_t> root, size, constraint;
+  std::vector<float> mean;
+  std::vector<uint8_t> flags;
+  void Capture(DenseGraph* g) {
+    const size_t n = (size_t)g->num_nodes();
+    root.resize(n);
+    size.resize(n);
+    constraint.resize(n);
+    mean.resize(3 * n);
+    flags.resize(n);
+    g->NodeStates(root.data(), mean.data(), size.data(), constraint.data(), flags.data());
+  }
+};
+
 class Segmentation {
  public:
   Segmentation(const SegOptions& o, int W, int H, int chunk_id, int max_frames, bool l1)
@@ -1668,11 +1715,13 @@ class Segmentation {
   DenseGraph* graph() { return graph_.get(); }
 
   // segmentation.cpp:272-303
-  void RunOverSegmentation(const std::vector<const float*>* flows) {
+  // states: where to snapshot the merge's state per node (parity hook), or null.
+  void RunOverSegmentation(const std::vector<const float*>* flows, NodeStateSnapshot* states = nullptr) {
     region_infos_.reset(new RegionInfoList());
     if (options_.two_stage_segmentation) graph_->SegmentGraphSpatially();   // segmentation.cpp:280-283
     graph_->SegmentGraph(options_.min_region_size, true);
     graph_->MergeStats(merge_stats_);
+    if (states) states->Capture(graph_.get());
     RegionInfoPtrMap map;
     graph_->ObtainResults(region_infos_.get(), &map, flows, options_.enforce_n4_connectivity,
                           options_.enforce_spatial_connectedness);
@@ -1853,6 +1902,8 @@ class DenseSegmentation {
 
   const std::vector<std::unique_ptr<SegmentationDesc>>& results() const { return results_; }
   const int64_t* last_merge_stats() const { return last_merge_stats_; }
+  void keep_node_states(bool on) { keep_node_states_ = on; }
+  const NodeStateSnapshot& node_states() const { return node_states_; }
 
   // Multi-GPU hand-off (not in the reference, where the state simply lives on in the object):
   // everything the next chunk needs from this one -- the id images of the two overlap
@@ -1929,7 +1980,8 @@ class DenseSegmentation {
     if (!flow_buffer_.empty()) {
       for (const auto& f : flow_buffer_) flows.push_back(f ? f->data() : nullptr);
     }
-    seg_->RunOverSegmentation(flow_buffer_.empty() ? nullptr : &flows);
+    seg_->RunOverSegmentation(flow_buffer_.empty() ? nullptr : &flows,
+                              keep_node_states_ ? &node_states_ : nullptr);
     std::memcpy(last_merge_stats_, seg_->merge_stats(), sizeof(last_merge_stats_));
 
     const int buffered = (int)feature_buffer_.size();
@@ -2000,6 +2052,8 @@ class DenseSegmentation {
   std::vector<std::unique_ptr<SegmentationDesc>> results_;
   std::unique_ptr<Segmentation> seg_;
   int64_t last_merge_stats_[3] = {0, 0, 0};
+  bool keep_node_states_ = false;
+  NodeStateSnapshot node_states_;   // of the last segmented chunk, while keep_node_states_
   std::vector<int32_t> halo_[2];
   bool pending_import_ = false;
 };
@@ -2203,6 +2257,19 @@ int vso_stream_result_first_region(const vso_stream* s, int i, int* id, float* m
 void vso_stream_last_merge_stats(const vso_stream* s, int64_t* stats3) {
   std::memcpy(stats3, s->ds->last_merge_stats(), 3 * sizeof(int64_t));
 }
+void vso_stream_keep_node_states(vso_stream* s, int on) { s->ds->keep_node_states(on != 0); }
+int vso_stream_last_node_states(const vso_stream* s, int64_t* n, const int32_t** root, const float** mean,
+                                const int32_t** size, const int32_t** constraint, const uint8_t** flags) {
+  const vso::NodeStateSnapshot& st = s->ds->node_states();
+  if (st.root.empty()) return -1;
+  *n = (int64_t)st.root.size();
+  *root = st.root.data();
+  *mean = st.mean.data();
+  *size = st.size.data();
+  *constraint = st.constraint.data();
+  *flags = st.flags.data();
+  return 0;
+}
 int vso_stream_last_smoothed(const vso_stream* s, float* out) {
   const float* p = s->ds->last_smoothed();
   if (!p) return -1;
@@ -2320,6 +2387,10 @@ int64_t vso_graph_num_neighbor_links(const vso_graph* g) {
   return n;
 }
 void vso_graph_node_roots(vso_graph* g, int32_t* out) { g->g->NodeRoots(out); }
+void vso_graph_node_states(vso_graph* g, int32_t* root, float* mean, int32_t* size, int32_t* constraint,
+                           uint8_t* flags) {
+  g->g->NodeStates(root, mean, size, constraint, flags);
+}
 void vso_graph_index_image(const vso_graph* g, int t, int32_t* out) {
   const size_t n = (size_t)g->W * g->H;
   for (size_t k = 0; k < n; ++k) out[k] = -1;

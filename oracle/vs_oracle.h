@@ -106,6 +106,14 @@ int vso_stream_result_hierarchy_regions(const vso_stream* s, int i);
 int vso_stream_result_first_region(const vso_stream* s, int i, int* id, float* moments6);
 /* merge statistics of the last segmented chunk: forced, regular, small. */
 void vso_stream_last_merge_stats(const vso_stream* s, int64_t* stats3);
+/* Parity hook (mirrors vsg_stream_keep_node_states / _last_node_states): with keeping on, every
+ * segmented chunk's per-node state is snapshotted right after SegmentGraph.  Entry i is the state of
+ * node i's representative: mean (3 f32), size, constraint id, flags (bit 0 region_finalized, bit 1
+ * virtual_no_desc -- the mean of such a region is indeterminate in the reference).  The pointers
+ * stay valid until the next segmented chunk.  -1 if nothing has been kept. */
+void vso_stream_keep_node_states(vso_stream* s, int on);
+int vso_stream_last_node_states(const vso_stream* s, int64_t* n, const int32_t** root, const float** mean,
+                                const int32_t** size, const int32_t** constraint, const uint8_t** flags);
 /* Smoothed feature frame of the most recently added frame (W*H*3 f32, BGR interleaved). */
 int vso_stream_last_smoothed(const vso_stream* s, float* out);
 
@@ -152,6 +160,10 @@ int64_t vso_graph_num_neighbor_links(const vso_graph* g);
 /* Per node label after the merge (representative node id, before FlattenUnionFind). Must be
  * called between vso_graph_segment and vso_graph_obtain_results. n = W*H*frames. */
 void vso_graph_node_roots(vso_graph* g, int32_t* out);
+/* The same call window: the state of every node's representative (see vso_stream_last_node_states).
+ * root, size, constraint: n int32; mean: 3n f32; flags: n u8. */
+void vso_graph_node_states(vso_graph* g, int32_t* root, float* mean, int32_t* size, int32_t* constraint,
+                           uint8_t* flags);
 /* Per pixel region *index* (RegionInformation::index) of frame t after obtain_results, from the
  * rasterizations.  -1 where uncovered (virtual slices). */
 void vso_graph_index_image(const vso_graph* g, int t, int32_t* out);

@@ -269,12 +269,24 @@ def oracle_keys(W, H, l1, with_flow):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_merge(W, H, min_size):
-    """(merge_stats, node_roots) of the oracle's two-frame graph over key_inputs with flow."""
+def _oracle_merge(W, H, min_size):
     f0, f1, flow, _ = key_inputs(W, H)
     og = ol.OracleGraph(W, H, 2)
     og.add_frame(f0)
     og.add_frame(f1)
     og.add_temporal(f1, f0, flow)
     og.segment(min_size, False)
-    return og.merge_stats(), og.node_roots()
+    out = (og.merge_stats(), og.node_roots(), og.node_states())
+    for a in (out[0], out[1]) + out[2]:
+        a.setflags(write=False)
+    return out
+
+
+def oracle_merge(W, H, min_size):
+    """(merge_stats, node_roots) of the oracle's two-frame graph over key_inputs with flow."""
+    return _oracle_merge(W, H, min_size)[:2]
+
+
+def oracle_merge_states(W, H, min_size):
+    """The same graph's node states (node_states.py) after the merge."""
+    return _oracle_merge(W, H, min_size)[2]

@@ -56,7 +56,24 @@ def lib():
     if _lib is not None:
         return _lib
     build_oracle()
-    L = C.CDLL(_LIB_PATH)
+    _lib = _bind(C.CDLL(_LIB_PATH))
+    return _lib
+
+
+_mutants = {}
+
+
+def mutant_lib(name):
+    """The oracle with a mutated region mean ('fused' or 'sumdiv', oracle/Makefile), built on demand:
+    pass it as L= to OracleStream / OracleGraph.  Test infrastructure of the state comparison."""
+    if name not in _mutants:
+        target = "libvs_oracle_%s.so" % name
+        subprocess.check_call(["make", "-C", ORACLE_DIR, "-s", target])
+        _mutants[name] = _bind(C.CDLL(os.path.join(ORACLE_DIR, target)))
+    return _mutants[name]
+
+
+def _bind(L):
     vp = C.c_void_p
     L.vso_default_options.argtypes = [C.POINTER(VsoOptions)]
     L.vso_stream_create.restype = vp
@@ -121,7 +138,10 @@ def lib():
     L.vso_graph_get_intervals.restype = C.c_int64
     L.vso_graph_get_intervals.argtypes = [vp, C.c_int, vp]
     L.vso_graph_bucket_census.argtypes = [vp, vp]
-    _lib = L
+    L.vso_stream_keep_node_states.argtypes = [vp, C.c_int]
+    L.vso_stream_last_node_states.restype = C.c_int
+    L.vso_stream_last_node_states.argtypes = [vp, C.POINTER(C.c_int64)] + [C.POINTER(vp)] * 5
+    L.vso_graph_node_states.argtypes = [vp, vp, vp, vp, vp, vp]
     return L
 
 
@@ -145,15 +165,16 @@ def default_options(**kw):
 class OracleStream:
     """DenseSegmentation::ProcessFrame restatement."""
 
-    def __init__(self, width, height, options=None, has_flow=False):
+    def __init__(self, width, height, options=None, has_flow=False, L=None):
+        self.L = L if L is not None else lib()
         self.W, self.H = width, height
         self.has_flow = has_flow
         self.opts = options if options is not None else default_options()
-        self.h = lib().vso_stream_create(C.byref(self.opts), width, height)
+        self.h = self.L.vso_stream_create(C.byref(self.opts), width, height)
 
     def close(self):
         if self.h:
-            lib().vso_stream_destroy(self.h)
+            self.L.vso_stream_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -165,8 +186,8 @@ class OracleStream:
         self._held = []
 
     def restart(self):
-        lib().vso_stream_destroy(self.h)
-        self.h = lib().vso_stream_create(C.byref(self.opts), self.W, self.H)
+        self.L.vso_stream_destroy(self.h)
+        self.h = self.L.vso_stream_create(C.byref(self.opts), self.W, self.H)
         self._held = None
 
     def process_frame(self, bgr, flow=None, flush=False):
@@ -187,58 +208,75 @@ class OracleStream:
         if flow is not None:
             flow = np.ascontiguousarray(flow, dtype=np.float32)
             assert flow.shape == (self.H, self.W, 2)
-        return lib().vso_stream_process_frame(self.h, int(flush), _ptr(bgr), stride, _ptr(flow),
+        return self.L.vso_stream_process_frame(self.h, int(flush), _ptr(bgr), stride, _ptr(flow),
                                               int(self.has_flow))
 
     def num_results(self):
-        return lib().vso_stream_num_results(self.h)
+        return self.L.vso_stream_num_results(self.h)
 
     def result_bytes(self, i):
         p = C.c_void_p()
         n = C.c_size_t()
-        rc = lib().vso_stream_result_bytes(self.h, i, C.byref(p), C.byref(n))
+        rc = self.L.vso_stream_result_bytes(self.h, i, C.byref(p), C.byref(n))
         assert rc == 0
         return C.string_at(p, n.value)
 
     def result_id_image(self, i):
         out = np.empty((self.H, self.W), np.int32)
-        assert lib().vso_stream_result_id_image(self.h, i, _ptr(out)) == 0
+        assert self.L.vso_stream_result_id_image(self.h, i, _ptr(out)) == 0
         return out
 
     def result_num_regions(self, i):
-        return lib().vso_stream_result_num_regions(self.h, i)
+        return self.L.vso_stream_result_num_regions(self.h, i)
 
     def result_hierarchy_regions(self, i):
-        return lib().vso_stream_result_hierarchy_regions(self.h, i)
+        return self.L.vso_stream_result_hierarchy_regions(self.h, i)
 
     def result_first_region(self, i):
         rid = C.c_int()
         m = np.zeros(6, np.float32)
-        assert lib().vso_stream_result_first_region(self.h, i, C.byref(rid), _ptr(m)) == 0
+        assert self.L.vso_stream_result_first_region(self.h, i, C.byref(rid), _ptr(m)) == 0
         return rid.value, m
 
     def last_merge_stats(self):
         s = np.zeros(3, np.int64)
-        lib().vso_stream_last_merge_stats(self.h, _ptr(s))
+        self.L.vso_stream_last_merge_stats(self.h, _ptr(s))
         return s
+
+    def keep_node_states(self, on=True):
+        """Snapshot the merge's per-node state of every segmented chunk (vso_stream_keep_node_states)."""
+        self.L.vso_stream_keep_node_states(self.h, int(on))
+
+    def last_node_states(self):
+        """(root, mean [n,3], size, constraint, flags) of the last segmented chunk, copied."""
+        n = C.c_int64()
+        p = [C.c_void_p() for _ in range(5)]
+        rc = self.L.vso_stream_last_node_states(self.h, C.byref(n), *[C.byref(x) for x in p])
+        assert rc == 0, "no node states kept"
+        n = n.value
+
+        def arr(ptr, ctype, count):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(count,)).copy()
+        return (arr(p[0], C.c_int32, n), arr(p[1], C.c_float, 3 * n).reshape(n, 3), arr(p[2], C.c_int32, n),
+                arr(p[3], C.c_int32, n), arr(p[4], C.c_uint8, n))
 
     def last_smoothed(self):
         out = np.empty((self.H, self.W, 3), np.float32)
-        assert lib().vso_stream_last_smoothed(self.h, _ptr(out)) == 0
+        assert self.L.vso_stream_last_smoothed(self.h, _ptr(out)) == 0
         return out
 
     def export_halo(self):
         a = np.empty((self.H, self.W), np.int32)
         b = np.empty((self.H, self.W), np.int32)
         s = np.zeros(4, np.int64)
-        assert lib().vso_stream_export_halo(self.h, _ptr(a), _ptr(b), _ptr(s)) == 0
+        assert self.L.vso_stream_export_halo(self.h, _ptr(a), _ptr(b), _ptr(s)) == 0
         return a, b, s
 
     def import_halo(self, labels_virtual, labels_constrained, scalars):
         a = np.ascontiguousarray(labels_virtual, np.int32)
         b = np.ascontiguousarray(labels_constrained, np.int32)
         s = np.ascontiguousarray(scalars, np.int64)
-        lib().vso_stream_import_halo(self.h, _ptr(a), _ptr(b), _ptr(s))
+        self.L.vso_stream_import_halo(self.h, _ptr(a), _ptr(b), _ptr(s))
         held, self._held = getattr(self, "_held", None), None
         for (bgr, flow, flush) in held or []:
             n = self._process_frame(bgr, flow, flush)
@@ -343,15 +381,16 @@ def temporal_buckets(cur, prev, flow=None, l1=False):
 class OracleGraph:
     """DenseSegGraphInterface restatement (seam 3)."""
 
-    def __init__(self, width, height, max_frames, l1=False):
+    def __init__(self, width, height, max_frames, l1=False, L=None):
+        self.L = L if L is not None else lib()
         self.W, self.H, self.max_frames = width, height, max_frames
-        self.h = lib().vso_graph_create(width, height, max_frames, int(l1))
+        self.h = self.L.vso_graph_create(width, height, max_frames, int(l1))
         self._keep = []
         self.num_frames = 0
 
     def close(self):
         if self.h:
-            lib().vso_graph_destroy(self.h)
+            self.L.vso_graph_destroy(self.h)
             self.h = None
 
     def __del__(self):
@@ -362,30 +401,39 @@ class OracleGraph:
         self._keep.append(feat)
         if constraint_ids is not None:
             constraint_ids = np.ascontiguousarray(constraint_ids, np.int32)
-        lib().vso_graph_add_frame(self.h, _ptr(feat), _ptr(constraint_ids))
+        self.L.vso_graph_add_frame(self.h, _ptr(feat), _ptr(constraint_ids))
         self.num_frames += 1
 
     def add_virtual_frame(self, constraint_ids):
         constraint_ids = np.ascontiguousarray(constraint_ids, np.int32)
-        lib().vso_graph_add_virtual_frame(self.h, _ptr(constraint_ids))
+        self.L.vso_graph_add_virtual_frame(self.h, _ptr(constraint_ids))
         self.num_frames += 1
 
     def add_temporal(self, cur, prev, flow=None, is_virtual=False):
         if flow is not None:
             flow = np.ascontiguousarray(flow, np.float32)
             self._keep.append(flow)
-        lib().vso_graph_add_temporal(self.h, _ptr(cur), _ptr(prev), _ptr(flow), int(is_virtual))
+        self.L.vso_graph_add_temporal(self.h, _ptr(cur), _ptr(prev), _ptr(flow), int(is_virtual))
 
     def segment_spatially(self):
-        lib().vso_graph_segment_spatially(self.h)
+        self.L.vso_graph_segment_spatially(self.h)
 
     def segment(self, min_region_size, force_constraints):
-        lib().vso_graph_segment(self.h, min_region_size, int(force_constraints))
+        self.L.vso_graph_segment(self.h, min_region_size, int(force_constraints))
 
     def node_roots(self):
         out = np.empty(self.W * self.H * self.num_frames, np.int32)
-        lib().vso_graph_node_roots(self.h, _ptr(out))
+        self.L.vso_graph_node_roots(self.h, _ptr(out))
         return out
+
+    def node_states(self):
+        """(root, mean [n,3], size, constraint, flags) per node, between segment and obtain_results."""
+        n = self.W * self.H * self.num_frames
+        root, size, cons = (np.empty(n, np.int32) for _ in range(3))
+        mean = np.empty((n, 3), np.float32)
+        flags = np.empty(n, np.uint8)
+        self.L.vso_graph_node_states(self.h, _ptr(root), _ptr(mean), _ptr(size), _ptr(cons), _ptr(flags))
+        return root, mean, size, cons, flags
 
     def obtain_results(self, flows=None, enforce_n4=True, enforce_spatial_connectedness=True):
         arr = None
@@ -398,51 +446,51 @@ class OracleGraph:
                     arr[i] = f.ctypes.data
                 else:
                     arr[i] = None
-        lib().vso_graph_obtain_results(self.h, arr, int(enforce_n4),
+        self.L.vso_graph_obtain_results(self.h, arr, int(enforce_n4),
                                        int(enforce_spatial_connectedness))
 
     def num_regions(self):
-        return lib().vso_graph_num_regions(self.h)
+        return self.L.vso_graph_num_regions(self.h)
 
     def num_neighbor_links(self):
-        return lib().vso_graph_num_neighbor_links(self.h)
+        return self.L.vso_graph_num_neighbor_links(self.h)
 
     def index_image(self, t):
         out = np.empty((self.H, self.W), np.int32)
-        lib().vso_graph_index_image(self.h, t, _ptr(out))
+        self.L.vso_graph_index_image(self.h, t, _ptr(out))
         return out
 
     def region_sizes(self):
         n = self.num_regions()
         s = np.empty(n, np.int32)
         c = np.empty(n, np.int32)
-        lib().vso_graph_region_sizes(self.h, _ptr(s), _ptr(c))
+        self.L.vso_graph_region_sizes(self.h, _ptr(s), _ptr(c))
         return s, c
 
     def merge_stats(self):
         s = np.zeros(3, np.int64)
-        lib().vso_graph_merge_stats(self.h, _ptr(s))
+        self.L.vso_graph_merge_stats(self.h, _ptr(s))
         return s
 
     def get_regions(self):
         """RegionInfoList: (regions [n,5] = index, size, constrained_id, first, last frame;
         nbr_ptr [n+1]; nbr_idx)."""
         n = self.num_regions()
-        total = lib().vso_graph_get_regions(self.h, None, None, None)
+        total = self.L.vso_graph_get_regions(self.h, None, None, None)
         regs = np.empty((n, 5), np.int32)
         ptr = np.empty(n + 1, np.int32)
         idx = np.empty(max(total, 1), np.int32)
-        lib().vso_graph_get_regions(self.h, _ptr(regs), _ptr(ptr), _ptr(idx))
+        self.L.vso_graph_get_regions(self.h, _ptr(regs), _ptr(ptr), _ptr(idx))
         return regs, ptr, idx[:total]
 
     def get_intervals(self, t):
         """Scan intervals of slice t: [m,4] = region index, y, left_x, right_x."""
-        m = lib().vso_graph_get_intervals(self.h, t, None)
+        m = self.L.vso_graph_get_intervals(self.h, t, None)
         out = np.empty((max(m, 1), 4), np.int32)
-        lib().vso_graph_get_intervals(self.h, t, _ptr(out))
+        self.L.vso_graph_get_intervals(self.h, t, _ptr(out))
         return out[:m]
 
     def bucket_census(self):
         out = np.zeros((2048, 7), np.int64)
-        lib().vso_graph_bucket_census(self.h, _ptr(out))
+        self.L.vso_graph_bucket_census(self.h, _ptr(out))
         return out

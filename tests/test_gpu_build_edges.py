@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import edge_shape_cases as ec
+import node_states as ns
 from test_gpu_parity import bits, canon_partition
 
 pytestmark = pytest.mark.gpu
@@ -68,7 +69,8 @@ def test_slot_order_through_the_merge(vsg, W, H, min_size):
     g.add_frame_features(f1)
     g.add_temporal(flow)
     g.segment(min_size, False)
-    stats, roots = g.merge_stats(), g.node_roots()
+    stats, roots, states = g.merge_stats(), g.node_roots(), g.node_states()
     g.close()
     assert np.array_equal(stats, want_stats)
     assert np.array_equal(canon_partition(roots), canon_partition(want_roots))
+    ns.assert_states_equal(states, ec.oracle_merge_states(W, H, min_size), "%dx%d min %d" % (W, H, min_size), W, H)

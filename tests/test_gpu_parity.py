@@ -6,6 +6,7 @@ fields) must be byte-identical.
 import numpy as np
 import pytest
 
+import node_states as ns
 import oracle_lib as ol
 import synth
 
@@ -38,11 +39,12 @@ def bits(a):
     return np.ascontiguousarray(a, np.float32).view(np.uint32)
 
 
-def canon_partition(labels):
-    """Relabels by first occurrence so that two partitions can be compared exactly."""
-    _, first, inv = np.unique(labels, return_index=True, return_inverse=True)
-    order = np.argsort(np.argsort(first))
-    return order[inv]
+canon_partition = ns.canon_partition
+
+
+def assert_graph_states_equal(gg, og, what):
+    """The state the merge left in both graphs (between segment and obtain_results)."""
+    ns.assert_states_equal(gg.node_states(), og.node_states(), what, gg.W, gg.H)
 
 
 @pytest.mark.parametrize("W,H,kind,pad", [(64, 48, "noise", 0), (161, 97, "smooth", 5),
@@ -119,6 +121,7 @@ def test_graph_merge_and_readout(vsg, W, H, F, kind, flow):
     og.segment(minsz, False)
     assert np.array_equal(gg.merge_stats(), og.merge_stats())
     assert np.array_equal(canon_partition(gg.node_roots()), canon_partition(og.node_roots()))
+    assert_graph_states_equal(gg, og, "%dx%dx%d %s" % (W, H, F, kind))
     gg.obtain_results(use_flows=flow)
     og.obtain_results(flows)
     assert gg.num_regions() == og.num_regions()
@@ -192,6 +195,7 @@ def test_seam3_region_list_constrained_chunk(vsg):
     gg.segment(30, True)
     og.segment(30, True)
     assert np.array_equal(gg.merge_stats(), og.merge_stats())
+    assert_graph_states_equal(gg, og, "constrained chunk")
     gg.obtain_results(use_flows=True)
     og.obtain_results([None, fl, fl, fl, fl])
     assert_region_lists_equal(gg, og, 5)
@@ -202,7 +206,9 @@ def test_seam3_region_list_constrained_chunk(vsg):
 
 def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, on_chunk=None, **options):
     """Streams N frames through the HIP library and the CPU oracle side by side; every call must give
-    the same number of results, the same SegmentationDesc bytes and the same merge statistics.
+    the same number of results, the same SegmentationDesc bytes and the same merge statistics, and
+    every segmented chunk must leave the same state -- mean, size, constraint, flags of every region
+    (node_states.py) -- unless its graph is above node_states.NODE_CAP nodes.
     on_chunk(stream), if given, is called after every call that segmented a chunk (what that
     chunk's merge did: stream.last_merge_paths())."""
     rng = np.random.default_rng(seed)
@@ -212,7 +218,12 @@ def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, on_chunk=N
     os_ = ol.OracleStream(W, H, oo, has_flow=flow)
     fl = synth.const_flow(W, H) if flow else None
     total = 0
+    slices = 0   # of the chunk graph being built: a later chunk starts with a virtual and a constrained one
     for k in range(N):
+        slices += 1
+        keep = slices * W * H <= ns.NODE_CAP
+        gs.keep_node_states(keep)
+        os_.keep_node_states(keep)
         if frames is not None:
             frame = frames[k]
         elif kind == "probe":
@@ -235,6 +246,14 @@ def run_streams(vsg, W, H, N, kind, flow, chunk, seed=5, frames=None, on_chunk=N
                     (i, k, int((gi != oi).sum()), len(gb), len(ob)))
         if no:
             assert np.array_equal(gs.last_merge_stats(), os_.last_merge_stats())
+            what = "%dx%d chunk graph segmented at frame %d" % (W, H, k)
+            if keep:
+                assert ns.compare_stream_chunk(gs, os_, what)
+                assert len(gs.last_node_states()[0]) == slices * W * H
+            else:
+                print("node states: %s skipped, %d nodes are above the cap of %d" %
+                      (what, slices * W * H, ns.NODE_CAP))
+            slices = 2
             if on_chunk is not None:
                 on_chunk(gs)
         total += no
@@ -349,6 +368,8 @@ def test_two_stage_oversegment_stream_and_graph(vsg):
         o = ol.OracleStream(W, H, ol.default_options(chunk_size=chunk, two_stage_oversegment=1),
                             has_flow=True)
         plain = ol.OracleStream(W, H, ol.default_options(chunk_size=chunk), has_flow=True)
+        g.keep_node_states()
+        o.keep_node_states()
         rng = np.random.default_rng(3)
         fl = synth.const_flow(W, H)
         differs = False
@@ -361,6 +382,7 @@ def test_two_stage_oversegment_stream_and_graph(vsg):
             assert ng == no == npl
             if ng:
                 assert np.array_equal(g.last_merge_stats(), o.last_merge_stats())
+                assert ns.compare_stream_chunk(g, o, "two-stage %dx%d, frame %d" % (W, H, k))
             for i in range(ng):
                 assert g.result_bytes(i) == o.result_bytes(i), (k, i)
                 differs = differs or o.result_bytes(i) != plain.result_bytes(i)
@@ -386,9 +408,11 @@ def test_two_stage_oversegment_stream_and_graph(vsg):
     g.segment_spatially()
     o.segment_spatially()
     assert np.array_equal(g.merge_stats(), o.merge_stats())
+    assert_graph_states_equal(g, o, "after segment_spatially")
     g.segment(50, False)
     o.segment(50, False)
     assert np.array_equal(g.merge_stats(), o.merge_stats())
+    assert_graph_states_equal(g, o, "after segment")
     g.obtain_results(use_flows=False)
     o.obtain_results(None, True, True)
     assert g.num_regions() == o.num_regions()

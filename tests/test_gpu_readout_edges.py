@@ -7,6 +7,7 @@ import numpy as np
 import pytest
 
 import edge_shape_cases as ec
+import node_states as ns
 import oracle_lib as ol
 import synth
 from test_gpu_parity import assert_region_lists_equal
@@ -111,6 +112,7 @@ def test_readout_constrained_chunk(vsg):
     gg.segment(4, True)
     og.segment(4, True)
     assert np.array_equal(gg.merge_stats(), og.merge_stats())
+    ns.assert_states_equal(gg.node_states(), og.node_states(), "constrained 65x9 chunk", W, H)
     gg.obtain_results(use_flows=True)
     og.obtain_results([None] + [fl] * real)
     assert_region_lists_equal(gg, og, real + 1)

@@ -141,6 +141,7 @@ EXPORTED_SYMBOLS = [
     "vsg_vectorize_id_image",
     "vsg_stream_create", "vsg_stream_destroy", "vsg_stream_process_frame", "vsg_stream_chunk_size",
     "vsg_stream_result_bytes", "vsg_stream_result_id_image", "vsg_stream_last_merge_stats",
+    "vsg_stream_keep_node_states", "vsg_stream_last_node_states",
     "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_merge_paths", "vsg_stream_last_spine_paths",
     "vsg_stream_last_smoothed", "vsg_stream_export_halo",
     "vsg_stream_import_halo", "vsg_stream_expect_halo", "vsg_stream_restart",
@@ -155,6 +156,7 @@ EXPORTED_SYMBOLS = [
     "vsg_graph_region_sizes", "vsg_graph_index_image", "vsg_graph_get_regions",
     "vsg_graph_get_intervals", "vsg_graph_smoothed",
     "vsg_graph_spatial_buckets", "vsg_graph_temporal_buckets", "vsg_graph_node_roots",
+    "vsg_graph_node_states",
     "vsg_graph_merge_stats", "vsg_graph_timings", "vsg_graph_diagnostics", "vsg_graph_merge_paths",
     "vsg_graph_spine_paths",
     "vsg_debug_sort_pairs", "vsg_debug_sort_pairs_timed", "vsg_debug_exclusive_sum", "vsg_debug_runs_of_sorted_keys",
@@ -203,6 +205,8 @@ def lib():
     L.vsg_stream_result_bytes.argtypes = [vp, C.c_int, C.POINTER(vp), C.POINTER(C.c_size_t)]
     L.vsg_stream_result_id_image.argtypes = [vp, C.c_int, vp]
     L.vsg_stream_last_merge_stats.argtypes = [vp, vp]
+    L.vsg_stream_keep_node_states.argtypes = [vp, C.c_int]
+    L.vsg_stream_last_node_states.argtypes = [vp, C.POINTER(C.c_int64)] + [C.POINTER(vp)] * 5
     L.vsg_stream_last_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_stream_last_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
     L.vsg_stream_last_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
@@ -250,6 +254,7 @@ def lib():
     L.vsg_graph_spatial_buckets.argtypes = [vp, C.c_int, vp]
     L.vsg_graph_temporal_buckets.argtypes = [vp, C.c_int, vp, vp]
     L.vsg_graph_node_roots.argtypes = [vp, vp]
+    L.vsg_graph_node_states.argtypes = [vp, vp, vp, vp, vp, vp]
     L.vsg_graph_merge_stats.argtypes = [vp, vp]
     L.vsg_graph_timings.argtypes = [vp, C.POINTER(VsgTimings)]
     L.vsg_graph_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]

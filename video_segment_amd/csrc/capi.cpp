@@ -368,6 +368,28 @@ int vsg_stream_last_merge_stats(const vsg_stream* s, int64_t* st) {
   });
 }
 
+int vsg_stream_keep_node_states(vsg_stream* s, int on) {
+  return Guard([&] {
+    VSG_REQUIRE(s, VSG_ERR_INVALID, "null argument");
+    s->impl->keep_node_states(on != 0);
+  });
+}
+
+int vsg_stream_last_node_states(const vsg_stream* s, int64_t* n, const int32_t** root, const float** mean,
+                                const int32_t** size, const int32_t** constraint, const uint8_t** flags) {
+  return Guard([&] {
+    VSG_REQUIRE(s && n && root && mean && size && constraint && flags, VSG_ERR_INVALID, "null argument");
+    const auto& st = s->impl->last_node_states();
+    VSG_REQUIRE(!st.root.empty(), VSG_ERR_STATE, "no chunk has been segmented with keeping on");
+    *n = (int64_t)st.root.size();
+    *root = st.root.data();
+    *mean = st.mean.data();
+    *size = st.size.data();
+    *constraint = st.constraint.data();
+    *flags = st.flags.data();
+  });
+}
+
 int vsg_stream_last_timings(const vsg_stream* s, vsg_timings* t) {
   return Guard([&] {
     VSG_REQUIRE(s && t, VSG_ERR_INVALID, "null argument");
@@ -1110,6 +1132,15 @@ int vsg_graph_node_roots(vsg_graph* g, int32_t* out) {
     VSG_REQUIRE(g && out, VSG_ERR_INVALID, "null argument");
     DeviceGuard dg(g->device);
     g->g->CopyNodeRoots(out);
+  });
+}
+
+int vsg_graph_node_states(vsg_graph* g, int32_t* root, float* mean, int32_t* size, int32_t* constraint,
+                          uint8_t* flags) {
+  return Guard([&] {
+    VSG_REQUIRE(g && root && mean && size && constraint && flags, VSG_ERR_INVALID, "null argument");
+    DeviceGuard dg(g->device);
+    g->g->CopyNodeStates(root, mean, size, constraint, flags);
   });
 }
 

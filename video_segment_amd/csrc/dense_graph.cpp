@@ -2000,4 +2000,31 @@ void DenseGraphHip::CopyNodeRoots(int32_t* out) {
   VSG_HIP(hipStreamSynchronize(stream_));
 }
 
+// Like CopyNodeRoots, with the state of every node's representative gathered behind it.  The
+// device arrays are the call's own (label_uf_ and the other N-sized arrays carry what ObtainResults
+// left for the accessors that follow it).
+void DenseGraphHip::CopyNodeStates(int32_t* root, float* mean, int32_t* size, int32_t* cons,
+                                   uint8_t* flags) {
+  const size_t N = wh_ * (size_t)num_frames_;
+  if (N == 0) return;
+  DevBuf<int32_t> d_root(N), d_cons(N), d_flags(N);
+  DevBuf<float4> d_ds(N);
+  std::vector<float4> h_ds(N);
+  std::vector<int32_t> h_flags(N);
+  LaunchFlatten(nodes(), N, d_root.get(), stream_);
+  LaunchGatherStates(nodes(), d_root.get(), (int)N, d_ds.get(), d_cons.get(), d_flags.get(), stream_);
+  D2H(root, d_root.get(), N, stream_);
+  D2H(h_ds.data(), d_ds.get(), N, stream_);
+  D2H(cons, d_cons.get(), N, stream_);
+  D2H(h_flags.data(), d_flags.get(), N, stream_);
+  VSG_HIP(hipStreamSynchronize(stream_));
+  for (size_t i = 0; i < N; ++i) {
+    mean[3 * i + 0] = h_ds[i].x;
+    mean[3 * i + 1] = h_ds[i].y;
+    mean[3 * i + 2] = h_ds[i].z;
+    std::memcpy(&size[i], &h_ds[i].w, sizeof(int32_t));   // (the size travels as the bits of .w)
+    flags[i] = (uint8_t)h_flags[i];
+  }
+}
+
 }  // namespace vsg

@@ -103,6 +103,10 @@ class DenseGraphHip {
   void CopySpatialBuckets(int t, uint16_t* out_host);                     // [4][H][W]
   void CopyTemporalBuckets(int t, uint16_t* out_host, int32_t* prev_idx_host);   // [9][H][W]
   void CopyNodeRoots(int32_t* out_host);
+  // Entry i: representative of node i and that region's state as the last Segment /
+  // SegmentSpatially left it -- mean (3 f32 per node), size, constraint id, the flags byte as stored
+  // (device_graph.h: kFlag*).  Host outputs of W*H*num_frames entries.
+  void CopyNodeStates(int32_t* root, float* mean, int32_t* size, int32_t* cons, uint8_t* flags);
 
  private:
   struct ListBuf {

@@ -325,6 +325,16 @@ void DenseSegmentationHip::SegmentAndOutputChunk(bool flush) {
   graph_->FinishBuilding();
   if (options_.two_stage_oversegment) graph_->SegmentSpatially();   // segmentation.cpp:280-283
   graph_->Segment(MinRegionSize(), true);
+  if (keep_node_states_) {
+    const size_t n = wh_ * (size_t)graph_->num_frames();
+    node_states_.root.resize(n);
+    node_states_.size.resize(n);
+    node_states_.constraint.resize(n);
+    node_states_.mean.resize(3 * n);
+    node_states_.flags.resize(n);
+    graph_->CopyNodeStates(node_states_.root.data(), node_states_.mean.data(), node_states_.size.data(),
+                           node_states_.constraint.data(), node_states_.flags.data());
+  }
   graph_->ObtainResults(have_flows ? &flows : nullptr, options_.enforce_n4_connectivity != 0,
                         options_.enforce_spatial_connectedness != 0);
   const double t_host0 = NowMs();

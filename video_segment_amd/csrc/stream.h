@@ -90,6 +90,16 @@ class DenseSegmentationHip {
   const std::string& result_bytes(int i);
   const SegDesc& result(int i) const { return *results_[i]; }
   void last_merge_stats(int64_t* s3) const;
+  // Parity hook (vsg_stream_keep_node_states): while on, the per-node state of every segmented chunk
+  // is copied to host memory between Segment and ObtainResults -- the next chunk's graph is opened
+  // inside the same ProcessFrame call, so nothing of it can be read afterwards.
+  struct NodeStates {
+    std::vector<int32_t> root, size, constraint;
+    std::vector<float> mean;
+    std::vector<uint8_t> flags;
+  };
+  void keep_node_states(bool on) { keep_node_states_ = on; }
+  const NodeStates& last_node_states() const { return node_states_; }
   const vsg_timings& last_timings() const { return last_timings_; }
   const GraphTimings& last_graph_timings() const { return last_graph_timings_; }
   void CopyLastSmoothed(float* out_interleaved_host);
@@ -152,6 +162,8 @@ class DenseSegmentationHip {
   std::vector<std::unique_ptr<SegDesc>> results_;
   std::vector<std::string> encoded_;
   int64_t last_merge_stats_[3] = {0, 0, 0};
+  bool keep_node_states_ = false;
+  NodeStates node_states_;
   vsg_timings last_timings_;
   GraphTimings last_graph_timings_;   // the graph's own record of the last segmented chunk (diagnostics)
   vsg_timings accum_;   // preprocess / edge time accumulated while the chunk is being built

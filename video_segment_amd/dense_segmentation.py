@@ -131,6 +131,23 @@ class DenseSegmentation:
         check(lib().vsg_stream_last_merge_stats(self.h, s.ctypes.data_as(C.c_void_p)))
         return s
 
+    def keep_node_states(self, on=True):
+        """Parity hook: snapshot the merge's per-node state of every chunk segmented from now on."""
+        check(lib().vsg_stream_keep_node_states(self.h, int(on)))
+
+    def last_node_states(self):
+        """(root, mean [n,3], size, constraint, flags) of the last segmented chunk's graph, copied:
+        entry i is the state of node i's representative (vsg_stream_last_node_states)."""
+        n = C.c_int64()
+        p = [C.c_void_p() for _ in range(5)]
+        check(lib().vsg_stream_last_node_states(self.h, C.byref(n), *[C.byref(x) for x in p]))
+        n = n.value
+
+        def arr(ptr, ctype, count):
+            return np.ctypeslib.as_array(C.cast(ptr, C.POINTER(ctype)), shape=(count,)).copy()
+        return (arr(p[0], C.c_int32, n), arr(p[1], C.c_float, 3 * n).reshape(n, 3), arr(p[2], C.c_int32, n),
+                arr(p[3], C.c_int32, n), arr(p[4], C.c_uint8, n))
+
     def last_timings(self):
         t = VsgTimings()
         check(lib().vsg_stream_last_timings(self.h, C.byref(t)))
@@ -356,6 +373,17 @@ class DenseSegGraph:
         out = np.empty(self.W * self.H * self.num_frames(), np.int32)
         check(lib().vsg_graph_node_roots(self.h, out.ctypes.data_as(C.c_void_p)))
         return out
+
+    def node_states(self):
+        """(root, mean [n,3], size, constraint, flags): per node, the state of its representative as
+        of the last segment / segment_spatially (vsg_graph_node_states)."""
+        n = self.W * self.H * self.num_frames()
+        root, size, cons = (np.empty(n, np.int32) for _ in range(3))
+        mean = np.empty((n, 3), np.float32)
+        flags = np.empty(n, np.uint8)
+        check(lib().vsg_graph_node_states(self.h, *[a.ctypes.data_as(C.c_void_p)
+                                                    for a in (root, mean, size, cons, flags)]))
+        return root, mean, size, cons, flags
 
     def merge_stats(self):
         s = np.zeros(3, np.int64)
