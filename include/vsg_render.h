@@ -42,8 +42,9 @@
  * reference's GetBoundary (segment_util/segmentation_boundary.{h,cpp}), the N4 inner or outer boundary
  * pixels of a rasterization in row-major order.  Contour tracing at a level (BoundaryComputation,
  * segmentation/boundary.cpp) is offered by vsg_render_level_contours: the closed outlines of every region or
- * component as ordered vertex lists.  Still not offered: the reference's shared-segment mesh (segments cut at
- * junctions and shared by the two regions they separate) and its approxPolyDP simplification.
+ * component as ordered vertex lists.  The reference's shared-segment mesh (segments cut at junctions and
+ * shared by the two regions they separate) is offered by vsg_render_level_mesh, at any level and for
+ * components; the approxPolyDP simplification of its segments is still not offered.
  * Which regions or components of a level touch in a frame, and along how many pixel sides, is what
  * vsg_render_level_adjacency returns; the reference has no per-frame counterpart
  * (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
@@ -754,6 +755,95 @@ typedef struct vsg_render_contour_stats {
   int rounds, launches;
 } vsg_render_contour_stats;               /* 64 bytes */
 int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s);
+
+/* ---- Level mesh: the contours of a level cut at the junctions into segments shared by two groups ----
+ *
+ * vsg_render_level_contours gives every group its own closed polygons, so the border between two groups is
+ * stored twice.  The mesh stores it once: every contour is a list of references to segments, and a segment
+ * between two groups is referenced by both, by one of them backwards.
+ *
+ * The plane P, groups, group index k, cracks, crack keys, direction of travel and the successor rule are those
+ * of vsg_render_level_contours for the same (level, connectedness).  Positions outside the frame count as -1,
+ * and so do uncovered pixels.
+ *
+ * Sides at a corner.  Lattice corner (cx, cy) is surrounded clockwise by the pixels (cx-1, cy-1), (cx, cy-1),
+ * (cx, cy), (cx-1, cy).  sides(cx, cy) is the number of cyclically adjacent pairs among these four with
+ * different values of P.  It is 0, 2, 3 or 4.  A corner with sides >= 3 is a junction.  Junctions include the
+ * saddle a, b, a, b and a region border arriving at the frame edge (a, b, -1).  The four frame corners and a
+ * -1/-1 contact are not junctions.
+ *
+ * Halves.  Every contour is a cycle of cracks.  It is cut at every crack whose start corner is a junction.
+ * The pieces are the contour's halves.  A contour without a junction is one closed half that begins at its
+ * leader, the turn crack of smallest key, as in the contours call.  All cracks of a half have the same value
+ * across them.  This value is the half's other side, a group or -1.
+ *
+ * Segments.  A half is an owner when the group index of its other side is smaller than its own.  -1 counts
+ * as smaller than every group.  Every half whose other side is a group has exactly one twin.  The twin is the
+ * half of that group made of the opposite sides (pixel across, side + 2) in reverse order.  Exactly one of
+ * the two is the owner.  A segment is an owner half.  Segments are listed in (right group index, key of the
+ * half's first crack) order.
+ *
+ * The vertex list of an open segment, in the owner's direction of travel, holds the start corner of its first
+ * crack, the start corners of its later turn cracks, and the end corner of its last crack.  Both end corners
+ * are always listed, including where the curve runs straight through the junction.  Interior collinear
+ * corners are never listed.  A closed segment lists exactly its contour's vertices and repeats none.  A half
+ * that starts and ends at the same junction is open, not closed; an island that touches another island
+ * diagonally is such a case.
+ *
+ * Loops and refs.  Loop c is contour c of the sibling contours call, with the same count and the same order.
+ * Its refs are its halves in travel order.  The list begins with the half that contains the contour's leader
+ * crack.  An owner half is written as its segment index s.  The other half is written as ~s: the same
+ * segment travelled backwards. */
+typedef struct vsg_render_mesh_segment {   /* 32 bytes, no padding */
+  int32_t right, left;            /* group index on the right hand (the owner) and on the left hand; left = -1: none */
+  int32_t first_vertex, num_vertices;   /* slice of `vertices`; open: >= 2, closed: even and >= 4 */
+  int32_t length;                 /* cracks */
+  int32_t closed;                 /* 1: a contour without a junction */
+  int32_t start_sides, end_sides; /* sides() at the first and last corner: 3 or 4; both 0 when closed */
+} vsg_render_mesh_segment;
+typedef struct vsg_render_mesh_loop {      /* 16 bytes, no padding */
+  int32_t group, first_ref, num_refs, length;   /* length = the contour's = the sum over its refs */
+} vsg_render_mesh_loop;
+
+/* vertices: int32 pairs {x, y}, grouped by segment in list order; capacity_vertices and *num_vertices count
+ * pairs.  refs: int32, grouped by loop in list order.
+ *
+ * Decode, hierarchy rules (the desc's own hierarchy replaces the kept one), level refusals, the non-negative
+ * ids and the handling of vector-only descs are those of vsg_render_level_regions.  *num_segments,
+ * *num_vertices, *num_loops and *num_refs are always set on VSG_OK and when a capacity is too small; in that
+ * case the call fails with VSG_ERR_INVALID and no output is touched.  All four outputs NULL with all four
+ * capacities 0 asks for the counts only (VSG_OK; needs the device).  A null handle, a null count pointer, a
+ * memory kind other than the two, or a connectedness other than 0, VSG_RENDER_CONNECT_N4 and
+ * VSG_RENDER_CONNECT_N8 is VSG_ERR_INVALID, answered before the handle is dereferenced.  A frame with no
+ * covered pixel returns four zero counts.  The call neither resolves nor changes the level the handle keeps
+ * for vsg_render_frame (vsg_render_level).  Counts are 32-bit like the siblings': a handle whose crack keys
+ * would not fit (4 * W * H above 2^31) is refused with VSG_ERR_INVALID.  All four lists in mem_out memory.
+ *
+ * The call runs the stages of vsg_render_level_contours internally, as a count-only call: afterwards
+ * vsg_render_last_contour_stats (and, for N4 / N8, vsg_render_last_component_stats) describe that run. */
+int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments,
+                          int32_t* vertices, size_t capacity_vertices, size_t* num_vertices,
+                          vsg_render_mesh_loop* loops, size_t capacity_loops, size_t* num_loops,
+                          int32_t* refs, size_t capacity_refs, size_t* num_refs, int mem_out);
+
+/* What the last vsg_render_level_mesh call of the handle did.  cracks: as in vsg_render_contour_stats;
+ * segments, vertices, loops, refs: the lengths of the four lists; closed_segments: segments with closed = 1;
+ * shared_segments: segments with left >= 0; junctions: corners with sides >= 3; longest_segment_cracks: the
+ * longest `length`.  Device times are HIP events around the stages: plane_us and classify_us, those of the
+ * contour stages; trace_us, the contour stages' trace_us + table_us; split_us, the junction bits, the third
+ * pointer doubling and the halves; table_us, the segments' sort, the vertices, the records, loops, refs,
+ * lengths and the copies.  rounds: the rounds of all three doublings, three times ceil(log2 cracks) made even.
+ * launches, those of the contour stages included, is a function of the connectedness, of ceil(log2 cracks),
+ * of where the outputs go and of how the plane is made, not of the plane's content.  Everything but cracks
+ * is 0 when there is no crack. */
+typedef struct vsg_render_mesh_stats {
+  int64_t cracks, segments, closed_segments, shared_segments, vertices, loops, refs, junctions,
+      longest_segment_cracks;
+  float plane_us, classify_us, trace_us, split_us, table_us;
+  int rounds, launches;
+} vsg_render_mesh_stats;                  /* 104 bytes with 4 bytes of tail padding */
+int vsg_render_last_mesh_stats(vsg_render* h, vsg_render_mesh_stats* s);
 
 /* ---- Boundary distance: the exact distance transform of a level's edges, boundary scores of all levels ----
  *

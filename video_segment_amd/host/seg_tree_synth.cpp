@@ -55,6 +55,12 @@
 // components, for every frame and prints
 // level_contours_count=<sum> level_contours_fnv1a32=<hash of every frame's records, then its vertices' bytes>.
 //
+//   --level_mesh <level> [--mesh_components [--components_n8]]
+// asks vsg_render_level_mesh for the shared-segment mesh of that level's regions, or of their connected
+// components, for every frame and prints
+// level_mesh_count=<segments over all frames> level_mesh_fnv1a32=<hash of every frame's segments, vertices,
+// loops and refs bytes, in that order>.
+//
 //   --boundary_distance <level>
 // asks vsg_render_boundary_distance for the exact squared distance of every pixel to that level's nearest
 // edge pixel, for every frame, and prints a line
@@ -522,6 +528,73 @@ class LevelContoursSinkUnit : public VideoUnit {
   std::vector<vsg_render_level_contour> records_buf_;
   std::vector<int32_t> vertices_buf_;
   long contours_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
+// --level_mesh: the same for the shared-segment mesh of a level's regions or of their connected components
+// (vsg_render_level_mesh): segments, vertices, loops, refs.
+class LevelMeshSinkUnit : public VideoUnit {
+ public:
+  LevelMeshSinkUnit(int level, int connectedness, int device)
+      : level_(level), connect_(connectedness), device_(device) {}
+  ~LevelMeshSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    size_t ns = 0, nv = 0, nl = 0, nr = 0;
+    VF_CHECK(vsg_render_level_mesh(render_, seg, desc.wire.size(), level_, connect_, nullptr, 0, &ns, nullptr, 0, &nv,
+                                   nullptr, 0, &nl, nullptr, 0, &nr, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    segments_buf_.resize(ns);
+    vertices_buf_.resize(2 * nv);
+    loops_buf_.resize(nl);
+    refs_buf_.resize(nr);
+    if (ns) {
+      VF_CHECK(vsg_render_level_mesh(render_, seg, desc.wire.size(), level_, connect_, segments_buf_.data(), ns, &ns,
+                                     vertices_buf_.data(), nv, &nv, loops_buf_.data(), nl, &nl, refs_buf_.data(), nr,
+                                     &nr, VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+    }
+    Hash(segments_buf_.data(), ns * sizeof(vsg_render_mesh_segment));
+    Hash(vertices_buf_.data(), nv * 2 * sizeof(int32_t));
+    Hash(loops_buf_.data(), nl * sizeof(vsg_render_mesh_loop));
+    Hash(refs_buf_.data(), nr * sizeof(int32_t));
+    segments_ += (long)ns;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long segments() const { return segments_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  std::vector<vsg_render_mesh_segment> segments_buf_;
+  std::vector<int32_t> vertices_buf_;
+  std::vector<vsg_render_mesh_loop> loops_buf_;
+  std::vector<int32_t> refs_buf_;
+  long segments_ = 0;
   uint32_t hash_ = 2166136261u;
 };
 
@@ -1030,6 +1103,10 @@ struct Flags {
   // (N4, or N8 with --components_n8) with --contours_components
   int level_contours = -1;
   bool contours_components = false;
+  // vsg_render_level_mesh at this level for every frame; < 0: off.  Of the regions, or of the components
+  // (N4, or N8 with --components_n8) with --mesh_components
+  int level_mesh = -1;
+  bool mesh_components = false;
   // vsg_render_boundary_distance at this level for every frame; < 0: off
   int boundary_distance = -1;
   // vsg_render_boundary_benchmark with this tolerance_sq for every frame after the first, against the
@@ -1069,7 +1146,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
                                    "adjacency_components", "overlap_components", "persistence", "colors_components",
-                                   "contours_components",
+                                   "contours_components", "mesh_components",
                                    "help"};
     bool is_bool = false, negated = false;
     for (const char* b : kBools) {
@@ -1132,6 +1209,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "boundary_distance") f->boundary_distance = atoi(v.c_str());
     else if (a == "boundary_benchmark") f->boundary_benchmark = atoi(v.c_str());
     else if (a == "contours_components") f->contours_components = bv;
+    else if (a == "level_mesh") f->level_mesh = atoi(v.c_str());
+    else if (a == "mesh_components") f->mesh_components = bv;
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -1391,6 +1470,15 @@ int main(int argc, char** argv) {
     contours_sink->AttachTo(input);
     input = contours_sink.get();
   }
+  std::unique_ptr<LevelMeshSinkUnit> mesh_sink;
+  if (FLAGS.level_mesh >= 0) {
+    const int connectedness = !FLAGS.mesh_components ? 0
+                              : FLAGS.components_n8  ? VSG_RENDER_CONNECT_N8
+                                                     : VSG_RENDER_CONNECT_N4;
+    mesh_sink.reset(new LevelMeshSinkUnit(FLAGS.level_mesh, connectedness, FLAGS.device));
+    mesh_sink->AttachTo(input);
+    input = mesh_sink.get();
+  }
   std::unique_ptr<BoundaryDistanceSinkUnit> distance_sink;
   if (FLAGS.boundary_distance >= 0 || FLAGS.boundary_benchmark >= 0) {
     distance_sink.reset(new BoundaryDistanceSinkUnit(FLAGS.boundary_distance, FLAGS.boundary_benchmark, FLAGS.device));
@@ -1471,6 +1559,9 @@ int main(int argc, char** argv) {
   if (contours_sink) {
     std::printf("level_contours_count=%ld level_contours_fnv1a32=%08x\n", contours_sink->contours(),
                 contours_sink->hash());
+  }
+  if (mesh_sink) {
+    std::printf("level_mesh_count=%ld level_mesh_fnv1a32=%08x\n", mesh_sink->segments(), mesh_sink->hash());
   }
   if (distance_sink && distance_sink->level() >= 0) {
     std::printf("boundary_distance_level=%d boundary_distance_edge_pixels=%ld boundary_distance_max=%ld "

@@ -119,6 +119,17 @@ class VsgRenderContourStats(_capi.Structure):
     ]
 
 
+class VsgRenderMeshStats(_capi.Structure):
+    _fields_ = [
+        ("cracks", C.c_int64), ("segments", C.c_int64), ("closed_segments", C.c_int64),
+        ("shared_segments", C.c_int64), ("vertices", C.c_int64), ("loops", C.c_int64), ("refs", C.c_int64),
+        ("junctions", C.c_int64), ("longest_segment_cracks", C.c_int64),
+        ("plane_us", C.c_float), ("classify_us", C.c_float), ("trace_us", C.c_float), ("split_us", C.c_float),
+        ("table_us", C.c_float),
+        ("rounds", C.c_int), ("launches", C.c_int),
+    ]
+
+
 class VsgRenderDistanceStats(_capi.Structure):
     _fields_ = [
         ("levels", C.c_int64), ("edge_pixels", C.c_int64), ("other_edge_pixels", C.c_int64),
@@ -221,6 +232,21 @@ LEVEL_CONTOUR_DTYPE = np.dtype([
 assert LEVEL_CONTOUR_DTYPE.itemsize == 48
 LEVEL_CONTOUR_WORDS = 12
 
+# vsg_render_mesh_segment: 32 bytes, no padding
+MESH_SEGMENT_DTYPE = np.dtype([
+    ("right", np.int32), ("left", np.int32), ("first_vertex", np.int32), ("num_vertices", np.int32),
+    ("length", np.int32), ("closed", np.int32), ("start_sides", np.int32), ("end_sides", np.int32),
+])
+assert MESH_SEGMENT_DTYPE.itemsize == 32
+MESH_SEGMENT_WORDS = 8
+
+# vsg_render_mesh_loop: 16 bytes, no padding
+MESH_LOOP_DTYPE = np.dtype([
+    ("group", np.int32), ("first_ref", np.int32), ("num_refs", np.int32), ("length", np.int32),
+])
+assert MESH_LOOP_DTYPE.itemsize == 16
+MESH_LOOP_WORDS = 4
+
 # vsg_render_boundary_score: 32 bytes, no padding
 BOUNDARY_SCORE_DTYPE = np.dtype([
     ("seg_edges", np.int64), ("seg_matched", np.int64), ("gt_edges", np.int64), ("gt_matched", np.int64),
@@ -251,6 +277,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_last_persistence_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
     "vsg_render_level_contours", "vsg_render_last_contour_stats",
+    "vsg_render_level_mesh", "vsg_render_last_mesh_stats",
     "vsg_render_boundary_distance", "vsg_render_boundary_benchmark", "vsg_render_last_distance_stats",
 ]
 
@@ -318,6 +345,11 @@ def lib():
     L.vsg_render_level_contours.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t,
                                             C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_contour_stats.argtypes = [vp, C.POINTER(VsgRenderContourStats)]
+    L.vsg_render_level_mesh.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int,
+                                        vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                        vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                        C.c_int]
+    L.vsg_render_last_mesh_stats.argtypes = [vp, C.POINTER(VsgRenderMeshStats)]
     L.vsg_render_boundary_distance.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_int]
     L.vsg_render_boundary_benchmark.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp,
                                                 C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
@@ -914,6 +946,68 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_contour_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def level_mesh(self, seg_bytes, level=0, connectedness=0, segments_out=None, vertices_out=None, loops_out=None,
+                   refs_out=None):
+        """The shared-segment mesh of hierarchy level `level`: the contours of level_contours (same level, same
+        connectedness) cut at the junction corners into segments, each stored once and shared by the two groups
+        it separates: (segments, vertices, loops, refs).  segments: a MESH_SEGMENT_DTYPE array in (right, first
+        crack) order, `right` and `left` being group indices as in level_contours, left = -1 for the frame and
+        uncovered pixels.  vertices: (n, 2) int32 corners, grouped by segment, in the direction that has `right`
+        on the right hand; open segments list both end corners.  loops: a MESH_LOOP_DTYPE array, loop c being
+        contour c of level_contours.  refs: int32, grouped by loop in travel order: s is segment s forwards, ~s
+        segment s backwards.  Without outputs the counts are asked for first and the arrays are allocated
+        exactly.  *_out: buffers to fill instead, all four numpy (the two dtypes, (capacity, 2) int32 and
+        (capacity,) int32) or all four torch CUDA int32 tensors ((capacity, 8), (capacity, 2), (capacity, 4),
+        (capacity,)); the filled parts of them are returned.  See mesh_polygons and mesh_desc."""
+        seg_bytes = bytes(seg_bytes)
+        ns, nv, nl, nr = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
+        outs = (segments_out, vertices_out, loops_out, refs_out)
+        if any(o is None for o in outs) and not all(o is None for o in outs):
+            raise ValueError("pass all four outputs or none")
+        if segments_out is None:
+            check(lib().vsg_render_level_mesh(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                              None, 0, C.byref(ns), None, 0, C.byref(nv), None, 0, C.byref(nl),
+                                              None, 0, C.byref(nr), VSG_MEM_HOST))
+            segments_out = np.empty(ns.value, MESH_SEGMENT_DTYPE)
+            vertices_out = np.empty((nv.value, 2), np.int32)
+            loops_out = np.empty(nl.value, MESH_LOOP_DTYPE)
+            refs_out = np.empty(nr.value, np.int32)
+            if ns.value == 0:
+                return segments_out, vertices_out, loops_out, refs_out
+            outs = (segments_out, vertices_out, loops_out, refs_out)
+        if len({_capi.is_torch(o) for o in outs}) != 1:
+            raise ValueError("all outputs have to be numpy arrays or all torch tensors")
+        if _capi.is_torch(segments_out):
+            for o, words, name in ((segments_out, MESH_SEGMENT_WORDS, "segments_out"),
+                                   (loops_out, MESH_LOOP_WORDS, "loops_out")):
+                if o.dim() != 2 or o.shape[1] != words or str(o.dtype) != "torch.int32":
+                    raise ValueError("%s has to be (capacity, %d) int32" % (name, words))
+        else:
+            if segments_out.dtype != MESH_SEGMENT_DTYPE or segments_out.ndim != 1:
+                raise ValueError("segments_out has to be a one-dimensional MESH_SEGMENT_DTYPE array")
+            if loops_out.dtype != MESH_LOOP_DTYPE or loops_out.ndim != 1:
+                raise ValueError("loops_out has to be a one-dimensional MESH_LOOP_DTYPE array")
+        if (len(vertices_out.shape) != 2 or vertices_out.shape[1] != 2
+                or str(vertices_out.dtype).replace("torch.", "") != "int32"):
+            raise ValueError("vertices_out has to be (capacity, 2) int32")
+        if len(refs_out.shape) != 1 or str(refs_out.dtype).replace("torch.", "") != "int32":
+            raise ValueError("refs_out has to be (capacity,) int32")
+        ptrs = [_capi.contiguous_ptr(o) for o in outs]
+        if len({mem for _, mem in ptrs}) != 1:
+            raise ValueError("all outputs have to be in the same kind of memory")
+        check(lib().vsg_render_level_mesh(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                          ptrs[0][0], segments_out.shape[0], C.byref(ns),
+                                          ptrs[1][0], vertices_out.shape[0], C.byref(nv),
+                                          ptrs[2][0], loops_out.shape[0], C.byref(nl),
+                                          ptrs[3][0], refs_out.shape[0], C.byref(nr), ptrs[0][1]))
+        return segments_out[:ns.value], vertices_out[:nv.value], loops_out[:nl.value], refs_out[:nr.value]
+
+    def last_mesh_stats(self):
+        """vsg_render_last_mesh_stats of the last level_mesh call, as a dict."""
+        s = VsgRenderMeshStats()
+        check(lib().vsg_render_last_mesh_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def boundary_distance(self, seg_bytes, level=0, out=None):
         """The exact squared Euclidean distance from every pixel to the nearest edge pixel of hierarchy level
         `level`: H x W int32, 0 exactly where id_image(seg, level) differs from its right or below neighbour,
@@ -1037,3 +1131,99 @@ def contour_polygons(contours, vertices):
     for c in contours:
         groups[int(c["group"])].append(vertices[int(c["first_vertex"]):int(c["first_vertex"]) + int(c["num_vertices"])])
     return groups
+
+
+def _loop_points(segments, vertices, loop, refs):
+    """The closed vertex list of one loop as a list of (x, y): its refs joined, every joint once."""
+    points = []
+    for ref in refs[int(loop["first_ref"]):int(loop["first_ref"]) + int(loop["num_refs"])]:
+        ref = int(ref)
+        seg = segments[ref if ref >= 0 else ~ref]
+        part = vertices[int(seg["first_vertex"]):int(seg["first_vertex"]) + int(seg["num_vertices"])].tolist()
+        if ref < 0:
+            part.reverse()
+        points += part if seg["closed"] else part[:-1]      # an open segment ends where the next ref begins
+    return points
+
+
+def mesh_polygons(segments, vertices, loops, refs):
+    """The host arrays of level_mesh as polygons: a list with one entry per group, in group order, each the list
+    of that group's (n, 2) int32 vertex arrays, one per loop in loop order.  Every loop is rebuilt from its refs:
+    joints listed once, collinear corners dropped, rotated to begin at the start corner of its turn crack of
+    smallest key, so that the result equals contour_polygons of the level_contours call.  Host numpy only."""
+    segments, vertices, loops, refs = (np.asarray(a) for a in (segments, vertices, loops, refs))
+    groups = [[] for _ in range(int(loops["group"].max()) + 1 if len(loops) else 0)]
+    side_of = {(1, 0): 0, (0, 1): 1, (-1, 0): 2, (0, -1): 3}
+    start = ((0, 0), (1, 0), (1, 1), (0, 1))
+    for loop in loops:
+        pts = _loop_points(segments, vertices, loop, refs)
+        n = len(pts)
+
+        def direction(a, b):
+            return ((b[0] > a[0]) - (b[0] < a[0]), (b[1] > a[1]) - (b[1] < a[1]))
+
+        kept = [k for k in range(n) if direction(pts[k - 1], pts[k]) != direction(pts[k], pts[(k + 1) % n])]
+        pts = [pts[k] for k in kept]
+        n = len(pts)
+        # the crack that starts at corner k: side s of pixel corner - start[s]; keys order like (y, x, s)
+        keys = []
+        for k in range(n):
+            s = side_of[direction(pts[k], pts[(k + 1) % n])]
+            keys.append((pts[k][1] - start[s][1], pts[k][0] - start[s][0], s))
+        first = keys.index(min(keys))
+        groups[int(loop["group"])].append(np.asarray(pts[first:] + pts[:first], np.int32).reshape(-1, 2))
+    return groups
+
+
+def _varint(v):
+    v &= (1 << 64) - 1
+    out = bytearray()
+    while v >= 0x80:
+        out.append((v & 0x7f) | 0x80)
+        v >>= 7
+    out.append(v)
+    return bytes(out)
+
+
+def _field(number, payload):
+    """A length-delimited field."""
+    return _varint(number << 3 | 2) + _varint(len(payload)) + payload
+
+
+def mesh_desc(width, height, group_ids, segments, vertices, loops, refs):
+    """The host arrays of level_mesh as the bytes of a vector-only SegmentationDesc of width x height:
+    frame_width / frame_height, rasterization_removed, one vector_mesh in which every distinct corner occurs
+    once, one Region2D per distinct id of group_ids (the region id of every group index, e.g. the `id` column
+    of level_regions or level_components) in ascending id order, its vectorization holding one polygon per
+    loop of its groups, the first point repeated at the end, `hole` set where the loop's area is negative.
+    rasterize() of the same size scan-converts it back to the level's id plane.  Host numpy only."""
+    polygons = mesh_polygons(segments, vertices, loops, refs)
+    group_ids = [int(i) for i in np.asarray(group_ids).tolist()]
+    if len(polygons) > len(group_ids):
+        raise ValueError("group_ids has fewer entries than the loops have groups")
+    index = {}
+    coord = []
+    by_id = {}
+    for g, polys in enumerate(polygons):
+        for pts in polys:
+            pts = pts.tolist()
+            area2 = sum(pts[k][0] * pts[(k + 1) % len(pts)][1] - pts[(k + 1) % len(pts)][0] * pts[k][1]
+                        for k in range(len(pts)))
+            idx = []
+            for x, y in pts + pts[:1]:
+                if (x, y) not in index:
+                    index[(x, y)] = len(coord)
+                    coord += [float(x), float(y)]
+                idx.append(index[(x, y)])
+            polygon = _field(1, b"".join(_varint(i) for i in idx))           # Polygon.coord_idx, packed
+            if area2 < 0:
+                polygon += _varint(2 << 3) + _varint(1)                       # Polygon.hole
+            by_id.setdefault(group_ids[g], []).append(_field(1, polygon))    # Vectorization.polygon
+    out = bytearray()
+    for rid in sorted(by_id):
+        region = _varint(1 << 3) + _varint(rid) + _field(6, b"".join(by_id[rid]))   # Region2D.id, .vectorization
+        out += _field(2, region)                                             # SegmentationDesc.region
+    out += _varint(4 << 3) + _varint(int(width)) + _varint(5 << 3) + _varint(int(height))
+    out += _field(11, _field(1, np.asarray(coord, "<f4").tobytes()))         # vector_mesh.coord, packed
+    out += _varint(13 << 3) + _varint(1)                                     # rasterization_removed
+    return bytes(out)

@@ -437,6 +437,14 @@ const uint2* LaunchContourTrace(const uint32_t* key, const uint32_t* succ, uint3
   return in;
 }
 
+const uint2* LaunchContourSums(uint2* in, uint2* out, uint32_t n, int rounds, hipStream_t stream) {
+  for (int r = 0; r < rounds; r += 2) {
+    hipLaunchKernelGGL((k_contour_round<true>), GridOf(n), dim3(kContourBlock), 0, stream, in, out, n);
+    std::swap(in, out);
+  }
+  return in;
+}
+
 void LaunchContourLeaders(const uint32_t* leader, const uint32_t* key, const int32_t* plane, uint32_t n,
                           uint32_t capacity, unsigned long long* ckeys, ContourStatus* status, hipStream_t stream) {
   hipLaunchKernelGGL(k_contour_leaders, GridOf(n), dim3(kContourBlock), 0, stream, leader, key, plane, n, capacity,

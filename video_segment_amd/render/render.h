@@ -432,6 +432,10 @@ int ContourRounds(uint32_t n);
 // cracks in [i, leader) along the contour, 0 for the leader.  The other buffer is free afterwards.
 const uint2* LaunchContourTrace(const uint32_t* key, const uint32_t* succ, uint32_t n, int rounds, uint2* state_a,
                                 uint2* state_b, uint32_t* leader, ContourStatus* status, hipStream_t stream);
+// The summing rounds alone (k_contour_round<true>), rounds / 2 launches from `in` to `out` and back: for a
+// state {next, weight} whose fixed points weigh 0, .y becomes the sum of the weights from i up to its fixed
+// point.  Every .x has to be below n.  Returns the buffer that holds the result; the other one is free.
+const uint2* LaunchContourSums(uint2* in, uint2* out, uint32_t n, int rounds, hipStream_t stream);
 // ckeys[slot] = group << 32 | leader of every contour, in no order; status->contours.  ckeys has `capacity`
 // entries, set to ~0 before so that unused slots sort last.
 void LaunchContourLeaders(const uint32_t* leader, const uint32_t* key, const int32_t* plane, uint32_t n,
@@ -458,6 +462,91 @@ void LaunchContourTable(const unsigned long long* ckeys_sorted, const uint32_t* 
 void LaunchContourCopy(const int32_t* records, const int32_t* vertices, uint32_t capacity, uint32_t n,
                        uint32_t capacity_records, uint32_t capacity_vertices, int32_t* records_out,
                        int32_t* vertices_out, const ContourStatus* status, hipStream_t stream);
+
+// ---- level mesh (mesh.hip): the contours cut at the junctions into shared segments -----------------------
+
+constexpr int kMeshSegmentWords = 8;   // vsg_render_mesh_segment as int32 words
+constexpr int kMeshLoopWords = 4;      // vsg_render_mesh_loop
+
+enum MeshFlag {
+  MESH_FLAG_RANGE = 1,   // a crack, a contour, a half, a segment or a vertex was out of range
+};
+
+// Written by the mesh kernels; read by the host after the split and at the end of a call.
+struct MeshStatus {
+  uint32_t junctions;   // corners with three or four sides
+  uint32_t segments;    // owner halves
+  uint32_t refs;        // halves
+  uint32_t vertices;
+  uint32_t closed, shared, longest;
+  uint32_t flags;
+};
+
+// What the contour stages of a call left on the device.  n cracks; `contours` contours in list order.
+struct MeshInput {
+  const int32_t* plane;
+  int width, height;
+  const uint8_t* mask;
+  const uint32_t* offset;
+  uint32_t n;
+  const uint32_t* key;
+  const uint32_t* succ;
+  const uint32_t* leader;
+  const uint32_t* place;
+  const uint2* ranked;
+  uint32_t contours;
+  const uint32_t* count;
+  const int32_t* records;
+};
+
+// Per crack (n entries each): sides, the two doubling states, half, head_of and behind it last_of (2 n),
+// seg_of, skeys.  Per contour: hasj, nrefs, first_ref.  heads: set by MeshSplit, one of the two states.
+struct MeshCrackSpace {
+  uint8_t* sides;
+  uint2* state_a;
+  uint2* state_b;
+  const uint2* heads;
+  uint32_t* half;
+  uint32_t* head_of;
+  uint32_t* seg_of;
+  unsigned long long* skeys;
+  uint32_t* hasj;
+  uint32_t* nrefs;
+  uint32_t* first_ref;
+};
+
+// Per segment: the sorted keys, scount, sfirst, the records.  vertex_slots vertices and their segments; the
+// loops (one per contour) and the refs (one per half).
+struct MeshSegmentSpace {
+  unsigned long long* skeys_sorted;
+  uint32_t* scount;
+  uint32_t* sfirst;
+  int32_t* segments;
+  uint32_t vertex_slots;
+  int32_t* vertices;
+  uint32_t* vseg;
+  int32_t* loops;
+  int32_t* refs;
+};
+
+// Work space of the sort of `items` keys and of a scan over as many.
+size_t MeshTempBytes(int64_t items, int end_bit);
+// Junction bits, the third doubling (rounds / 2 launches), the halves of every crack, head and last crack of
+// every half, the unsorted owner keys; status->junctions, ->segments, ->refs.  ckeys_sorted: the contours'.
+// 7 + rounds / 2 launches, the scan counted as one.
+hipError_t MeshSplit(void* temp, size_t temp_bytes, const MeshInput& in, const unsigned long long* ckeys_sorted,
+                     int rounds, MeshCrackSpace* w, MeshStatus* status, hipStream_t stream);
+// The segments' sort, their vertices, records, loops, refs and lengths; status->vertices, ->closed, ->shared,
+// ->longest.  n_segments, n_halves: as the host read them after MeshSplit.  11 launches, the sort and the
+// scan counted as one each.
+hipError_t MeshTables(void* temp, size_t temp_bytes, const MeshInput& in, const MeshCrackSpace& w,
+                      const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_halves, int end_bit,
+                      MeshStatus* status, hipStream_t stream);
+// Copies the four lists, or nothing when the vertices do not fit or a flag is up (the other three lengths
+// are the host's to check).
+void LaunchMeshCopy(const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_loops, uint32_t n_refs,
+                    uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
+                    int32_t* refs_out, const MeshStatus* status, hipStream_t stream);
 
 // ---- boundary distance (distance.hip): the squared distance to an edge set, the boundary benchmark ------
 

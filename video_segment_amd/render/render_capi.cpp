@@ -43,6 +43,7 @@ enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_ST
 enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
 enum ContourStage { CNT_CLASSIFY = 0, CNT_TRACE, CNT_TABLE, CNT_STAGES };
+enum MeshStage { MSH_SPLIT = 0, MSH_TABLE, MSH_STAGES };
 // DST_PLANE: the upload of a host label plane
 enum DistStage { DST_PLANE = 0, DST_CLASSIFY, DST_COLUMNS, DST_ROWS, DST_MATCH, DST_STAGES };
 
@@ -343,7 +344,7 @@ struct vsg_render {
   int device = 0, W = 0, H = 0, pitch = 0;
   hipStream_t stream = nullptr;
   // clear, fill, compose; the vector path's walk, sort, pairs; the level stages; the component stages
-  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock, tclock, dclock;
+  StageClock clock, vclock, lclock, cclock, bclock, aclock, oclock, pclock, kclock, tclock, dclock, mclock;
   // SegmentationRenderUnit's state
   bool level_resolved = false;
   int level = 0;
@@ -396,6 +397,12 @@ struct vsg_render {
   // offsets); the records; the status words and the pinned block the status and host outputs come back
   // through
   Block d_cont_mask, d_cont_offset, d_cont_cracks, d_cont_slots, d_cont_records, d_cont_status, h_cont;
+  // level mesh: what there is per crack and per contour (the third doubling's two states, the unsorted owner
+  // keys, half, head and last crack of a half, a half's segment, the contours' junction marks, ref counts and
+  // offsets, the cracks' sides); what there is per segment, vertex, loop and ref (sorted keys, vertex counts
+  // and offsets, the four lists, the vertices' segments); the status words and the pinned block the status
+  // and host outputs come back through
+  Block d_mesh_cracks, d_mesh_lists, d_mesh_status, h_mesh;
   // boundary distance: the edge set's words; the columns' squared distances; D of a host output or of the
   // other plane's edge set; the three histograms; the records of a host output; the status words and the
   // pinned block they come back through
@@ -412,6 +419,7 @@ struct vsg_render {
   vsg_render_color_stats kstats;
   vsg_render_contour_stats tstats;
   vsg_render_distance_stats dstats;
+  vsg_render_mesh_stats mstats;
 
   ~vsg_render() {
     if (!stream) return;
@@ -1014,6 +1022,9 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->dclock.Create(DST_STAGES + 1);
     h->h_dist.pinned = true;
     std::memset(&h->dstats, 0, sizeof(h->dstats));
+    h->mclock.Create(MSH_STAGES + 1);
+    h->h_mesh.pinned = true;
+    std::memset(&h->mstats, 0, sizeof(h->mstats));
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });
@@ -2521,11 +2532,25 @@ int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s) {
   });
 }
 
-int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
-                              vsg_render_level_contour* contours, size_t capacity_contours, size_t* num_contours,
-                              int32_t* vertices, size_t capacity_vertices, size_t* num_vertices, int mem_out) {
-  return Guard([&] {
+}  // extern "C"
+
+namespace {
+
+// What a vsg_render_level_contours call left on the device for vsg_render_level_mesh; in.n == 0: no crack.
+struct ContourRun {
+  vsg_render_impl::MeshInput in;
+  const unsigned long long* ckeys_sorted;
+  uint32_t max_group;
+  int rounds;
+};
+
+// vsg_render_level_contours; run: null, or what the mesh call goes on with.
+void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                   vsg_render_level_contour* contours, size_t capacity_contours, size_t* num_contours,
+                   int32_t* vertices, size_t capacity_vertices, size_t* num_vertices, int mem_out, ContourRun* run) {
+  {
     using namespace vsg_render_impl;
+    if (run) std::memset(run, 0, sizeof(*run));
     static_assert(sizeof(vsg_render_level_contour) == kLevelContourWords * sizeof(int32_t), "moved as int32 words");
     static_assert(sizeof(vsg_render_contour_stats) == 64, "documented size");
     if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
@@ -2701,6 +2726,26 @@ int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len,
     ts.vertices = (int64_t)n_vertices;
     ts.holes = seen[1].holes;
     ts.largest_contour_cracks = seen[1].largest;
+    if (run) {
+      MeshInput& in = run->in;
+      in.plane = plane;
+      in.width = W;
+      in.height = H;
+      in.mask = mask;
+      in.offset = offset;
+      in.n = n;
+      in.key = key;
+      in.succ = succ;
+      in.leader = leader;
+      in.place = place;
+      in.ranked = ranked;
+      in.contours = (uint32_t)n_contours;
+      in.count = count;
+      in.records = d_records;
+      run->ckeys_sorted = ckeys_sorted;
+      run->max_group = max_group;
+      run->rounds = rounds;
+    }
     if (count_only) return;
     if (n_contours > capacity_contours || n_vertices > capacity_vertices) {
       Throw(VSG_ERR_INVALID, "the level has " + std::to_string(n_contours) + " contours and " +
@@ -2720,6 +2765,19 @@ int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len,
       std::memcpy(contours, stage, cb);
       std::memcpy(vertices, stage + cb, vb);
     }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                              vsg_render_level_contour* contours, size_t capacity_contours, size_t* num_contours,
+                              int32_t* vertices, size_t capacity_vertices, size_t* num_vertices, int mem_out) {
+  return Guard([&] {
+    LevelContours(h, seg, seg_len, level, connectedness, contours, capacity_contours, num_contours, vertices,
+                  capacity_vertices, num_vertices, mem_out, nullptr);
   });
 }
 
@@ -2727,6 +2785,198 @@ int vsg_render_last_contour_stats(vsg_render* h, vsg_render_contour_stats* s) {
   return Guard([&] {
     if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
     *s = h->tstats;
+  });
+}
+
+int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments,
+                          int32_t* vertices, size_t capacity_vertices, size_t* num_vertices,
+                          vsg_render_mesh_loop* loops, size_t capacity_loops, size_t* num_loops, int32_t* refs,
+                          size_t capacity_refs, size_t* num_refs, int mem_out) {
+  return Guard([&] {
+    using namespace vsg_render_impl;
+    static_assert(sizeof(vsg_render_mesh_segment) == kMeshSegmentWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_mesh_loop) == kMeshLoopWords * sizeof(int32_t), "moved as int32 words");
+    static_assert(sizeof(vsg_render_mesh_stats) == 104, "documented size");
+    if (connectedness != 0 && connectedness != VSG_RENDER_CONNECT_N4 && connectedness != VSG_RENDER_CONNECT_N8) {
+      Throw(VSG_ERR_INVALID, "connectedness is neither 0, VSG_RENDER_CONNECT_N4 nor VSG_RENDER_CONNECT_N8");
+    }
+    if (!h) Throw(VSG_ERR_INVALID, "handle is null");
+    if (!num_segments || !num_vertices || !num_loops || !num_refs) Throw(VSG_ERR_INVALID, "a count pointer is null");
+    CheckMem(mem_out, "mem_out");
+    *num_segments = *num_vertices = *num_loops = *num_refs = 0;
+    const bool count_only = !segments && !vertices && !loops && !refs && capacity_segments == 0 &&
+                            capacity_vertices == 0 && capacity_loops == 0 && capacity_refs == 0;
+    vsg_render_mesh_stats& ms = h->mstats;
+    std::memset(&ms, 0, sizeof(ms));
+
+    // ---- the contour stages, as a count-only call ----
+    ContourRun run;
+    size_t n_contours = 0, n_contour_vertices = 0;
+    struct ContourPart {
+      vsg_render* h;
+      ~ContourPart() {
+        const vsg_render_contour_stats& ts = h->tstats;
+        vsg_render_mesh_stats& ms = h->mstats;
+        ms.cracks = ts.cracks;
+        ms.plane_us = ts.plane_us;
+        ms.classify_us = ts.classify_us;
+        ms.trace_us = ts.trace_us + ts.table_us;
+        ms.rounds = ts.rounds;
+        ms.launches = ts.launches;
+      }
+    };
+    {
+      ContourPart part{h};
+      LevelContours(h, seg, seg_len, level, connectedness, nullptr, 0, &n_contours, nullptr, 0, &n_contour_vertices,
+                    VSG_MEM_HOST, &run);
+    }
+    const uint32_t n = run.in.n;
+    if (n == 0) return;   // no covered pixel: all four lists are empty
+    DeviceGuard guard(h->device);
+    const uint32_t C = run.in.contours;
+    int group_bits = 1;
+    while (group_bits < 32 && (run.max_group >> group_bits)) ++group_bits;
+    const int end_bit = 32 + group_bits;
+
+    // ---- split: junctions, the third doubling, halves, owners ----
+    // sized for every crack and for what is scanned here: the library's need is not promised to grow with the
+    // number of items
+    size_t temp_bytes = std::max<size_t>(std::max(MeshTempBytes(n, end_bit), MeshTempBytes(C, end_bit)), 16);
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    h->d_mesh_status.Reserve(sizeof(MeshStatus), &h->allocations);
+    h->h_mesh.Reserve(2 * sizeof(MeshStatus), &h->allocations);
+    h->d_mesh_cracks.Reserve((size_t)n * 40 + (size_t)C * 12 + n, &h->allocations);
+    MeshStatus* status = h->d_mesh_status.As<MeshStatus>();
+    MeshStatus* seen = h->h_mesh.As<MeshStatus>();   // [0] after the split, [1] at the end
+    std::memset(seen, 0, 2 * sizeof(MeshStatus));
+    MeshCrackSpace w;
+    w.state_a = h->d_mesh_cracks.As<uint2>();
+    w.state_b = w.state_a + n;
+    w.skeys = reinterpret_cast<unsigned long long*>(w.state_b + n);
+    w.half = reinterpret_cast<uint32_t*>(w.skeys + n);
+    w.head_of = w.half + n;            // and last_of behind it
+    w.seg_of = w.head_of + 2 * (size_t)n;
+    w.hasj = w.seg_of + n;
+    w.nrefs = w.hasj + C;
+    w.first_ref = w.nrefs + C;
+    w.sides = reinterpret_cast<uint8_t*>(w.first_ref + C);
+    w.heads = nullptr;
+    int launches = 0;
+    auto finish = [&] {
+      ms.launches += launches;
+      h->stats.launches += launches;
+      h->stats.device_allocations = h->allocations;
+    };
+    VSG_HIP(hipMemsetAsync(status, 0, sizeof(MeshStatus), h->stream));
+    h->mclock.Begin(h->stream);
+    VSG_HIP(MeshSplit(h->d_sort_temp.p, temp_bytes, run.in, run.ckeys_sorted, run.rounds, &w, status, h->stream));
+    h->mclock.Mark(MSH_SPLIT);
+    VSG_HIP(hipMemcpyAsync(&seen[0], status, sizeof(MeshStatus), hipMemcpyDeviceToHost, h->stream));
+    // the clear, MeshSplit's 7 and a launch for two rounds, the status
+    launches += 9 + run.rounds / 2;
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    ms.rounds += run.rounds;
+    ms.junctions = seen[0].junctions;
+    const uint32_t S = seen[0].segments, R = seen[0].refs;
+    if ((seen[0].flags & MESH_FLAG_RANGE) || S == 0 || S > n || R < C || R > n || S > R) {
+      finish();
+      Throw(VSG_ERR_INTERNAL, "a crack, a contour or a half is out of range");
+    }
+
+    // ---- tables: the segments' order, vertices, records, loops, refs, lengths ----
+    if ((uint64_t)n + S > 0xffffffffull) {
+      finish();
+      Throw(VSG_ERR_INVALID, "the level has more than 2^32 - 1 cracks and segments");
+    }
+    const uint32_t slots = n + S;      // a vertex per crack of an owner half and an end corner per segment
+    temp_bytes = std::max(temp_bytes, MeshTempBytes(S, end_bit));
+    h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
+    const size_t seg_words = (size_t)S * kMeshSegmentWords, loop_words = (size_t)C * kMeshLoopWords;
+    h->d_mesh_lists.Reserve((size_t)S * 16 + (seg_words + (size_t)slots * 3 + loop_words + R) * 4, &h->allocations);
+    MeshSegmentSpace t;
+    t.skeys_sorted = h->d_mesh_lists.As<unsigned long long>();
+    t.scount = reinterpret_cast<uint32_t*>(t.skeys_sorted + S);
+    t.sfirst = t.scount + S;
+    t.segments = reinterpret_cast<int32_t*>(t.sfirst + S);
+    t.vertex_slots = slots;
+    t.vertices = t.segments + seg_words;
+    t.vseg = reinterpret_cast<uint32_t*>(t.vertices + (size_t)slots * 2);
+    t.loops = reinterpret_cast<int32_t*>(t.vseg + slots);
+    t.refs = t.loops + loop_words;
+    VSG_HIP(MeshTables(h->d_sort_temp.p, temp_bytes, run.in, w, t, S, R, end_bit, status, h->stream));
+    launches += 11;
+    const bool fits = S <= capacity_segments && C <= capacity_loops && R <= capacity_refs;
+    const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && segments && vertices && loops && refs;
+    if (to_device) {
+      // the number of vertices is on the device: the copy decides there whether they fit.  Counted whether or
+      // not the other three lists fit
+      if (fits) {
+        LaunchMeshCopy(t, S, C, R, (uint32_t)std::min<size_t>(capacity_vertices, slots),
+                       reinterpret_cast<int32_t*>(segments), vertices, reinterpret_cast<int32_t*>(loops), refs, status,
+                       h->stream);
+        VSG_HIP(hipGetLastError());
+      }
+      ++launches;
+    }
+    h->mclock.Mark(MSH_TABLE);
+    VSG_HIP(hipMemcpyAsync(&seen[1], status, sizeof(MeshStatus), hipMemcpyDeviceToHost, h->stream));
+    ++launches;
+    if (!count_only && mem_out == VSG_MEM_HOST) launches += 4;   // counted whether or not the lists fit
+    VSG_HIP(hipStreamSynchronize(h->stream));
+    {
+      float us[MSH_STAGES];
+      h->mclock.Read(us, MSH_STAGES);
+      ms.split_us = us[MSH_SPLIT];
+      ms.table_us = us[MSH_TABLE];
+    }
+    finish();
+    const size_t V = seen[1].vertices;
+    if ((seen[1].flags & MESH_FLAG_RANGE) || V > slots || V < 2ull * S) {
+      Throw(VSG_ERR_INTERNAL, "a segment, a vertex or a ref is out of range");
+    }
+    *num_segments = S;
+    *num_vertices = V;
+    *num_loops = C;
+    *num_refs = R;
+    ms.segments = S;
+    ms.closed_segments = seen[1].closed;
+    ms.shared_segments = seen[1].shared;
+    ms.vertices = (int64_t)V;
+    ms.loops = C;
+    ms.refs = R;
+    ms.longest_segment_cracks = seen[1].longest;
+    if (count_only) return;
+    if (!fits || V > capacity_vertices) {
+      Throw(VSG_ERR_INVALID, "the level has " + std::to_string(S) + " segments, " + std::to_string(V) + " vertices, " +
+                                 std::to_string(C) + " loops and " + std::to_string(R) + " refs, the capacities are " +
+                                 std::to_string(capacity_segments) + ", " + std::to_string(capacity_vertices) + ", " +
+                                 std::to_string(capacity_loops) + " and " + std::to_string(capacity_refs));
+    }
+    if (!segments || !vertices || !loops || !refs) Throw(VSG_ERR_INVALID, "an output is null");
+    if (mem_out == VSG_MEM_HOST) {
+      // through the pinned block, now that the lengths are known
+      const size_t sb = seg_words * 4, vb = V * 8, lb = loop_words * 4, rb = (size_t)R * 4;
+      h->h_mesh.Reserve(2 * sizeof(MeshStatus) + sb + vb + lb + rb, &h->allocations);
+      h->stats.device_allocations = h->allocations;
+      char* stage = reinterpret_cast<char*>(h->h_mesh.As<MeshStatus>() + 2);
+      VSG_HIP(hipMemcpyAsync(stage, t.segments, sb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(stage + sb, t.vertices, vb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(stage + sb + vb, t.loops, lb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipMemcpyAsync(stage + sb + vb + lb, t.refs, rb, hipMemcpyDeviceToHost, h->stream));
+      VSG_HIP(hipStreamSynchronize(h->stream));
+      std::memcpy(segments, stage, sb);
+      std::memcpy(vertices, stage + sb, vb);
+      std::memcpy(loops, stage + sb + vb, lb);
+      std::memcpy(refs, stage + sb + vb + lb, rb);
+    }
+  });
+}
+
+int vsg_render_last_mesh_stats(vsg_render* h, vsg_render_mesh_stats* s) {
+  return Guard([&] {
+    if (!h || !s) Throw(VSG_ERR_INVALID, "null argument");
+    *s = h->mstats;
   });
 }
 
