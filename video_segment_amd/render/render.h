@@ -1,6 +1,6 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
 // boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip, distance.hip),
-// called by render_capi.cpp.
+// called by the parts of render_capi.cpp (render_handle.h and the capi_*.inc files).
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
 
