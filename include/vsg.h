@@ -172,6 +172,13 @@ typedef struct vsg_spine_paths {
   int64_t sorts_library;             /* ... by the library's                                          */
 } vsg_spine_paths;
 
+/* What the chunk boundary of a stream did beside the merge (the last call that segmented a chunk).  Host
+ * counts, incremented where the host already branches: no launch, copy or wait of their own.  A struct
+ * beside vsg_spine_paths so that the others keep their size.  DESIGN 4.23. */
+typedef struct vsg_boundary_paths {
+  int64_t halo_planes_in_pool;   /* id planes of the overlap frames rendered inside the encode pool      */
+} vsg_boundary_paths;
+
 /* Device memory of the library, per device.  A closed handle leaves its blocks in a process-wide
  * cache and the next handle adopts them (no hipMalloc / hipFree after the first window of a caller
  * that creates a graph per window, dense_seg_graph_interface.h:58-98); the cached, unused bytes are
@@ -246,6 +253,7 @@ int vsg_stream_last_timings(const vsg_stream* s, vsg_timings* t);
 int vsg_stream_last_diagnostics(const vsg_stream* s, vsg_diagnostics* d);
 int vsg_stream_last_merge_paths(const vsg_stream* s, vsg_merge_paths* out);
 int vsg_stream_last_spine_paths(const vsg_stream* s, vsg_spine_paths* out);
+int vsg_stream_last_boundary_paths(const vsg_stream* s, vsg_boundary_paths* out);
 /* Parity hook: smoothed feature planes of the most recently added frame, W*H*3 f32 BGR
  * interleaved, host memory (PreprocessFeatures output, cpp:164-198). */
 int vsg_stream_last_smoothed(vsg_stream* s, float* out);

@@ -110,6 +110,16 @@ class VsgSpinePaths(C.Structure):
         return {k: (list(getattr(self, k)) if issubclass(t, C.Array) else getattr(self, k)) for k, t in self._fields_}
 
 
+class VsgBoundaryPaths(C.Structure):
+    """vsg_boundary_paths (include/vsg.h), field for field."""
+    _fields_ = [
+        ("halo_planes_in_pool", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class VsgMemoryStats(C.Structure):
     _fields_ = [
         ("bytes_in_use", C.c_int64), ("bytes_in_use_peak", C.c_int64), ("bytes_cached", C.c_int64),
@@ -143,6 +153,7 @@ EXPORTED_SYMBOLS = [
     "vsg_stream_result_bytes", "vsg_stream_result_id_image", "vsg_stream_last_merge_stats",
     "vsg_stream_keep_node_states", "vsg_stream_last_node_states",
     "vsg_stream_last_timings", "vsg_stream_last_diagnostics", "vsg_stream_last_merge_paths", "vsg_stream_last_spine_paths",
+    "vsg_stream_last_boundary_paths",
     "vsg_stream_last_smoothed", "vsg_stream_export_halo",
     "vsg_stream_import_halo", "vsg_stream_expect_halo", "vsg_stream_restart",
     "vsg_chain_create", "vsg_chain_destroy", "vsg_chain_info", "vsg_chain_send_halo",
@@ -211,6 +222,7 @@ def lib():
     L.vsg_stream_last_diagnostics.argtypes = [vp, C.POINTER(VsgDiagnostics)]
     L.vsg_stream_last_merge_paths.argtypes = [vp, C.POINTER(VsgMergePaths)]
     L.vsg_stream_last_spine_paths.argtypes = [vp, C.POINTER(VsgSpinePaths)]
+    L.vsg_stream_last_boundary_paths.argtypes = [vp, C.POINTER(VsgBoundaryPaths)]
     L.vsg_stream_last_smoothed.argtypes = [vp, vp]
     L.vsg_stream_export_halo.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), vp]
     L.vsg_stream_import_halo.argtypes = [vp, vp, vp, C.c_int, vp]

@@ -419,6 +419,13 @@ int vsg_stream_last_spine_paths(const vsg_stream* s, vsg_spine_paths* out) {
   });
 }
 
+int vsg_stream_last_boundary_paths(const vsg_stream* s, vsg_boundary_paths* out) {
+  return Guard([&] {
+    VSG_REQUIRE(s && out, VSG_ERR_INVALID, "null argument");
+    *out = s->impl->last_boundary_paths();
+  });
+}
+
 int vsg_stream_last_smoothed(vsg_stream* s, float* out) {
   return Guard([&] {
     VSG_REQUIRE(s && out, VSG_ERR_INVALID, "null argument");

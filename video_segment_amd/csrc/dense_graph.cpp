@@ -1418,11 +1418,9 @@ void DenseGraphHip::ObtainResults(const std::vector<const float*>* dev_flows, bo
     LaunchEnforceN4(label_img_.get(), W_, H_, small_i32_a_.get(), nf, row_counts_.get(), adjust_.get(), stream_);
   }
 
-  // 3. run-length intervals in (slice, y, x) order.
-  for (int i = 0; i < nf; ++i) {
-    LaunchRowRunCounts(label_img_.get(), W_, H_, frames[i], row_counts_.get() + (size_t)i * H_,
-                       stream_);
-  }
+  // 3. run-length intervals in (slice, y, x) order: all rasterised slices in one launch (the slice
+  //    list is on the device since step 2; it stays there until fetch_states reuses the buffer).
+  LaunchRowRunCounts(label_img_.get(), W_, H_, small_i32_a_.get(), nf, row_counts_.get(), stream_);
   VSG_HIP(hipMemsetAsync(row_counts_.get() + rows, 0, sizeof(int32_t), stream_));
   ExclusiveSum(ScanScratch{scan_sums_.get()}, row_counts_.get(), row_offsets_.get(), rows + 1, stream_);
   int num_iv = 0;
@@ -1433,10 +1431,7 @@ void DenseGraphHip::ObtainResults(const std::vector<const float*>* dev_flows, bo
   iv_lx_.ensure((size_t)num_iv);
   iv_rx_.ensure((size_t)num_iv);
   IntervalArrays iva{iv_label_.get(), iv_ty_.get(), iv_lx_.get(), iv_rx_.get()};
-  for (int i = 0; i < nf; ++i) {
-    LaunchWriteIntervals(label_img_.get(), W_, H_, frames[i],
-                         row_offsets_.get() + (size_t)i * H_, iva, stream_);
-  }
+  LaunchWriteIntervals(label_img_.get(), W_, H_, small_i32_a_.get(), nf, row_offsets_.get(), iva, stream_);
   // (pinned host memory, kept between chunks: the 14 MB of a many-region chunk took 1.5 ms into
   // freshly allocated pageable vectors)
   iv_host_.ensure(4 * (size_t)std::max(num_iv, 1));

@@ -53,6 +53,8 @@ class DenseGraphHip {
   int max_frames() const { return max_frames_; }
   int num_frames() const { return num_frames_; }
   hipStream_t stream() const { return stream_; }
+  // Idle outside Segment(): the stream handle runs the input side of its frames here.
+  hipStream_t aux_stream() const { return aux_stream_; }
 
   // Starts a new (empty) graph reusing all device buffers.  max_frames may shrink/grow up to the
   // capacity given at construction.

@@ -425,18 +425,19 @@ void LaunchFlatten(NodeArrays nodes, size_t n, int32_t* label_uf, hipStream_t s)
 void LaunchEnforceN4(int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
                      int32_t* row_flags /* [num_frames * H] scratch, zeroed */, int32_t* adjust /* [N] */,
                      hipStream_t s);
-// Run-length encoding of one slice: counts per row, then intervals.
-void LaunchRowRunCounts(const int32_t* label_img, int W, int H, int frame, int32_t* row_counts,
-                        hipStream_t s);
+// Run-length encoding of the listed slices in one launch each: counts per row in (slice, y) order,
+// then intervals.
+void LaunchRowRunCounts(const int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
+                        int32_t* row_counts /* [num_frames * H] */, hipStream_t s);
 struct IntervalArrays {
   int32_t* label;     // region representative key
   uint32_t* ty;       // frame << 16 | y
   int32_t* lx;        // left_x
   int32_t* rx;        // right_x
 };
-void LaunchWriteIntervals(const int32_t* label_img, int W, int H, int frame,
-                          const int32_t* row_offsets /* exclusive, global */, IntervalArrays out,
-                          hipStream_t s);
+void LaunchWriteIntervals(const int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
+                          const int32_t* row_offsets /* exclusive, global, [num_frames * H] */,
+                          IntervalArrays out, hipStream_t s);
 // Relabels nodes covered by the given intervals (tube splitting).
 void LaunchRelabelIntervals(const uint32_t* ty, const int32_t* lx, const int32_t* rx,
                             const int32_t* new_label, int n, int W, int H, int32_t* label_uf,

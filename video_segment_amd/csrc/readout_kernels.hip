@@ -164,12 +164,14 @@ void LaunchEnforceN4(int32_t* label_img, int W, int H, const int32_t* frames_dev
   VSG_HIP(hipGetLastError());
 }
 
-// K8a: number of runs in every row of a slice (one wavefront per row).
-__global__ __launch_bounds__(64) void k_row_run_counts(const int32_t* __restrict__ img, int W, int H,
+// K8a: number of runs in every row of the listed slices (one wavefront per row; blockIdx.y is the
+// position of the slice in the list, the counts are in (slice, y) order).
+__global__ __launch_bounds__(64) void k_row_run_counts(const int32_t* __restrict__ label_img, int W, int H,
+                                                        const int32_t* __restrict__ frames,
                                                         int32_t* __restrict__ row_counts) {
   const int y = blockIdx.x;
   const int lane = threadIdx.x;
-  const int32_t* row = img + (size_t)y * W;
+  const int32_t* row = label_img + ((size_t)frames[blockIdx.y] * H + y) * W;
   int count = 0;
   for (int x0 = 0; x0 < W; x0 += 64) {
     const int x = x0 + lane;
@@ -177,26 +179,28 @@ __global__ __launch_bounds__(64) void k_row_run_counts(const int32_t* __restrict
     if (x < W) start = (x == 0) || (row[x] != row[x - 1]);
     count += __popcll(__ballot(start));
   }
-  if (lane == 0) row_counts[y] = count;
+  if (lane == 0) row_counts[(size_t)blockIdx.y * H + y] = count;
 }
 
-void LaunchRowRunCounts(const int32_t* label_img, int W, int H, int frame, int32_t* row_counts,
-                        hipStream_t s) {
-  hipLaunchKernelGGL(k_row_run_counts, dim3(H), dim3(64), 0, s, label_img + (size_t)frame * W * H,
-                     W, H, row_counts);
+void LaunchRowRunCounts(const int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
+                        int32_t* row_counts, hipStream_t s) {
+  if (num_frames <= 0) return;
+  hipLaunchKernelGGL(k_row_run_counts, dim3(H, num_frames), dim3(64), 0, s, label_img, W, H, frames_dev,
+                     row_counts);
   VSG_HIP(hipGetLastError());
 }
 
 // K8b: write the intervals of every row at its global offset (row_offsets = exclusive scan of
 // the run counts of all rows of all rasterised slices, in (slice, y) order).
-__global__ __launch_bounds__(64) void k_write_intervals(const int32_t* __restrict__ img, int W, int H,
-                                                         int frame,
+__global__ __launch_bounds__(64) void k_write_intervals(const int32_t* __restrict__ label_img, int W, int H,
+                                                         const int32_t* __restrict__ frames,
                                                          const int32_t* __restrict__ row_offsets,
                                                          IntervalArrays out) {
   const int y = blockIdx.x;
   const int lane = threadIdx.x;
-  const int32_t* row = img + (size_t)y * W;
-  int base = row_offsets[y];
+  const int frame = frames[blockIdx.y];
+  const int32_t* row = label_img + ((size_t)frame * H + y) * W;
+  int base = row_offsets[(size_t)blockIdx.y * H + y];
   for (int x0 = 0; x0 < W; x0 += 64) {
     const int x = x0 + lane;
     bool start = false;
@@ -219,10 +223,11 @@ __global__ __launch_bounds__(64) void k_write_intervals(const int32_t* __restric
   if (lane == 0) out.rx[base - 1] = W - 1;   // last run of the row
 }
 
-void LaunchWriteIntervals(const int32_t* label_img, int W, int H, int frame,
+void LaunchWriteIntervals(const int32_t* label_img, int W, int H, const int32_t* frames_dev, int num_frames,
                           const int32_t* row_offsets, IntervalArrays out, hipStream_t s) {
-  hipLaunchKernelGGL(k_write_intervals, dim3(H), dim3(64), 0, s,
-                     label_img + (size_t)frame * W * H, W, H, frame, row_offsets, out);
+  if (num_frames <= 0) return;
+  hipLaunchKernelGGL(k_write_intervals, dim3(H, num_frames), dim3(64), 0, s, label_img, W, H, frames_dev,
+                     row_offsets, out);
   VSG_HIP(hipGetLastError());
 }
 

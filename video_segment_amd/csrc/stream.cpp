@@ -128,7 +128,12 @@ DenseSegmentationHip::DenseSegmentationHip(const vsg_options& o, int W, int H)
   // The caller (capi.cpp) has bound this thread to the handle's device.
   VSG_HIP(hipStreamCreateWithFlags(&stream_, hipStreamNonBlocking));
   graph_.reset(new DenseGraphHip(W, H, options_.chunk_size + 1, options_.color_distance == 0, stream_));
-  pre_.reset(new Preprocessor(W, H, stream_));
+  // The input side of a frame (staging copy, min/max, LUT upload, filter, flow copy) runs on the
+  // graph's first side stream, which is idle outside Segment(): the host's wait for min/max then does
+  // not wait for the previous frame's edge kernels on stream_, and those run beside this frame's filter.
+  input_stream_ = graph_->aux_stream();
+  VSG_HIP(hipEventCreateWithFlags(&input_done_, hipEventDisableTiming));
+  pre_.reset(new Preprocessor(W, H, input_stream_));
   planes_ = std::make_shared<PlanePool>();
   std::memset(&last_timings_, 0, sizeof(last_timings_));
   std::memset(&accum_, 0, sizeof(accum_));
@@ -138,6 +143,8 @@ DenseSegmentationHip::~DenseSegmentationHip() {
   quiesce_.Begin();   // one device synchronisation for all the buffers released below
   if (stream_) {
     (void)hipStreamSynchronize(stream_);
+    if (input_done_) (void)hipEventDestroy(input_done_);
+    for (hipEvent_t e : edge_ev_) (void)hipEventDestroy(e);
     graph_.reset();
     pre_.reset();
     feature_buffer_.clear();
@@ -169,11 +176,19 @@ int DenseSegmentationHip::ProcessFrame(bool flush, const uint8_t* bgr, size_t st
   }
   if (bgr) {
     VSG_REQUIRE(stride >= (size_t)W_ * 3, -1, "stride smaller than a row");
+    // An error below must not return while the input stream still reads the caller's buffers.
+    struct InputDrain {
+      hipStream_t s;
+      bool armed = true;
+      ~InputDrain() {
+        if (armed) (void)hipStreamSynchronize(s);
+      }
+    } drain{input_stream_};
     const uint8_t* bgr_dev = bgr;
     if (mem == VSG_MEM_HOST) {
       staging_bgr_.ensure(stride * (size_t)H_);
       VSG_HIP(hipMemcpyAsync(staging_bgr_.get(), bgr, stride * (size_t)(H_ - 1) + (size_t)W_ * 3,
-                             hipMemcpyHostToDevice, stream_));
+                             hipMemcpyHostToDevice, input_stream_));
       bgr_dev = staging_bgr_.get();
     }
     DevPlane feat = planes_->Take(3 * wh_);
@@ -197,12 +212,22 @@ int DenseSegmentationHip::ProcessFrame(bool flush, const uint8_t* bgr, size_t st
         DevPlane fd = planes_->Take(2 * wh_);
         VSG_HIP(hipMemcpyAsync(fd->get(), flow, 2 * wh_ * sizeof(float),
                                mem == VSG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
-                               stream_));
+                               input_stream_));
         flow_dev_buffer_.push_back(fd);
       }
     }
+    // Nothing below reads a buffer of the caller's.  The edge kernels wait for the input side on the
+    // device; the host waits for it before the call returns (the caller may recycle its buffers then).
+    // What the two sides share stays ordered: staging_bgr_ and the min/max words are touched by the
+    // input stream alone, keys_tmp_ / hist_tmp_ by stream_ alone, and a plane of the pool is handed out
+    // again only after a chunk boundary, whose read-out has drained stream_.
+    VSG_HIP(hipEventRecord(input_done_, input_stream_));
+    VSG_HIP(hipStreamWaitEvent(stream_, input_done_, 0));
 
-    const double te = NowMs();
+    const bool first_after_import = pending_import_;
+    const int ev = TakeEdgeEvents();
+    try {
+    VSG_HIP(hipEventRecord(edge_ev_[(size_t)ev], stream_));
     if (pending_import_) {
       // First frame after vsg_stream_import_halo: it is the constrained overlap frame.
       feature_buffer_.push_back(nullptr);   // virtual slot
@@ -230,8 +255,16 @@ int DenseSegmentationHip::ProcessFrame(bool flush, const uint8_t* bgr, size_t st
                             false);
       }
     }
-    VSG_HIP(hipStreamSynchronize(stream_));
-    accum_.edges_ms += (float)(NowMs() - te);
+    VSG_HIP(hipEventRecord(edge_ev_[(size_t)ev + 1], stream_));
+    } catch (...) {
+      edge_ev_used_ = ev;   // the pair goes back: its end was never recorded and must not be summed
+      throw;
+    }
+    if (first_after_import) {
+      VSG_HIP(hipStreamSynchronize(stream_));   // the halo hand-over keeps its full wait
+    }
+    VSG_HIP(hipEventSynchronize(input_done_));
+    drain.armed = false;
     accum_.edge_launches += 1;
     ++input_frames_;
   }
@@ -240,6 +273,18 @@ int DenseSegmentationHip::ProcessFrame(bool flush, const uint8_t* bgr, size_t st
     return (int)results_.size();
   }
   return 0;
+}
+
+// Two timing events on stream_ around the edge kernels of one frame (edges_ms is their device time,
+// summed after FinishBuilding); the pool grows to the frames of a chunk and is then reused.
+int DenseSegmentationHip::TakeEdgeEvents() {
+  while ((size_t)edge_ev_used_ + 2 > edge_ev_.size()) {
+    hipEvent_t e = nullptr;
+    VSG_HIP(hipEventCreate(&e));
+    edge_ev_.push_back(e);
+  }
+  edge_ev_used_ += 2;
+  return edge_ev_used_ - 2;
 }
 
 // AddVirtualImageConstrained + constrained AddFrame + virtual temporal edges
@@ -268,50 +313,15 @@ void DenseSegmentationHip::ChunkBoundaryOutput(bool flush) {
     return;
   }
   VSG_REQUIRE((int)overlap_segmentations_.size() == constraint_frames_ + 1, -4, "overlap size");
-  // Render the two overlap segmentations to id images (SegmentationDescToIdImage): both at once,
-  // into pinned memory (a pageable source made the two 8 MB copies 1.5 ms per chunk).
-  if (!halo_ids_host_) {
-    halo_ids_host_ = static_cast<int32_t*>(CacheAlloc(2 * wh_ * sizeof(int32_t), kCachePinned));
-  }
-  {
-    auto render = [&](int k) {
-      int32_t* ids = halo_ids_host_ + (size_t)k * wh_;
-      std::fill(ids, ids + wh_, -1);
-      RenderIdImage(*overlap_segmentations_[k], W_, ids);
-    };
-    // (a throwing render -- VSG_REQUIRE in RenderIdImage, bad_alloc -- must neither leave a joinable
-    // thread behind nor escape from the second thread: both end in std::terminate)
-    std::exception_ptr other_error;
-    std::thread other([&] {
-      try {
-        render(1);
-      } catch (...) {
-        other_error = std::current_exception();
-      }
-    });
-    try {
-      render(0);
-    } catch (...) {
-      other.join();
-      throw;
-    }
-    other.join();
-    if (other_error) std::rethrow_exception(other_error);
-  }
-  for (int k = 0; k < 2; ++k) {
-    halo_ids_dev_[k].ensure(wh_);
-    VSG_HIP(hipMemcpyAsync(halo_ids_dev_[k].get(), halo_ids_host_ + (size_t)k * wh_, wh_ * sizeof(int32_t),
-                           hipMemcpyHostToDevice, stream_));
-  }
-  // (the next write to the pinned planes is a whole chunk -- and several stream synchronisations -- away)
-  halo_valid_ = true;
+  // (the id planes of the two overlap segmentations were rendered inside the encode pool and are on
+  // their way to the device: SegmentAndOutputChunk)
   const double tb2 = NowMs();
   StartConstrainedGraph(halo_ids_dev_[0].get(), halo_ids_dev_[1].get(), max_region_id_);
   overlap_segmentations_.clear();
   if (getenv("VSG_DEBUG_STATS")) {
     VSG_HIP(hipStreamSynchronize(stream_));
-    std::fprintf(stderr, "[vsg] boundary: segment+output %.1f ms, halo planes %.1f ms, next graph start %.1f ms\n",
-                 tb1 - tb0, tb2 - tb1, NowMs() - tb2);
+    std::fprintf(stderr, "[vsg] boundary: segment+output %.1f ms, halo planes %.1f ms (%d in the pool), next graph start %.1f ms\n",
+                 tb1 - tb0, tb2 - tb1, (int)boundary_paths_.halo_planes_in_pool, NowMs() - tb2);
   }
 }
 
@@ -323,6 +333,12 @@ void DenseSegmentationHip::SegmentAndOutputChunk(bool flush) {
   }
   // RunOverSegmentation (segmentation.cpp:272-303)
   graph_->FinishBuilding();
+  for (int k = 0; k + 1 < edge_ev_used_; k += 2) {
+    float ms = 0;
+    VSG_HIP(hipEventElapsedTime(&ms, edge_ev_[(size_t)k], edge_ev_[(size_t)k + 1]));
+    accum_.edges_ms += ms;
+  }
+  edge_ev_used_ = 0;
   if (options_.two_stage_oversegment) graph_->SegmentSpatially();   // segmentation.cpp:280-283
   graph_->Segment(MinRegionSize(), true);
   if (keep_node_states_) {
@@ -389,26 +405,72 @@ void DenseSegmentationHip::SegmentAndOutputChunk(bool flush) {
   const int num_result_frames = max_result_frame - curr_chunk_start_ + 1;
   std::vector<std::unique_ptr<SegDesc>> descs((size_t)num_result_frames);
   std::vector<std::string> wires((size_t)num_result_frames);
+  // The two overlap frames are taken right after the chunk's first: whoever has built one renders its id plane
+  // (SegmentationDescToIdImage) into the pinned halo buffer right away, beside the other frames'
+  // retrieval, and the planes go to the device as soon as the pool has joined.  (The last upload from
+  // the pinned planes is a whole chunk -- and several stream synchronisations -- back.)
+  const int first_overlap_task = last_output_frame - curr_chunk_start_;
+  const int num_halo_tasks = flush ? 0 : num_result_frames - first_overlap_task;
+  if (!flush) {
+    VSG_REQUIRE(num_halo_tasks == constraint_frames_ + 1 && num_halo_tasks == 2, -4, "overlap size");
+    if (!halo_ids_host_) {
+      halo_ids_host_ = static_cast<int32_t*>(CacheAlloc(2 * wh_ * sizeof(int32_t), kCachePinned));
+    }
+  }
+  std::atomic<int> halo_planes(0);
   {
     std::atomic<int> next(0);
+    // (a throwing task -- VSG_REQUIRE in RenderIdImage, bad_alloc -- must neither leave a joinable
+    // thread behind nor escape from a pool thread: both end in std::terminate)
+    std::mutex error_mu;
+    std::exception_ptr error;
     auto work = [&]() {
-      for (int i = next.fetch_add(1); i < num_result_frames; i = next.fetch_add(1)) {
-        const int frame_idx = curr_chunk_start_ + i;
-        std::unique_ptr<SegDesc> desc(new SegDesc());
-        Retrieve(frame_idx, frame_idx == curr_chunk_start_, desc.get());
-        desc->chunk_size = chunk_size;
-        desc->overlap_start = chunk_size;
-        desc->hierarchy_frame_idx = hierarchy_frame_idx;
-        if (frame_idx <= last_output_frame) wires[(size_t)i] = EncodeSegDesc(*desc);
-        descs[(size_t)i] = std::move(desc);
+      try {
+        for (int j = next.fetch_add(1); j < num_result_frames; j = next.fetch_add(1)) {
+          // task order: the chunk's first frame (it carries the hierarchy: the heaviest task), the
+          // overlap frames, then the other frames in order
+          const int halo = (j >= 1 && j <= num_halo_tasks) ? j - 1 : -1;
+          const int i = j == 0 ? 0 : halo >= 0 ? first_overlap_task + halo : j - num_halo_tasks;
+          const int frame_idx = curr_chunk_start_ + i;
+          std::unique_ptr<SegDesc> desc(new SegDesc());
+          Retrieve(frame_idx, frame_idx == curr_chunk_start_, desc.get());
+          desc->chunk_size = chunk_size;
+          desc->overlap_start = chunk_size;
+          desc->hierarchy_frame_idx = hierarchy_frame_idx;
+          if (halo >= 0) {
+            int32_t* ids = halo_ids_host_ + (size_t)halo * wh_;
+            std::fill(ids, ids + wh_, -1);
+            RenderIdImage(*desc, W_, ids);
+            halo_planes.fetch_add(1);
+          }
+          if (frame_idx <= last_output_frame) wires[(size_t)i] = EncodeSegDesc(*desc);
+          descs[(size_t)i] = std::move(desc);
+        }
+      } catch (...) {
+        std::lock_guard<std::mutex> lock(error_mu);
+        if (!error) error = std::current_exception();
+        next.store(num_result_frames);   // the others finish what they hold and stop
       }
     };
     const int hw = (int)std::thread::hardware_concurrency();
     const int num_threads = std::max(1, std::min({num_result_frames, hw > 0 ? hw : 1, 32}));
     std::vector<std::thread> pool;
-    for (int t = 1; t < num_threads; ++t) pool.emplace_back(work);
+    try {
+      for (int t = 1; t < num_threads; ++t) pool.emplace_back(work);
+    } catch (...) {   // no more threads: the ones that run and this one do the work
+    }
     work();
     for (std::thread& t : pool) t.join();
+    if (error) std::rethrow_exception(error);
+  }
+  boundary_paths_.halo_planes_in_pool = halo_planes.load();
+  if (!flush) {
+    for (int k = 0; k < 2; ++k) {
+      halo_ids_dev_[k].ensure(wh_);
+      VSG_HIP(hipMemcpyAsync(halo_ids_dev_[k].get(), halo_ids_host_ + (size_t)k * wh_, wh_ * sizeof(int32_t),
+                             hipMemcpyHostToDevice, stream_));
+    }
+    halo_valid_ = true;
   }
   t_h[1] = NowMs();
   for (int i = 0; i < num_result_frames; ++i) {
@@ -609,6 +671,7 @@ void DenseSegmentationHip::Restart() {
   halo_valid_ = false;
   flow_stream_seen_ = false;
   frames_fed_ = 0;
+  edge_ev_used_ = 0;
   forget_pending_ = true;   // unless the stream continues a video (ExpectHalo / ImportHalo)
   std::memset(&accum_, 0, sizeof(accum_));
 }

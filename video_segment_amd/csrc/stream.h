@@ -102,6 +102,7 @@ class DenseSegmentationHip {
   const NodeStates& last_node_states() const { return node_states_; }
   const vsg_timings& last_timings() const { return last_timings_; }
   const GraphTimings& last_graph_timings() const { return last_graph_timings_; }
+  const vsg_boundary_paths& last_boundary_paths() const { return boundary_paths_; }
   void CopyLastSmoothed(float* out_interleaved_host);
   int W() const { return W_; }
   int H() const { return H_; }
@@ -121,6 +122,7 @@ class DenseSegmentationHip {
   void StartConstrainedGraph(const int32_t* virt_ids_dev, const int32_t* cons_ids_dev,
                              int max_label);
   void Retrieve(int frame, bool output_hierarchy, SegDesc* desc) const;
+  int TakeEdgeEvents();
 
   QuiesceGuard quiesce_;   // first member: spans the release of every buffer below (device_cache.h)
   vsg_options options_;
@@ -128,6 +130,10 @@ class DenseSegmentationHip {
   size_t wh_;
   hipStream_t stream_ = nullptr;
   std::unique_ptr<DenseGraphHip> graph_;
+  hipStream_t input_stream_ = nullptr;   // graph_'s aux stream: the input side of ProcessFrame
+  hipEvent_t input_done_ = nullptr;      // after the last operation that reads a caller's buffer
+  std::vector<hipEvent_t> edge_ev_;      // pairs around each frame's edge kernels on stream_
+  int edge_ev_used_ = 0;
   std::unique_ptr<Preprocessor> pre_;
   std::shared_ptr<PlanePool> planes_;
   bool graph_open_ = false;
@@ -166,6 +172,7 @@ class DenseSegmentationHip {
   NodeStates node_states_;
   vsg_timings last_timings_;
   GraphTimings last_graph_timings_;   // the graph's own record of the last segmented chunk (diagnostics)
+  vsg_boundary_paths boundary_paths_ = {0};   // of the last segmented chunk
   vsg_timings accum_;   // preprocess / edge time accumulated while the chunk is being built
 };
 

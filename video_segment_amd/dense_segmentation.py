@@ -14,7 +14,8 @@ import ctypes as C
 import numpy as np
 
 from . import _lib
-from ._lib import VsgDiagnostics, VsgMergePaths, VsgOptions, VsgSpinePaths, VsgTimings, check, lib
+from ._lib import (VsgBoundaryPaths, VsgDiagnostics, VsgMergePaths, VsgOptions, VsgSpinePaths, VsgTimings, check,
+                   lib)
 
 
 def default_options(**kw):
@@ -164,6 +165,12 @@ class DenseSegmentation:
         ran), as a dict."""
         m = VsgMergePaths()
         check(lib().vsg_stream_last_merge_paths(self.h, C.byref(m)))
+        return m.as_dict()
+
+    def last_boundary_paths(self):
+        """vsg_stream_last_boundary_paths of the last segmented chunk (where the halo planes were rendered), as a dict."""
+        m = VsgBoundaryPaths()
+        check(lib().vsg_stream_last_boundary_paths(self.h, C.byref(m)))
         return m.as_dict()
 
     def last_spine_paths(self):
