@@ -372,6 +372,11 @@ int vsg_graph_add_virtual_frame(vsg_graph* g, const int32_t* constraint_ids, int
 /* AddTemporalEdges / AddTemporalFlowEdges / AddTemporalVirtualEdges / AddTemporalFlowVirtualEdges
  * (h:124-132): connects the last two added slices.  flow NULL = no flow. */
 int vsg_graph_add_temporal(vsg_graph* g, const float* flow, int is_virtual, int mem);
+/* vsg_graph_add_frame_features followed by vsg_graph_add_temporal as one chain of kernels (what a
+ * stream does for every frame after a chunk's first): the same two lists, bit for bit.  At least
+ * one slice has to be there already; is_virtual as for vsg_graph_add_temporal. */
+int vsg_graph_add_frame_features_temporal(vsg_graph* g, const float* feat, const int32_t* constraint_ids,
+                                          const float* flow, int is_virtual, int mem);
 /* FinishBuildingGraph (h:135): waits for the asynchronous build kernels. */
 int vsg_graph_finish_building(vsg_graph* g);
 /* SegmentGraphSpatially(), h:138: merges along the spatial edges only (min_region_size 0, no
@@ -416,6 +421,12 @@ int vsg_graph_get_intervals(vsg_graph* g, int frame, const vsg_interval** interv
 int vsg_graph_smoothed(vsg_graph* g, int t, float* out /* W*H*3 interleaved */);
 int vsg_graph_spatial_buckets(vsg_graph* g, int t, uint16_t* out /* 4*W*H, plane k */);
 int vsg_graph_temporal_buckets(vsg_graph* g, int t, uint16_t* out /* 9*W*H */, int32_t* prev_idx);
+/* An edge list exactly as the device holds it.  list = 2 t: the spatial list of slice t (slot =
+ * pix * 4 + k), 2 t - 1: the temporal list between slices t - 1 and t (slot = pix * 9 + k).
+ * offsets_out[2050]: start of every bucket (0..2047, 2048 = virtual edges, 2049 = end of the list);
+ * slots_out (room for 4 or 9 W*H): the first offsets_out[2049] entries are written, slot ids in slot
+ * order inside every bucket.  Read-only. */
+int vsg_graph_list_slots(vsg_graph* g, int list, uint32_t* slots_out, int32_t* offsets_out);
 /* Union-find representative (node id) of every node after segment(); n = W*H*frames. */
 int vsg_graph_node_roots(vsg_graph* g, int32_t* out);
 /* ... and the state of that representative, as of the last segment / segment_spatially call (see

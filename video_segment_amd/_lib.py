@@ -162,6 +162,7 @@ EXPORTED_SYMBOLS = [
     "vsg_regionseg_result_bytes", "vsg_bgr_to_lab",
     "vsg_graph_create", "vsg_graph_destroy", "vsg_graph_add_frame_bgr",
     "vsg_graph_add_frame_features", "vsg_graph_add_virtual_frame", "vsg_graph_add_temporal",
+    "vsg_graph_add_frame_features_temporal", "vsg_graph_list_slots",
     "vsg_graph_finish_building", "vsg_graph_segment_spatially", "vsg_graph_segment", "vsg_graph_obtain_results",
     "vsg_graph_num_frames", "vsg_graph_num_regions", "vsg_graph_num_neighbor_links",
     "vsg_graph_region_sizes", "vsg_graph_index_image", "vsg_graph_get_regions",
@@ -249,6 +250,8 @@ def lib():
     L.vsg_graph_add_frame_features.argtypes = [vp, vp, vp, C.c_int]
     L.vsg_graph_add_virtual_frame.argtypes = [vp, vp, C.c_int]
     L.vsg_graph_add_temporal.argtypes = [vp, vp, C.c_int, C.c_int]
+    L.vsg_graph_add_frame_features_temporal.argtypes = [vp, vp, vp, vp, C.c_int, C.c_int]
+    L.vsg_graph_list_slots.argtypes = [vp, C.c_int, vp, vp]
     L.vsg_graph_finish_building.argtypes = [vp]
     L.vsg_graph_segment_spatially.argtypes = [vp]
     L.vsg_graph_segment.argtypes = [vp, C.c_int, C.c_int]

@@ -977,6 +977,47 @@ int vsg_graph_add_temporal(vsg_graph* g, const float* flow, int is_virtual, int 
   });
 }
 
+int vsg_graph_add_frame_features_temporal(vsg_graph* g, const float* feat_in, const int32_t* constraint_ids,
+                                          const float* flow, int is_virtual, int mem) {
+  return Guard([&] {
+    VSG_REQUIRE(g && feat_in, VSG_ERR_INVALID, "null argument");
+    DeviceGuard dg(g->device);
+    const int nf = g->g->num_frames();
+    VSG_REQUIRE(nf >= 1, VSG_ERR_STATE, "temporal edges need two slices");
+    const float* prev = g->feats[nf - 1] ? g->feats[nf - 1]->get() : nullptr;
+    VSG_REQUIRE(is_virtual || prev, VSG_ERR_STATE, "real temporal edges need two real slices");
+    const float* src = feat_in;
+    if (mem == VSG_MEM_HOST) {
+      g->staging_f32.ensure(3 * g->wh);
+      VSG_HIP(hipMemcpyAsync(g->staging_f32.get(), feat_in, 3 * g->wh * sizeof(float),
+                             hipMemcpyHostToDevice, g->stream));
+      src = g->staging_f32.get();
+    }
+    auto feat = std::make_shared<vsg::DevBuf<float>>(3 * g->wh);
+    vsg::LaunchInterleavedToPlanar(src, g->wh, feat->get(), g->stream);
+    std::shared_ptr<vsg::DevBuf<float>> fd;
+    if (flow) {
+      fd = std::make_shared<vsg::DevBuf<float>>(2 * g->wh);
+      VSG_HIP(hipMemcpyAsync(fd->get(), flow, 2 * g->wh * sizeof(float),
+                             mem == VSG_MEM_HOST ? hipMemcpyHostToDevice : hipMemcpyDeviceToDevice,
+                             g->stream));
+    }
+    const int32_t* ids = StageIds(g, constraint_ids, mem);
+    g->g->AddFrameAndTemporal(feat->get(), ids, prev, fd ? fd->get() : nullptr, is_virtual != 0);
+    VSG_HIP(hipStreamSynchronize(g->stream));
+    g->feats.push_back(feat);
+    g->flows_dev.push_back(fd);
+  });
+}
+
+int vsg_graph_list_slots(vsg_graph* g, int list, uint32_t* slots_out, int32_t* offsets_out) {
+  return Guard([&] {
+    VSG_REQUIRE(g && slots_out && offsets_out, VSG_ERR_INVALID, "null argument");
+    DeviceGuard dg(g->device);
+    g->g->CopyListSlots(list, slots_out, offsets_out);
+  });
+}
+
 int vsg_graph_finish_building(vsg_graph* g) {
   return Guard([&] {
     VSG_REQUIRE(g, VSG_ERR_INVALID, "null argument");

@@ -64,9 +64,12 @@ DenseGraphHip::DenseGraphHip(int W, int H, int max_frames, bool l1, hipStream_t 
   const size_t total_slots = (size_t)(4 * max_frames + 9 * (max_frames - 1)) * wh_;
   kept_all_.alloc(total_slots);
   bucket_base_dev_.alloc((size_t)(kNumBuckets + 1) * (lists_.size() + 1));
-  keys_tmp_.alloc(9 * wh_ + 8);
-  hist_tmp_.alloc(EdgeSortHistInts(wh_));
-  hist_sums_.alloc(EdgeSortSumInts(wh_) + 1);
+  for (int k = 0; k < 2; ++k) {
+    const int per_px = k == 0 ? 4 : 9;
+    keys_tmp_[k].alloc((size_t)per_px * wh_ + 8);
+    hist_tmp_[k].alloc(EdgeSortHistInts(wh_, per_px));
+    hist_chunk_[k].alloc(EdgeSortChunkInts(wh_, per_px));
+  }
   scalars_.alloc(32);
   stats_.alloc(96);
   hub_excl_.alloc(kHubListInts);
@@ -151,17 +154,19 @@ void DenseGraphHip::ForgetLearned() {
   last_density_ = 1.0;
 }
 
-void DenseGraphHip::SortList(ListBuf& lb, int per_px) {
+EdgeSortList DenseGraphHip::SortEntry(ListBuf& lb, int per_px) {
+  const int k = per_px == 4 ? 0 : 1;
   const int n = (int)(per_px * wh_);
   lb.slots.ensure((size_t)n);
   lb.offsets.ensure(kBucketSlots);
-  LaunchBucketSort(keys_tmp_.get(), wh_, per_px, hist_tmp_.get(), hist_sums_.get(),
-                   lb.offsets.get(), lb.slots.get(), stream_);
   lb.n = n;
   lb.used = true;
+  return EdgeSortList{keys_tmp_[k].get(), hist_tmp_[k].get(), hist_chunk_[k].get(), lb.offsets.get(),
+                      lb.slots.get(), per_px};
 }
 
-void DenseGraphHip::AddFrame(const float* feat, const int32_t* cons_dev) {
+// Node initialisation and the key kernel of the next slice's spatial list.
+DenseGraphHip::ListBuf& DenseGraphHip::PrepareSpatialList(const float* feat, const int32_t* cons_dev) {
   VSG_REQUIRE(num_frames_ < max_frames_, -1, "more frames than max_frames (CHECK_LE)");
   const int t = num_frames_;
   const int base = (int)(wh_ * t);
@@ -170,10 +175,40 @@ void DenseGraphHip::AddFrame(const float* feat, const int32_t* cons_dev) {
   lb.type = 0;
   lb.base_a = base;
   lb.base_b = base;
-  LaunchSpatialKeys(feat, W_, H_, l1_ ? 1 : 0, keys_tmp_.get(), hist_tmp_.get(), stream_);
-  SortList(lb, 4);
+  LaunchSpatialKeys(feat, W_, H_, l1_ ? 1 : 0, keys_tmp_[0].get(), hist_tmp_[0].get(), stream_);
   if (cons_dev) has_constraints_ = true;
   ++num_frames_;
+  return lb;
+}
+
+// The key kernel of the temporal list between the last two slices.
+DenseGraphHip::ListBuf& DenseGraphHip::PrepareTemporalList(const float* cur, const float* prev,
+                                                           const float* flow, bool is_virtual) {
+  VSG_REQUIRE(num_frames_ >= 2, -3, "temporal edges need two slices");
+  const int t = num_frames_ - 1;
+  ListBuf& lb = lists_[2 * t - 1];
+  lb.type = 1;
+  lb.base_a = (int)(wh_ * t);
+  lb.base_b = (int)(wh_ * (t - 1));
+  lb.prev_idx.ensure(wh_);
+  LaunchTemporalKeys(cur, prev, flow, W_, H_, l1_ ? 1 : 0, is_virtual ? 1 : 0, keys_tmp_[1].get(),
+                     lb.prev_idx.get(), hist_tmp_[1].get(), stream_);
+  return lb;
+}
+
+void DenseGraphHip::AddFrame(const float* feat, const int32_t* cons_dev) {
+  const EdgeSortList l = SortEntry(PrepareSpatialList(feat, cons_dev), 4);
+  LaunchBucketSort(&l, 1, wh_, stream_);
+}
+
+void DenseGraphHip::AddFrameAndTemporal(const float* feat, const int32_t* cons_dev, const float* prev,
+                                        const float* flow, bool is_virtual) {
+  VSG_REQUIRE(num_frames_ >= 1, -3, "temporal edges need two slices");
+  ListBuf& sp = PrepareSpatialList(feat, cons_dev);
+  ListBuf& tp = PrepareTemporalList(is_virtual ? nullptr : feat, is_virtual ? nullptr : prev, flow, is_virtual);
+  // (the temporal tiles first: the spatial ones fill the last round of resident workgroups)
+  const EdgeSortList l[2] = {SortEntry(tp, 9), SortEntry(sp, 4)};
+  LaunchBucketSort(l, 2, wh_, stream_);
 }
 
 void DenseGraphHip::AddVirtualFrame(const int32_t* ids_dev, int max_label) {
@@ -215,16 +250,8 @@ void DenseGraphHip::SetHaloLabels(const int32_t* virtual_ids_dev, const int32_t*
 
 void DenseGraphHip::AddTemporal(const float* cur, const float* prev, const float* flow,
                                 bool is_virtual) {
-  VSG_REQUIRE(num_frames_ >= 2, -3, "temporal edges need two slices");
-  const int t = num_frames_ - 1;
-  ListBuf& lb = lists_[2 * t - 1];
-  lb.type = 1;
-  lb.base_a = (int)(wh_ * t);
-  lb.base_b = (int)(wh_ * (t - 1));
-  lb.prev_idx.ensure(wh_);
-  LaunchTemporalKeys(cur, prev, flow, W_, H_, l1_ ? 1 : 0, is_virtual ? 1 : 0, keys_tmp_.get(),
-                     lb.prev_idx.get(), hist_tmp_.get(), stream_);
-  SortList(lb, 9);
+  const EdgeSortList l = SortEntry(PrepareTemporalList(cur, prev, flow, is_virtual), 9);
+  LaunchBucketSort(&l, 1, wh_, stream_);
 }
 
 void DenseGraphHip::FinishBuilding() { VSG_HIP(hipStreamSynchronize(stream_)); }
@@ -1967,6 +1994,18 @@ void DenseGraphHip::CopySpatialBuckets(int t, uint16_t* out) {
       out[(size_t)(s & 3u) * wh_ + (s >> 2)] = (uint16_t)b;
     }
   }
+}
+
+int DenseGraphHip::CopyListSlots(int list, uint32_t* slots_host, int32_t* offsets_host) {
+  VSG_REQUIRE(list >= 0 && list < (int)lists_.size() && lists_[list].used, -1, "no such list");
+  ListBuf& lb = lists_[list];
+  D2H(offsets_host, lb.offsets.get(), (size_t)kBucketSlots, stream_);
+  VSG_HIP(hipStreamSynchronize(stream_));
+  const int n = offsets_host[kBucketSlots - 1];   // (the slots of the last bin, edges that do not exist, are not listed)
+  VSG_REQUIRE(n >= 0 && n <= lb.n, -4, "offsets out of range");
+  D2H(slots_host, lb.slots.get(), (size_t)n, stream_);
+  VSG_HIP(hipStreamSynchronize(stream_));
+  return n;
 }
 
 void DenseGraphHip::CopyTemporalBuckets(int t, uint16_t* out, int32_t* prev_idx) {

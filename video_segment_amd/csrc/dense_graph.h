@@ -80,6 +80,11 @@ class DenseGraphHip {
   // AddTemporal[Flow][Virtual]Edges: connects the last two slices.
   void AddTemporal(const float* cur_dev, const float* prev_dev, const float* flow_dev,
                    bool is_virtual);
+  // AddFrame followed by AddTemporal (cur = the new frame; both null for a virtual list) as one chain
+  // on the stream: both key kernels, one scan over both histogram matrices, one scatter over the
+  // tiles of both lists.  Same lists, bit for bit, as the two calls.
+  void AddFrameAndTemporal(const float* feat_planar_dev, const int32_t* cons_dev, const float* prev_dev,
+                           const float* flow_dev, bool is_virtual);
   void FinishBuilding();
   void Segment(int min_region_size, bool force_constraints) {
     SegmentLists(min_region_size, force_constraints, spatial_pass_done_ ? 2 : 0);
@@ -105,6 +110,10 @@ class DenseGraphHip {
   void CopySpatialBuckets(int t, uint16_t* out_host);                     // [4][H][W]
   void CopyTemporalBuckets(int t, uint16_t* out_host, int32_t* prev_idx_host);   // [9][H][W]
   void CopyNodeRoots(int32_t* out_host);
+  // A list as the device holds it (list 2 t: spatial list of slice t, 2 t - 1: temporal list between
+  // slices t - 1 and t): its kBucketSlots offsets and the first offsets[kBucketSlots - 1] sorted slots.
+  // Returns that number of slots; slots_host holds 4 or 9 W*H entries.
+  int CopyListSlots(int list, uint32_t* slots_host, int32_t* offsets_host);
   // Entry i: representative of node i and that region's state as the last Segment /
   // SegmentSpatially left it -- mean (3 f32 per node), size, constraint id, the flags byte as stored
   // (device_graph.h: kFlag*).  Host outputs of W*H*num_frames entries.
@@ -125,7 +134,9 @@ class DenseGraphHip {
   void EnsureScratch(size_t n_edges_max);
   void EnsureActiveScratch(size_t n_active_max);
   void DebugHash(const char* where);
-  void SortList(ListBuf& lb, int per_px);
+  ListBuf& PrepareSpatialList(const float* feat, const int32_t* cons_dev);
+  ListBuf& PrepareTemporalList(const float* cur, const float* prev, const float* flow, bool is_virtual);
+  EdgeSortList SortEntry(ListBuf& lb, int per_px);
   void MergeConstrainedHostAssisted();
   NodeArrays nodes() {
     return NodeArrays{parent_.get(), desc_sz_.get(), cons_.get(), flags_.get(), hub8_.get()};
@@ -170,8 +181,10 @@ class DenseGraphHip {
   DevBuf<int32_t> bucket_base_dev_;
   std::vector<int32_t> bucket_base_host_;
   // temporaries for edge generation / sorting
-  DevBuf<uint16_t> keys_tmp_;
-  DevBuf<int32_t> hist_tmp_, hist_sums_;   // edge_sort.hip scratch
+  // edge_sort.hip scratch, [0] of the spatial and [1] of the temporal list of a frame (their own, so
+  // that one chain can build both): keys, tile histograms, chunk bases of the scan
+  DevBuf<uint16_t> keys_tmp_[2];
+  DevBuf<int32_t> hist_tmp_[2], hist_chunk_[2];
   DevBuf<int32_t> first_label_scratch_;
   // merge scratch
   DevBuf<int32_t> e_ra_, e_rb_;

@@ -99,19 +99,29 @@ void LaunchConvertPlanar(const uint8_t* bgr, size_t stride, int W, int H, float*
 void LaunchInterleavedToPlanar(const float* in, size_t n, float* planes, hipStream_t s);
 void LaunchPlanarToInterleaved(const float* planes, size_t n, float* out, hipStream_t s);
 // ---- edge_sort.hip: edge keys + stable bucket (counting) sort of the edge slots -----------------
-// keys: u16 per slot (slot = pix*4+k / pix*9+k); hist: bin-major tile histograms (scratch of
-// EdgeSortHistInts ints, sums: EdgeSortSumInts ints).
-size_t EdgeSortHistInts(size_t n_px);
-size_t EdgeSortSumInts(size_t n_px);
+// keys: u16 per slot (slot = pix*4+k / pix*9+k); hist: one dense row of kBucketSlots counts per tile
+// (scratch of EdgeSortHistInts ints, written in full by the key kernels), chunk: the scan's chunk
+// bases (EdgeSortChunkInts ints).  per_px: 4 (spatial list) or 9 (temporal list).
+size_t EdgeSortHistInts(size_t n_px, int per_px);
+size_t EdgeSortChunkInts(size_t n_px, int per_px);
+// One list of a LaunchBucketSort call; the lists of a call do not share scratch.
+struct EdgeSortList {
+  const uint16_t* keys;
+  int32_t* hist;
+  int32_t* chunk;
+  int32_t* offsets;   // out [kBucketSlots]: start of every bucket
+  uint32_t* slots;    // out: slot ids of the existing edges, stably sorted by bucket
+  int per_px;
+};
+constexpr int kEdgeSortMaxLists = 2;
 void LaunchSpatialKeys(const float* feat, int W, int H, int l1, uint16_t* keys, int32_t* hist,
                        hipStream_t s);
 void LaunchTemporalKeys(const float* cur, const float* prev, const float* flow, int W, int H,
                         int l1, int is_virtual, uint16_t* keys, int32_t* prev_idx, int32_t* hist,
                         hipStream_t s);
-// offsets[kBucketSlots]: start of every bucket; slots_out: slot ids of the existing edges, stably
-// sorted by bucket.
-void LaunchBucketSort(const uint16_t* keys, size_t n_px, int per_px, int32_t* hist, int32_t* sums,
-                      int32_t* offsets, uint32_t* slots_out, hipStream_t s);
+// Sorts the lists of one frame (n_px pixels each) in one chain: two scan launches and one scatter
+// whose grid covers the tiles of all lists, in the order given (the list with the longer tiles first).
+void LaunchBucketSort(const EdgeSortList* lists, int n_lists, size_t n_px, hipStream_t s);
 void LaunchInitNodes(const float* feat, size_t n, int base, const int32_t* cons_in,
                      NodeArrays nodes, hipStream_t s);
 void LaunchInitVirtualNodes(const int32_t* labels, size_t n, int base, int num_labels,

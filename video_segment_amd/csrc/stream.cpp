@@ -248,11 +248,11 @@ int DenseSegmentationHip::ProcessFrame(bool flush, const uint8_t* bgr, size_t st
       pending_import_ = false;
     } else {
       feature_buffer_.push_back(feat);
-      graph_->AddFrame(feat->get(), nullptr);
-      if (feature_buffer_.size() > 1) {
+      if (feature_buffer_.size() > 1) {   // both lists of the frame in one chain
         const float* fl = flow_dev_buffer_.empty() ? nullptr : flow_dev_buffer_.back()->get();
-        graph_->AddTemporal(feature_buffer_.end()[-1]->get(), feature_buffer_.end()[-2]->get(), fl,
-                            false);
+        graph_->AddFrameAndTemporal(feat->get(), nullptr, feature_buffer_.end()[-2]->get(), fl, false);
+      } else {
+        graph_->AddFrame(feat->get(), nullptr);
       }
     }
     VSG_HIP(hipEventRecord(edge_ev_[(size_t)ev + 1], stream_));
@@ -299,9 +299,8 @@ void DenseSegmentationHip::StartConstrainedGraph(const int32_t* virt_ids_dev,
   } else {
     graph_->AddVirtualFrameDeferred();
   }
-  graph_->AddFrame(feature_buffer_[1]->get(), cons_ids_dev);
   const float* fl = flow_dev_buffer_.empty() ? nullptr : flow_dev_buffer_[1]->get();
-  graph_->AddTemporal(nullptr, nullptr, fl, true);
+  graph_->AddFrameAndTemporal(feature_buffer_[1]->get(), cons_ids_dev, nullptr, fl, true);
 }
 
 void DenseSegmentationHip::ChunkBoundaryOutput(bool flush) {

@@ -278,7 +278,10 @@ class DenseSegGraph:
             _same_mem(mem_c, mem, "constraint_ids")
         check(lib().vsg_graph_add_frame_bgr(self.h, p, _row_stride(bgr), presmoothing, pc, mem))
 
-    def add_frame_features(self, feat, constraint_ids=None):
+    def add_frame_features(self, feat, constraint_ids=None, temporal=False, flow=None, is_virtual=False):
+        """Adds a slice of smoothed features.  With temporal=True (or a flow) the temporal list to the
+        slice before it is built in the same chain of kernels (vsg_graph_add_frame_features_temporal):
+        the result equals add_frame_features followed by add_temporal(flow, is_virtual)."""
         if not _is_torch(feat):
             feat = np.ascontiguousarray(feat, np.float32)
         assert tuple(feat.shape) == (self.H, self.W, 3)
@@ -288,7 +291,15 @@ class DenseSegGraph:
         pc, mem_c = _ptr_mem(constraint_ids, "int32")
         if constraint_ids is not None:
             _same_mem(mem_c, mem, "constraint_ids")
-        check(lib().vsg_graph_add_frame_features(self.h, p, pc, mem))
+        if not (temporal or flow is not None or is_virtual):
+            check(lib().vsg_graph_add_frame_features(self.h, p, pc, mem))
+            return
+        if flow is not None and not _is_torch(flow):
+            flow = np.ascontiguousarray(flow, np.float32)
+        pf, mem_f = _ptr_mem(flow, "float32")
+        if flow is not None:
+            _same_mem(mem_f, mem, "flow")
+        check(lib().vsg_graph_add_frame_features_temporal(self.h, p, pc, pf, int(is_virtual), mem))
 
     def add_virtual_frame(self, constraint_ids):
         if not _is_torch(constraint_ids):
@@ -375,6 +386,17 @@ class DenseSegGraph:
         check(lib().vsg_graph_temporal_buckets(self.h, t, out.ctypes.data_as(C.c_void_p),
                                                pidx.ctypes.data_as(C.c_void_p)))
         return out, pidx
+
+    def list_slots(self, index):
+        """(slots, offsets) of an edge list as the device holds it (vsg_graph_list_slots): index 2 t is
+        the spatial list of slice t, 2 t - 1 the temporal list between slices t - 1 and t; offsets has
+        2050 entries, slots the offsets[2049] listed slot ids."""
+        per_px = 4 if index % 2 == 0 else 9
+        slots = np.empty(per_px * self.H * self.W, np.uint32)
+        offsets = np.empty(2050, np.int32)
+        check(lib().vsg_graph_list_slots(self.h, int(index), slots.ctypes.data_as(C.c_void_p),
+                                         offsets.ctypes.data_as(C.c_void_p)))
+        return slots[:int(offsets[2049])].copy(), offsets
 
     def node_roots(self):
         out = np.empty(self.W * self.H * self.num_frames(), np.int32)
