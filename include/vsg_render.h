@@ -44,7 +44,9 @@
  * segmentation/boundary.cpp) is offered by vsg_render_level_contours: the closed outlines of every region or
  * component as ordered vertex lists.  The reference's shared-segment mesh (segments cut at junctions and
  * shared by the two regions they separate) is offered by vsg_render_level_mesh, at any level and for
- * components; the approxPolyDP simplification of its segments is still not offered.
+ * components, and the approxPolyDP simplification of its segments by vsg_render_level_mesh_simplified.  The
+ * reference's polygon assembly on top of it (min_hole_length, its unordered_map hole order, the vector_mesh
+ * numbering) is still not offered.
  * Which regions or components of a level touch in a frame, and along how many pixel sides, is what
  * vsg_render_level_adjacency returns; the reference has no per-frame counterpart
  * (CompoundRegion.neighbor_id covers a chunk in 3-D).  Scores
@@ -844,6 +846,82 @@ typedef struct vsg_render_mesh_stats {
   int rounds, launches;
 } vsg_render_mesh_stats;                  /* 104 bytes with 4 bytes of tail padding */
 int vsg_render_last_mesh_stats(vsg_render* h, vsg_render_mesh_stats* s);
+
+/* ---- Simplified level mesh: the segments of the level mesh after Douglas-Peucker, on the device ----
+ *
+ * The reference's result files hold its borders after cv::approxPolyDP at max_error 1.0
+ * (ComputeVectorization, segmentation/boundary.cpp).  vsg_render_level_mesh_simplified applies that step to
+ * every segment of vsg_render_level_mesh.  A shared segment is simplified once, so the two groups it separates
+ * still meet along the same polyline.
+ *
+ * Segments, their order, right, left, length (cracks), closed, start_sides, end_sides, loops and refs are
+ * exactly those of vsg_render_level_mesh for the same (level, connectedness).  Only `vertices`, and each
+ * record's first_vertex and num_vertices, change.
+ *
+ * The point list.  Q(s) holds every lattice corner segment s passes, in the owner's direction of travel.  An
+ * open segment has length + 1 points, both end corners included.  A closed segment has length points.  It
+ * begins at the first vertex the mesh call lists for it, and none is repeated.
+ *
+ * Collapse rule.  Let t = max(3, min_segment_points) if min_segment_points > 0, else 0.  An open segment with
+ * length + 1 < t becomes {first corner, last corner}.  The reference's call uses 4.
+ *
+ * Otherwise the new list is ApproxPolyDP(Q, (double)max_error, closed = record.closed): OpenCV 2.4's
+ * approxPolyDP for integer points as this project restates it (video_segment_amd/csrc/boundary.cpp,
+ * tests/boundary_oracle.py).  It has three parts.  The three farthest-point sweeps choose the start of a
+ * closed curve.  The recursion splits a slice at its farthest point (dist > max_dist: the first index wins a
+ * tie) unless max_dist * max_dist <= eps * (dx * dx + dy * dy), with eps = max_error * max_error in double.
+ * The final in-place pass drops points on almost straight joints, the wrap-around read of a closed list
+ * included.  An open segment whose two end corners coincide goes in as closed = false, as the mesh records it;
+ * the function's own start_pt == end_pt branch handles it.
+ *
+ * An open segment always keeps both end corners (num_vertices >= 2).  A closed segment may come back with 1
+ * vertex or more.  Its vertex count need not be even.  It is generally a rotation of the list, because the
+ * sweeps choose the start.  max_error = 0 with min_segment_points = 0 returns every open segment's corner list
+ * unchanged, and every closed segment's list as a cyclic rotation.
+ *
+ * The stages work on the corner lists the mesh stages leave on the device, not on Q: along a straight run the
+ * distance to a chord is linear and the distance to a sweep's start is strictly convex, so every maximum falls
+ * on a corner.  Every double expression of the host function is evaluated operation for operation, without
+ * contraction.
+ *
+ * max_error has to be finite and >= 0, min_segment_points >= 0.  Both are checked together with the null
+ * handle, the null count pointers, mem_out and connectedness, before the handle is dereferenced; the refusal is
+ * VSG_ERR_INVALID with the argument's name in the last-error text.  Capacities, count-only calls, "no output is
+ * touched", level and vector-only rules and the 32-bit key limit are those of vsg_render_level_mesh:
+ * *num_segments, *num_vertices, *num_loops and *num_refs are always set on VSG_OK and when a capacity is too
+ * small; in that case the call fails with VSG_ERR_INVALID and no output is touched.  All four outputs NULL with
+ * all four capacities 0 asks for the counts only (VSG_OK; needs the device).  A frame with no covered pixel
+ * returns four zero counts.  The call neither resolves nor changes the level the handle keeps for
+ * vsg_render_frame.  All four lists in mem_out memory.
+ *
+ * The call runs the contour and mesh stages internally, as a count-only mesh call: afterwards
+ * vsg_render_last_contour_stats and vsg_render_last_mesh_stats describe that run. */
+int vsg_render_level_mesh_simplified(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
+                                     int connectedness, float max_error, int min_segment_points,
+                                     vsg_render_mesh_segment* segments, size_t capacity_segments,
+                                     size_t* num_segments, int32_t* vertices, size_t capacity_vertices,
+                                     size_t* num_vertices, vsg_render_mesh_loop* loops, size_t capacity_loops,
+                                     size_t* num_loops, int32_t* refs, size_t capacity_refs, size_t* num_refs,
+                                     int mem_out);
+
+/* What the last vsg_render_level_mesh_simplified call of the handle did.  segments: the mesh's;
+ * collapsed_segments: open segments the collapse rule replaced by their end corners; vertices_in: the mesh's
+ * vertices; vertices_kept: vertices after the recursion (2 for a collapsed segment); vertices_out: after the
+ * joint pass, the length of `vertices`; single_vertex_closed: closed segments that came back as one vertex;
+ * longest_segment_vertices_in: the most vertices a segment of the mesh has; max_rounds: the most refinement
+ * rounds any segment took, a round being one level of the recursion in which a vertex was kept.  Device times
+ * are HIP events around the stages: dp_us, the collapse rule, the sweeps and the rounds; clean_us, the joint
+ * pass; table_us, the scan, the compaction, the records and the copies.  launches, those of the contour and
+ * mesh stages included, is a function of the connectedness, of ceil(log2 cracks), of where the outputs go and
+ * of how the plane is made, not of the plane's content, max_error or min_segment_points: no launch happens
+ * per round.  Everything is 0 when there is no crack, but launches. */
+typedef struct vsg_render_simplify_stats {
+  int64_t segments, collapsed_segments, vertices_in, vertices_kept, vertices_out, single_vertex_closed,
+      longest_segment_vertices_in;
+  float dp_us, clean_us, table_us;
+  int max_rounds, launches;
+} vsg_render_simplify_stats;              /* 80 bytes with 4 bytes of tail padding */
+int vsg_render_last_simplify_stats(vsg_render* h, vsg_render_simplify_stats* s);
 
 /* ---- Boundary distance: the exact distance transform of a level's edges, boundary scores of all levels ----
  *

@@ -61,6 +61,11 @@
 // level_mesh_count=<segments over all frames> level_mesh_fnv1a32=<hash of every frame's segments, vertices,
 // loops and refs bytes, in that order>.
 //
+//   --level_mesh <level> --mesh_max_error <e> [--mesh_min_segment_points <n>]
+// asks vsg_render_level_mesh_simplified instead (n: 4 when absent; e finite and >= 0, n >= 0; either flag without
+// the one before it is refused) and prints
+// level_mesh_simplified_count=<segments over all frames> level_mesh_simplified_fnv1a32=<the same hash of its lists>.
+//
 //   --boundary_distance <level>
 // asks vsg_render_boundary_distance for the exact squared distance of every pixel to that level's nearest
 // edge pixel, for every frame, and prints a line
@@ -532,11 +537,12 @@ class LevelContoursSinkUnit : public VideoUnit {
 };
 
 // --level_mesh: the same for the shared-segment mesh of a level's regions or of their connected components
-// (vsg_render_level_mesh): segments, vertices, loops, refs.
+// (vsg_render_level_mesh): segments, vertices, loops, refs.  max_error >= 0: vsg_render_level_mesh_simplified.
 class LevelMeshSinkUnit : public VideoUnit {
  public:
-  LevelMeshSinkUnit(int level, int connectedness, int device)
-      : level_(level), connect_(connectedness), device_(device) {}
+  LevelMeshSinkUnit(int level, int connectedness, int device, float max_error, int min_segment_points)
+      : level_(level), connect_(connectedness), device_(device), max_error_(max_error),
+        min_segment_points_(min_segment_points) {}
   ~LevelMeshSinkUnit() override { vsg_render_destroy(render_); }
   bool OpenStreams(StreamSet* set) override {
     seg_idx_ = FindStreamIdx("SegmentationStream", set);
@@ -557,17 +563,22 @@ class LevelMeshSinkUnit : public VideoUnit {
     const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
     const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
     size_t ns = 0, nv = 0, nl = 0, nr = 0;
-    VF_CHECK(vsg_render_level_mesh(render_, seg, desc.wire.size(), level_, connect_, nullptr, 0, &ns, nullptr, 0, &nv,
-                                   nullptr, 0, &nl, nullptr, 0, &nr, VSG_MEM_HOST) == VSG_OK,
-             vsg_render_last_error());
+    auto mesh = [&](vsg_render_mesh_segment* segments, int32_t* vertices, vsg_render_mesh_loop* loops, int32_t* refs) {
+      if (max_error_ >= 0) {
+        return vsg_render_level_mesh_simplified(render_, seg, desc.wire.size(), level_, connect_, max_error_,
+                                                min_segment_points_, segments, ns, &ns, vertices, nv, &nv, loops, nl,
+                                                &nl, refs, nr, &nr, VSG_MEM_HOST);
+      }
+      return vsg_render_level_mesh(render_, seg, desc.wire.size(), level_, connect_, segments, ns, &ns, vertices, nv, &nv,
+                                   loops, nl, &nl, refs, nr, &nr, VSG_MEM_HOST);
+    };
+    VF_CHECK(mesh(nullptr, nullptr, nullptr, nullptr) == VSG_OK, vsg_render_last_error());
     segments_buf_.resize(ns);
     vertices_buf_.resize(2 * nv);
     loops_buf_.resize(nl);
     refs_buf_.resize(nr);
     if (ns) {
-      VF_CHECK(vsg_render_level_mesh(render_, seg, desc.wire.size(), level_, connect_, segments_buf_.data(), ns, &ns,
-                                     vertices_buf_.data(), nv, &nv, loops_buf_.data(), nl, &nl, refs_buf_.data(), nr,
-                                     &nr, VSG_MEM_HOST) == VSG_OK,
+      VF_CHECK(mesh(segments_buf_.data(), vertices_buf_.data(), loops_buf_.data(), refs_buf_.data()) == VSG_OK,
                vsg_render_last_error());
     }
     Hash(segments_buf_.data(), ns * sizeof(vsg_render_mesh_segment));
@@ -589,6 +600,8 @@ class LevelMeshSinkUnit : public VideoUnit {
     }
   }
   int level_, connect_, device_, seg_idx_ = -1;
+  float max_error_;
+  int min_segment_points_;
   vsg_render* render_ = nullptr;
   std::vector<vsg_render_mesh_segment> segments_buf_;
   std::vector<int32_t> vertices_buf_;
@@ -1107,6 +1120,11 @@ struct Flags {
   // (N4, or N8 with --components_n8) with --mesh_components
   int level_mesh = -1;
   bool mesh_components = false;
+  // mesh_simplified (--mesh_max_error was given): vsg_render_level_mesh_simplified with this max_error and
+  // mesh_min_segment_points instead
+  bool mesh_simplified = false, mesh_min_segment_points_given = false;
+  float mesh_max_error = 1.0f;
+  int mesh_min_segment_points = 4;
   // vsg_render_boundary_distance at this level for every frame; < 0: off
   int boundary_distance = -1;
   // vsg_render_boundary_benchmark with this tolerance_sq for every frame after the first, against the
@@ -1211,6 +1229,13 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "contours_components") f->contours_components = bv;
     else if (a == "level_mesh") f->level_mesh = atoi(v.c_str());
     else if (a == "mesh_components") f->mesh_components = bv;
+    else if (a == "mesh_max_error") {
+      f->mesh_simplified = true;
+      f->mesh_max_error = (float)atof(v.c_str());
+    } else if (a == "mesh_min_segment_points") {
+      f->mesh_min_segment_points_given = true;
+      f->mesh_min_segment_points = atoi(v.c_str());
+    }
     else if (a == "chunk_set_size") f->chunk_set_size = atoi(v.c_str());
     else if (a == "chunk_set_overlap") f->chunk_set_overlap = atoi(v.c_str());
     else if (a == "min_region_num") f->min_region_num = atoi(v.c_str());
@@ -1233,6 +1258,22 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
       std::fprintf(stderr, "unknown flag --%s\n", a.c_str());
       return false;
     }
+  }
+  if (f->mesh_simplified && f->level_mesh < 0) {
+    std::fprintf(stderr, "--mesh_max_error needs --level_mesh\n");
+    return false;
+  }
+  if (f->mesh_min_segment_points_given && !f->mesh_simplified) {
+    std::fprintf(stderr, "--mesh_min_segment_points needs --mesh_max_error\n");
+    return false;
+  }
+  if (f->mesh_simplified && (!std::isfinite(f->mesh_max_error) || f->mesh_max_error < 0)) {
+    std::fprintf(stderr, "--mesh_max_error has to be a finite number >= 0\n");
+    return false;
+  }
+  if (f->mesh_min_segment_points < 0) {
+    std::fprintf(stderr, "--mesh_min_segment_points has to be >= 0\n");
+    return false;
   }
   return true;
 }
@@ -1475,7 +1516,9 @@ int main(int argc, char** argv) {
     const int connectedness = !FLAGS.mesh_components ? 0
                               : FLAGS.components_n8  ? VSG_RENDER_CONNECT_N8
                                                      : VSG_RENDER_CONNECT_N4;
-    mesh_sink.reset(new LevelMeshSinkUnit(FLAGS.level_mesh, connectedness, FLAGS.device));
+    mesh_sink.reset(new LevelMeshSinkUnit(FLAGS.level_mesh, connectedness, FLAGS.device,
+                                          FLAGS.mesh_simplified ? FLAGS.mesh_max_error : -1.0f,
+                                          FLAGS.mesh_min_segment_points));
     mesh_sink->AttachTo(input);
     input = mesh_sink.get();
   }
@@ -1561,7 +1604,9 @@ int main(int argc, char** argv) {
                 contours_sink->hash());
   }
   if (mesh_sink) {
-    std::printf("level_mesh_count=%ld level_mesh_fnv1a32=%08x\n", mesh_sink->segments(), mesh_sink->hash());
+    std::printf(FLAGS.mesh_simplified ? "level_mesh_simplified_count=%ld level_mesh_simplified_fnv1a32=%08x\n"
+                                          : "level_mesh_count=%ld level_mesh_fnv1a32=%08x\n",
+                mesh_sink->segments(), mesh_sink->hash());
   }
   if (distance_sink && distance_sink->level() >= 0) {
     std::printf("boundary_distance_level=%d boundary_distance_edge_pixels=%ld boundary_distance_max=%ld "

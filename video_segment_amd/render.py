@@ -130,6 +130,16 @@ class VsgRenderMeshStats(_capi.Structure):
     ]
 
 
+class VsgRenderSimplifyStats(_capi.Structure):
+    _fields_ = [
+        ("segments", C.c_int64), ("collapsed_segments", C.c_int64), ("vertices_in", C.c_int64),
+        ("vertices_kept", C.c_int64), ("vertices_out", C.c_int64), ("single_vertex_closed", C.c_int64),
+        ("longest_segment_vertices_in", C.c_int64),
+        ("dp_us", C.c_float), ("clean_us", C.c_float), ("table_us", C.c_float),
+        ("max_rounds", C.c_int), ("launches", C.c_int),
+    ]
+
+
 class VsgRenderDistanceStats(_capi.Structure):
     _fields_ = [
         ("levels", C.c_int64), ("edge_pixels", C.c_int64), ("other_edge_pixels", C.c_int64),
@@ -278,6 +288,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
     "vsg_render_level_contours", "vsg_render_last_contour_stats",
     "vsg_render_level_mesh", "vsg_render_last_mesh_stats",
+    "vsg_render_level_mesh_simplified", "vsg_render_last_simplify_stats",
     "vsg_render_boundary_distance", "vsg_render_boundary_benchmark", "vsg_render_last_distance_stats",
 ]
 
@@ -350,6 +361,11 @@ def lib():
                                         vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t),
                                         C.c_int]
     L.vsg_render_last_mesh_stats.argtypes = [vp, C.POINTER(VsgRenderMeshStats)]
+    L.vsg_render_level_mesh_simplified.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, C.c_float, C.c_int,
+                                                   vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t,
+                                                   C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t),
+                                                   vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_simplify_stats.argtypes = [vp, C.POINTER(VsgRenderSimplifyStats)]
     L.vsg_render_boundary_distance.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_int]
     L.vsg_render_boundary_benchmark.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp,
                                                 C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
@@ -960,14 +976,19 @@ class SegmentationRenderer(_capi.Handle):
         (capacity,) int32) or all four torch CUDA int32 tensors ((capacity, 8), (capacity, 2), (capacity, 4),
         (capacity,)); the filled parts of them are returned.  See mesh_polygons and mesh_desc."""
         seg_bytes = bytes(seg_bytes)
+        head = (self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness))
+        return self._mesh_lists(lib().vsg_render_level_mesh, head, segments_out, vertices_out, loops_out, refs_out)
+
+    @staticmethod
+    def _mesh_lists(entry, head, segments_out, vertices_out, loops_out, refs_out):
+        """The four lists of a mesh entry point: `entry(*head, <the lists>, mem_out)`."""
         ns, nv, nl, nr = C.c_size_t(), C.c_size_t(), C.c_size_t(), C.c_size_t()
         outs = (segments_out, vertices_out, loops_out, refs_out)
         if any(o is None for o in outs) and not all(o is None for o in outs):
             raise ValueError("pass all four outputs or none")
         if segments_out is None:
-            check(lib().vsg_render_level_mesh(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
-                                              None, 0, C.byref(ns), None, 0, C.byref(nv), None, 0, C.byref(nl),
-                                              None, 0, C.byref(nr), VSG_MEM_HOST))
+            check(entry(*head, None, 0, C.byref(ns), None, 0, C.byref(nv), None, 0, C.byref(nl),
+                        None, 0, C.byref(nr), VSG_MEM_HOST))
             segments_out = np.empty(ns.value, MESH_SEGMENT_DTYPE)
             vertices_out = np.empty((nv.value, 2), np.int32)
             loops_out = np.empty(nl.value, MESH_LOOP_DTYPE)
@@ -995,17 +1016,36 @@ class SegmentationRenderer(_capi.Handle):
         ptrs = [_capi.contiguous_ptr(o) for o in outs]
         if len({mem for _, mem in ptrs}) != 1:
             raise ValueError("all outputs have to be in the same kind of memory")
-        check(lib().vsg_render_level_mesh(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
-                                          ptrs[0][0], segments_out.shape[0], C.byref(ns),
-                                          ptrs[1][0], vertices_out.shape[0], C.byref(nv),
-                                          ptrs[2][0], loops_out.shape[0], C.byref(nl),
-                                          ptrs[3][0], refs_out.shape[0], C.byref(nr), ptrs[0][1]))
+        check(entry(*head, ptrs[0][0], segments_out.shape[0], C.byref(ns), ptrs[1][0], vertices_out.shape[0],
+                    C.byref(nv), ptrs[2][0], loops_out.shape[0], C.byref(nl), ptrs[3][0], refs_out.shape[0],
+                    C.byref(nr), ptrs[0][1]))
         return segments_out[:ns.value], vertices_out[:nv.value], loops_out[:nl.value], refs_out[:nr.value]
 
     def last_mesh_stats(self):
         """vsg_render_last_mesh_stats of the last level_mesh call, as a dict."""
         s = VsgRenderMeshStats()
         check(lib().vsg_render_last_mesh_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
+    def level_mesh_simplified(self, seg_bytes, level=0, connectedness=0, max_error=1.0, min_segment_points=4,
+                              segments_out=None, vertices_out=None, loops_out=None, refs_out=None):
+        """level_mesh with every segment's vertex list simplified on the device as the reference's
+        ComputeVectorization does: an open segment of fewer than max(3, min_segment_points) lattice points
+        (min_segment_points = 0: none) becomes its two end corners, every other segment goes through
+        Douglas-Peucker (OpenCV 2.4's approxPolyDP for integer points) at max_error.  Segments, loops and refs
+        are those of level_mesh; only the vertices and the records' first_vertex / num_vertices differ.  An open
+        segment keeps both end corners; a closed one may come back rotated, and as a single vertex.  Outputs as
+        for level_mesh.  See mesh_polygons and simplified_mesh_desc."""
+        seg_bytes = bytes(seg_bytes)
+        head = (self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), float(max_error),
+                int(min_segment_points))
+        return self._mesh_lists(lib().vsg_render_level_mesh_simplified, head, segments_out, vertices_out, loops_out,
+                                refs_out)
+
+    def last_simplify_stats(self):
+        """vsg_render_last_simplify_stats of the last level_mesh_simplified call, as a dict."""
+        s = VsgRenderSimplifyStats()
+        check(lib().vsg_render_last_simplify_stats(self.h, C.byref(s)))
         return s.as_dict()
 
     def boundary_distance(self, seg_bytes, level=0, out=None):
@@ -1150,27 +1190,40 @@ def mesh_polygons(segments, vertices, loops, refs):
     """The host arrays of level_mesh as polygons: a list with one entry per group, in group order, each the list
     of that group's (n, 2) int32 vertex arrays, one per loop in loop order.  Every loop is rebuilt from its refs:
     joints listed once, collinear corners dropped, rotated to begin at the start corner of its turn crack of
-    smallest key, so that the result equals contour_polygons of the level_contours call.  Host numpy only."""
+    smallest key, so that the result equals contour_polygons of the level_contours call.  The arrays of
+    level_mesh_simplified are taken as well: a point repeated at a joint is listed once, a point on the straight
+    line between its neighbours is dropped, and an oblique edge counts as the side whose quadrant its direction
+    lies in (0: x grows and y does not fall, 1: y grows and x does not grow, 2: x falls and y does not grow, 3: y
+    falls and x does not fall), which for the edges of level_mesh is their side.  A loop that is left with fewer
+    than three points is returned as it is.  Host numpy only."""
     segments, vertices, loops, refs = (np.asarray(a) for a in (segments, vertices, loops, refs))
     groups = [[] for _ in range(int(loops["group"].max()) + 1 if len(loops) else 0)]
-    side_of = {(1, 0): 0, (0, 1): 1, (-1, 0): 2, (0, -1): 3}
     start = ((0, 0), (1, 0), (1, 1), (0, 1))
+
+    def side_of(a, b):
+        dx, dy = b[0] - a[0], b[1] - a[1]
+        return 0 if dx > 0 and dy >= 0 else 1 if dy > 0 else 2 if dx < 0 else 3
+
+    def straight(a, b, c):
+        """b lies between a and c on one line."""
+        return ((b[0] - a[0]) * (c[1] - b[1]) == (b[1] - a[1]) * (c[0] - b[0])
+                and (b[0] - a[0]) * (c[0] - b[0]) + (b[1] - a[1]) * (c[1] - b[1]) > 0)
+
     for loop in loops:
         pts = _loop_points(segments, vertices, loop, refs)
+        pts = [p for k, p in enumerate(pts) if len(pts) == 1 or p != pts[k - 1]]
         n = len(pts)
-
-        def direction(a, b):
-            return ((b[0] > a[0]) - (b[0] < a[0]), (b[1] > a[1]) - (b[1] < a[1]))
-
-        kept = [k for k in range(n) if direction(pts[k - 1], pts[k]) != direction(pts[k], pts[(k + 1) % n])]
-        pts = [pts[k] for k in kept]
-        n = len(pts)
-        # the crack that starts at corner k: side s of pixel corner - start[s]; keys order like (y, x, s)
-        keys = []
-        for k in range(n):
-            s = side_of[direction(pts[k], pts[(k + 1) % n])]
-            keys.append((pts[k][1] - start[s][1], pts[k][0] - start[s][0], s))
-        first = keys.index(min(keys))
+        if n >= 3:
+            pts = [pts[k] for k in range(n) if not straight(pts[k - 1], pts[k], pts[(k + 1) % n])]
+            n = len(pts)
+        first = 0
+        if n >= 3:
+            # the crack that starts at corner k: side s of pixel corner - start[s]; keys order like (y, x, s)
+            keys = []
+            for k in range(n):
+                s = side_of(pts[k], pts[(k + 1) % n])
+                keys.append((pts[k][1] - start[s][1], pts[k][0] - start[s][0], s))
+            first = keys.index(min(keys))
         groups[int(loop["group"])].append(np.asarray(pts[first:] + pts[:first], np.int32).reshape(-1, 2))
     return groups
 
@@ -1227,3 +1280,15 @@ def mesh_desc(width, height, group_ids, segments, vertices, loops, refs):
     out += _field(11, _field(1, np.asarray(coord, "<f4").tobytes()))         # vector_mesh.coord, packed
     out += _varint(13 << 3) + _varint(1)                                     # rasterization_removed
     return bytes(out)
+
+
+def simplified_mesh_desc(width, height, group_ids, segments, vertices, loops, refs):
+    """mesh_desc for the host arrays of level_mesh_simplified.  The loops whose polygon has fewer than three
+    distinct vertices are dropped first (the reference drops polygon.size() == 3 && polygon[0] == polygon[2]): a
+    closed segment that came back as one vertex, a loop of collapsed segments.  Then mesh_desc is called with the
+    loops that are left.  For the arrays of level_mesh itself the result is mesh_desc's, byte for byte; for
+    level_mesh_simplified at max_error 0 without a collapse, rasterize() of the same size gives the level's id
+    plane back; at a larger max_error it gives the simplified partition.  Host numpy only."""
+    segments, vertices, loops, refs = (np.asarray(a) for a in (segments, vertices, loops, refs))
+    keep = [len({tuple(p) for p in _loop_points(segments, vertices, loop, refs)}) >= 3 for loop in loops]
+    return mesh_desc(width, height, group_ids, segments, vertices, loops[np.asarray(keep, bool)], refs)

@@ -1,4 +1,5 @@
-// capi_contours.inc -- vsg_render_level_contours and vsg_render_level_mesh, which goes on from the contours' cracks.
+// capi_contours.inc -- vsg_render_level_contours and vsg_render_level_mesh, which goes on from the contours' cracks
+// (and capi_simplify.inc from the mesh).
 // A part of render_capi.cpp.
 namespace {
 
@@ -205,13 +206,25 @@ int vsg_render_level_contours(vsg_render* h, const uint8_t* seg, size_t seg_len,
 
 VSG_RENDER_LAST_STATS(vsg_render_last_contour_stats, vsg_render_contour_stats, cont.stats)
 
-int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
-                          vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments,
-                          int32_t* vertices, size_t capacity_vertices, size_t* num_vertices,
-                          vsg_render_mesh_loop* loops, size_t capacity_loops, size_t* num_loops, int32_t* refs,
-                          size_t capacity_refs, size_t* num_refs, int mem_out) {
-  return Guard([&] {
+}  // extern "C"
+
+namespace {
+
+// What a vsg_render_level_mesh call left on the device for vsg_render_level_mesh_simplified: the four lists
+// and their lengths; segments == 0: no crack.
+struct MeshRun {
+  vsg_render_impl::MeshSegmentSpace t;
+  uint32_t segments, vertices, loops, refs;
+};
+
+// vsg_render_level_mesh; left: null, or what the simplified call goes on with.
+void LevelMesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+               vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments, int32_t* vertices,
+               size_t capacity_vertices, size_t* num_vertices, vsg_render_mesh_loop* loops, size_t capacity_loops,
+               size_t* num_loops, int32_t* refs, size_t capacity_refs, size_t* num_refs, int mem_out, MeshRun* left) {
+  {
     using namespace vsg_render_impl;
+    if (left) std::memset(left, 0, sizeof(*left));
     static_assert(sizeof(vsg_render_mesh_segment) == kMeshSegmentWords * sizeof(int32_t), "moved as int32 words");
     static_assert(sizeof(vsg_render_mesh_loop) == kMeshLoopWords * sizeof(int32_t), "moved as int32 words");
     static_assert(sizeof(vsg_render_mesh_stats) == 104, "documented size");
@@ -352,6 +365,13 @@ int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int
     ms.loops = C;
     ms.refs = R;
     ms.longest_segment_cracks = seen[1].longest;
+    if (left) {
+      left->t = t;
+      left->segments = S;
+      left->vertices = (uint32_t)V;
+      left->loops = C;
+      left->refs = R;
+    }
     if (count_only) return;
     if (!fits || V > capacity_vertices) {
       Throw(VSG_ERR_INVALID, "the level has " + std::to_string(S) + " segments, " + std::to_string(V) + " vertices, " +
@@ -369,6 +389,22 @@ int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int
                      {t.refs, (size_t)R * 4, refs}});
       h->stats.device_allocations = h->allocations;
     }
+  }
+}
+
+}  // namespace
+
+extern "C" {
+
+int vsg_render_level_mesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments,
+                          int32_t* vertices, size_t capacity_vertices, size_t* num_vertices,
+                          vsg_render_mesh_loop* loops, size_t capacity_loops, size_t* num_loops, int32_t* refs,
+                          size_t capacity_refs, size_t* num_refs, int mem_out) {
+  return Guard([&] {
+    LevelMesh(h, seg, seg_len, level, connectedness, segments, capacity_segments, num_segments, vertices,
+              capacity_vertices, num_vertices, loops, capacity_loops, num_loops, refs, capacity_refs, num_refs, mem_out,
+              nullptr);
   });
 }
 

@@ -548,6 +548,63 @@ void LaunchMeshCopy(const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_l
                     uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
                     int32_t* refs_out, const MeshStatus* status, hipStream_t stream);
 
+// ---- mesh simplification (simplify.hip): Douglas-Peucker on the segments of the level mesh ----------------
+
+constexpr int kSimplifyWavePoints = 256;    // the most corners of a segment a wavefront takes
+constexpr int kSimplifyLdsPoints = 2048;    // the most corners whose state a workgroup keeps in LDS
+
+enum SimplifyFlag {
+  SIMPLIFY_FLAG_RANGE = 1,   // a segment, a vertex or a count was out of range
+};
+
+// Written by the simplification kernels; read by the host at the end of a call.
+struct SimplifyStatus {
+  uint32_t vertices_out;     // after the joint pass
+  uint32_t vertices_kept;    // after the recursion
+  uint32_t collapsed, single_closed, max_rounds, longest_in;
+  uint32_t long_segments;    // segments of more than kSimplifyWavePoints corners
+  uint32_t flags;
+};
+
+// The mesh's records and vertices (n_segments, slots - n_segments) and the stage's blocks.  A segment of c
+// vertices keeps at most c + 1: segment s has the c + 1 slots from first_vertex + s on, of `slots` in all.
+// Per slot: kept, kseg (the slot's segment, all ones where nothing was kept), lo, hi and two words of best (the
+// state of a segment of more than kSimplifyLdsPoints corners).  Per segment: kcount (vertices kept), rounds,
+// sflag (1: collapsed), long_list.
+struct SimplifyView {
+  const int32_t* segments;
+  const int2* vertices;
+  uint32_t n_segments, slots;
+  double eps;                // (double)max_error, squared
+  uint32_t threshold;        // an open segment of fewer lattice points collapses; 0: none does
+  int2* kept;
+  uint32_t* kseg;
+  uint32_t* lo;
+  uint32_t* hi;
+  unsigned long long* best;
+  uint32_t* kcount;
+  uint32_t* rounds;
+  uint32_t* sflag;
+  uint32_t* long_list;
+};
+
+// Work space of the scan over `segments` counts.
+size_t SimplifyTempBytes(int64_t segments);
+// The collapse rule, the sweeps and the rounds of every segment; kept, kseg, kcount, rounds, sflag.  3 launches:
+// the clear of kseg, the wavefronts, the workgroups of the long segments.  status: cleared by the caller.
+hipError_t SimplifyDp(const SimplifyView& m, SimplifyStatus* status, hipStream_t stream);
+// The joint pass of every segment, in place in `kept`; ncount[s] = its new number of vertices.  1 launch.
+hipError_t SimplifyClean(const SimplifyView& m, uint32_t* ncount, hipStream_t stream);
+// nfirst = the scan of ncount, the vertices to their places, the records (n_segments of kMeshSegmentWords) and
+// the counts of status.  3 launches, the scan counted as one.
+hipError_t SimplifyTables(void* temp, size_t temp_bytes, const SimplifyView& m, const uint32_t* ncount, uint32_t* nfirst,
+                          int32_t* segments_out, int32_t* vertices_out, SimplifyStatus* status, hipStream_t stream);
+// Copies the four lists, or nothing when the vertices do not fit or a flag is up.
+void LaunchSimplifyCopy(const int32_t* segments, const int32_t* vertices, const int32_t* loops, const int32_t* refs,
+                        uint32_t n_segments, uint32_t n_loops, uint32_t n_refs, uint32_t slots,
+                        uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
+                        int32_t* refs_out, const SimplifyStatus* status, hipStream_t stream);
+
 // ---- boundary distance (distance.hip): the squared distance to an edge set, the boundary benchmark ------
 
 constexpr int kDistChunkRows = 32;        // rows of a column that one word of the edge set holds

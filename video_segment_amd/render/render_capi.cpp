@@ -18,6 +18,7 @@
 //   capi_persistence.inc   vsg_render_persistence_image, _frame, _graph
 //   capi_colors.inc        vsg_render_level_colors, vsg_render_mean_frame
 //   capi_contours.inc      vsg_render_level_contours, vsg_render_level_mesh
+//   capi_simplify.inc      vsg_render_level_mesh_simplified
 //   capi_distance.inc      vsg_render_boundary_distance, vsg_render_boundary_benchmark
 #include <algorithm>
 #include <chrono>
@@ -44,4 +45,5 @@
 #include "capi_persistence.inc"
 #include "capi_colors.inc"
 #include "capi_contours.inc"
+#include "capi_simplify.inc"
 #include "capi_distance.inc"

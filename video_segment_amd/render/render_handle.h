@@ -17,6 +17,7 @@ using vsg_render_impl::LevelStatus;
 using vsg_render_impl::MeshStatus;
 using vsg_render_impl::OvlStatus;
 using vsg_render_impl::PersStatus;
+using vsg_render_impl::SimplifyStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
 
@@ -33,6 +34,7 @@ enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
 enum ContourStage { CNT_CLASSIFY = 0, CNT_TRACE, CNT_TABLE, CNT_STAGES };
 enum MeshStage { MSH_SPLIT = 0, MSH_TABLE, MSH_STAGES };
+enum SimplifyStage { SMP_DP = 0, SMP_CLEAN, SMP_TABLE, SMP_STAGES };
 // DST_PLANE: the upload of a host label plane
 enum DistStage { DST_PLANE = 0, DST_CLASSIFY, DST_COLUMNS, DST_ROWS, DST_MATCH, DST_STAGES };
 
@@ -167,6 +169,17 @@ struct MeshState {
   void Init() { InitFamily(this, MSH_STAGES); }
 };
 
+// mesh simplification: what there is per slot (the kept vertices and their segments, the state of the long
+// segments' rounds) and per segment (kept and new counts, new offsets, rounds, the collapse marks, the list of
+// long segments); the new records and vertices; the status words and the pinned block the status and host
+// outputs come back through
+struct SimplifyState {
+  StageClock clock;
+  Block work, lists, status, seen;
+  vsg_render_simplify_stats stats;
+  void Init() { InitFamily(this, SMP_STAGES); }
+};
+
 // The number of bits of a sort key's field that holds values up to `value`: at least 1, at most `limit`.
 int BitsFor(uint64_t value, int limit) {
   int bits = 1;
@@ -206,6 +219,7 @@ struct vsg_render {
   ContourState cont;
   DistanceState dist;
   MeshState mesh;
+  SimplifyState simp;
 
   ~vsg_render() {
     if (!stream) return;
