@@ -62,7 +62,9 @@
  * image; the quotients (precision, recall, F) are left to the caller.
  * Appearance descriptors (Lab histograms, the hierarchical stage's) are not offered; the exact colour sums
  * of every group of a level and the mean-colour picture are: vsg_render_level_colors and
- * vsg_render_mean_frame.
+ * vsg_render_mean_frame.  All of the above is per frame; what a region id sums up to over the frames of a video
+ * (life span, volume, trajectory, colour sums, overlap with ground-truth labels: the inputs of the 3-D
+ * supervoxel scores) is accumulated on the device by a volume session: vsg_render_volume_begin, _add, _table.
  *
  * A well-formed SegmentationDesc rasterizes a partition of the frame: scan intervals do not
  * overlap.  Where they do, which region a pixel shows is unspecified (the reference paints in
@@ -673,6 +675,113 @@ typedef struct vsg_render_color_stats {
   int launches;
 } vsg_render_color_stats;                 /* 56 bytes with the tail padding */
 int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s);
+
+/* ---- Volume session: a level's supervoxels accumulated over frames ----
+ *
+ * One row of the volume table, as vsg_render_volume_table returns it: a region id of the session's level, that
+ * is a supervoxel, over every frame added so far. */
+typedef struct vsg_render_volume_row {    /* 152 bytes, no padding */
+  int32_t id, first_frame, last_frame, frames;   /* the smallest and the largest `frame` in which it painted a
+                                                    pixel, and the number of adds in which it did */
+  int32_t min_x, min_y, max_x, max_y;            /* bounding box over all frames, inclusive */
+  int32_t first_pair, num_pairs, best_label, reserved0;   /* its slice of the pairs; the label with the largest
+                                                    count, ties: the smallest label, -1 when num_pairs == 0;
+                                                    reserved0 is written as 0 */
+  int64_t volume, unlabelled, best_count;        /* voxels; of those, voxels where B is negative; the count of
+                                                    best_label, 0 when num_pairs == 0 */
+  int64_t sum_x, sum_y, sum_t;                   /* over its voxels, with t = `frame` */
+  int64_t sum[3], sum_sq[3];                     /* B, G, R over its voxels, and the squares of the same bytes */
+  uint8_t min[3], max[3], reserved1[2];          /* reserved1 is written as 0 */
+} vsg_render_volume_row;
+
+/* One column of the volume table: a label of the `other` planes. */
+typedef struct vsg_render_volume_col {    /* 48 bytes, no padding */
+  int32_t label, num_pairs, best_row, first_frame, last_frame, frames;   /* best_row: index in the row list of
+                                                    the supervoxel with the largest count; ties: the smallest
+                                                    index; -1 when num_pairs == 0 */
+  int64_t volume, uncovered, best_count;         /* voxels with that label; of those, voxels where P is -1 */
+} vsg_render_volume_col;
+
+/* One non-empty cell of the volume table. */
+typedef struct vsg_render_volume_pair {   /* 24 bytes, no padding */
+  int32_t row, col, label, frames;        /* indices into the two lists; cols[col].label; the number of adds in
+                                             which the two shared a pixel */
+  int64_t count;                          /* voxels with P = the row's id and B = label; > 0 */
+} vsg_render_volume_pair;
+
+/* What the volume session of the handle holds and what its last calls did.  frames, rows, cols, pairs: of the
+ * session.  new_rows, new_cols, new_pairs: keys the last add brought; resorts: the tables (0 to 3) it sorted
+ * again because of them.  covered, labelled, both: voxels with P >= 0, with B >= 0 and with both, over the
+ * session (labelled and both are 0 without with_labels).  Device times are HIP events: frame_us, the internal
+ * per-frame stages of the last add (the stages of the internal vsg_render_level_overlap and
+ * vsg_render_level_colors calls, or of the level's interval list alone); geometry_us, k_volume_geometry;
+ * merge_us, the three merge kernels; sort_us, the radix sorts and gathers of the re-sorted tables (0 when the
+ * add brought no key; the wait for the status words between the merge and the sorts is in no stage); table_us,
+ * everything the last vsg_render_volume_table call ran.  launches: of the last add, the internal calls'
+ * included; it does not depend on H, on the number of groups or on the frames added so far, only on which
+ * tables had to be sorted again. */
+typedef struct vsg_render_volume_stats {
+  int64_t frames, rows, cols, pairs;
+  int64_t new_rows, new_cols, new_pairs, resorts;
+  int64_t covered, labelled, both;
+  float frame_us, geometry_us, merge_us, sort_us, table_us;
+  int launches;
+} vsg_render_volume_stats;                /* 112 bytes */
+
+/* A volume session is a device-resident table that every added frame is merged into and that can be read out at
+ * any time: how long a supervoxel lives, its volume, its trajectory, its colour sums and its overlap with the
+ * labels of a ground truth, without a per-frame table leaving the device.  Everything in it is an integer.
+ *
+ * The groups are the regions of one hierarchy level, keyed by region id.  Connected components are not offered
+ * as groups: their indices mean nothing across frames.
+ *
+ * vsg_render_volume_begin starts, or restarts and empties, the session and fixes `level` (>= 0) and the two
+ * flags (0 or 1) for all of it.  A null handle, a negative level or a flag other than 0 and 1 is
+ * VSG_ERR_INVALID, answered before the handle is dereferenced; the call touches no device.
+ *
+ * vsg_render_volume_add adds one frame.  `frame` >= 0 is the caller's frame index, in any order; adding an
+ * index twice counts it twice (unchecked).  Decode, hierarchy rules (the desc's own hierarchy replaces the kept
+ * one, so a chunk's later frames use the hierarchy its first frame brought), level refusals, the non-negative
+ * ids and the handling of vector-only descs are those of vsg_render_level_regions; the level is checked by the
+ * add.  bgr, stride and mem_in are those of vsg_render_level_colors: required with with_colors, not looked at
+ * without.  other, other_pitch and mem_other are those of vsg_render_level_overlap: required with with_labels,
+ * not looked at without.  Without a session the call returns VSG_ERR_STATE.  A null handle or a negative frame
+ * is VSG_ERR_INVALID, answered before the handle is dereferenced; a required plane that is null and an unknown
+ * memory kind of a required plane are VSG_ERR_INVALID too, answered once the session's flags are read, and
+ * touch no device; stride and pitch are compared with the handle's width.  A failed add leaves the session as
+ * it was before the call: the per-frame stages run, and are checked, before anything is merged.  The one exception
+ * is a failure of the device or of an allocation once the merge has begun (VSG_ERR_DEVICE, VSG_ERR_INTERNAL): it
+ * ends the session, every later add or table call returns VSG_ERR_STATE until the next vsg_render_volume_begin.
+ * The per-frame stages are internal calls: with with_labels vsg_render_level_overlap (connectedness 0), with
+ * with_colors vsg_render_level_colors (connectedness 0); they overwrite vsg_render_last_overlap_stats and
+ * vsg_render_last_color_stats, and every add overwrites vsg_render_last_stats.  Other calls on the handle
+ * between two adds do not disturb the session.
+ *
+ * vsg_render_volume_table may be called at any time of a session and does not end it (VSG_ERR_STATE without
+ * one).  Rows.  One row per region id that painted at least one pixel in any added frame, ascending by id.
+ * Cols.  One column per distinct non-negative value of any added `other`, ascending by label.  Pairs.  One pair
+ * per (id, label) with a common voxel, grouped by row in row order and within a row by ascending label.
+ * first_pair of a row without a pair is the number of pairs of the rows before it.
+ * Without with_labels: unlabelled = 0, best_label = -1, best_count = 0, first_pair = num_pairs = 0, and there
+ * are no cols and no pairs.  Without with_colors: the colour fields are 0.
+ * volume - unlabelled is the sum of the counts of the row's pairs, volume - uncovered the sum of the counts of
+ * the column's pairs.  The table equals the field-wise sum (minimum and maximum for the extrema) over the added
+ * frames of what vsg_render_level_regions, vsg_render_level_colors and vsg_render_level_overlap
+ * (connectedness 0) return for each frame.
+ * *num_rows, *num_cols and *num_pairs are always set on VSG_OK and when a capacity is too small; in that case
+ * the call fails with VSG_ERR_INVALID and no output is touched.  All three outputs NULL with all three
+ * capacities 0 asks for the counts only.  A null handle, a null count pointer or an unknown mem_out is
+ * VSG_ERR_INVALID, answered before the handle is dereferenced.  All three lists in mem_out memory. */
+int vsg_render_volume_begin(vsg_render* h, int level, int with_colors, int with_labels);
+int vsg_render_volume_add(vsg_render* h, const uint8_t* seg, size_t seg_len, int frame,
+                          const uint8_t* bgr, size_t stride, int mem_in,
+                          const int32_t* other, size_t other_pitch, int mem_other);
+int vsg_render_volume_table(vsg_render* h,
+                            vsg_render_volume_row* rows, size_t capacity_rows, size_t* num_rows,
+                            vsg_render_volume_col* cols, size_t capacity_cols, size_t* num_cols,
+                            vsg_render_volume_pair* pairs, size_t capacity_pairs, size_t* num_pairs,
+                            int mem_out);
+int vsg_render_last_volume_stats(vsg_render* h, vsg_render_volume_stats* s);
 
 /* ---- Level contours: the traced closed outlines of every group of a level ----
  *

@@ -80,6 +80,14 @@
 // boundary_gt_edges=<sum> boundary_gt_matched=<sum> boundary_benchmark_fnv1a32=<hash of every compared
 // frame's records>.
 //
+//   --volume_level <level> [--volume_out FILE]
+// gives the SegmentationRenderUnit a volume session at that hierarchy level (--render_level 0 is implied when no
+// render level was given): every rendered frame is accumulated on the device, and after the last frame one line
+// volume_level=<level> volume_frames=<adds> volume_supervoxels=<rows> volume_voxels=<sum of the volumes>
+// volume_fnv1a32=<hash of the rows' bytes> is printed, and one text line per supervoxel,
+// "id first_frame last_frame frames volume min_x min_y max_x max_y sum_x sum_y sum_t sum_b sum_g sum_r",
+// is written to FILE (to stdout, each line beginning with "supervoxel ", without --volume_out).
+//
 //   --write_to_file --remove_rasterization [--original_width W --original_height H]
 // writes vector-only descs as seg_tree_sample does (seg_tree.cpp:308), scaled to the video's original
 // size where the source says it was downscaled; a render unit in the same run is then put behind the
@@ -1130,6 +1138,9 @@ struct Flags {
   // vsg_render_boundary_benchmark with this tolerance_sq for every frame after the first, against the
   // previous frame's level-0 id image; < 0: off
   int boundary_benchmark = -1;
+  // SegmentationRenderUnitOptions::volume_level; < 0: off.  The supervoxel lines go to volume_out, or to stdout
+  int volume_level = -1;
+  std::string volume_out;
   // SegmentationWriterUnitOptions::remove_rasterization (seg_tree.cpp:308 sets it for --write_to_file;
   // here it is opt-in, so that the files of existing runs stay what they were)
   bool remove_rasterization = false;
@@ -1226,6 +1237,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_contours") f->level_contours = atoi(v.c_str());
     else if (a == "boundary_distance") f->boundary_distance = atoi(v.c_str());
     else if (a == "boundary_benchmark") f->boundary_benchmark = atoi(v.c_str());
+    else if (a == "volume_level") f->volume_level = atoi(v.c_str());
+    else if (a == "volume_out") f->volume_out = v;
     else if (a == "contours_components") f->contours_components = bv;
     else if (a == "level_mesh") f->level_mesh = atoi(v.c_str());
     else if (a == "mesh_components") f->mesh_components = bv;
@@ -1271,6 +1284,11 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     std::fprintf(stderr, "--mesh_max_error has to be a finite number >= 0\n");
     return false;
   }
+  if (!f->volume_out.empty() && f->volume_level < 0) {
+    std::fprintf(stderr, "--volume_out needs --volume_level\n");
+    return false;
+  }
+  if (f->volume_level >= 0 && f->render_level < 0) f->render_level = 0;   // the session lives in the render unit
   if (f->mesh_min_segment_points < 0) {
     std::fprintf(stderr, "--mesh_min_segment_points has to be >= 0\n");
     return false;
@@ -1537,6 +1555,7 @@ int main(int argc, char** argv) {
     render_options.concat_with_source = FLAGS.render_concat;
     render_options.blend_alpha = (float)FLAGS.render_blend_alpha;
     render_options.device = FLAGS.device;
+    render_options.volume_level = FLAGS.volume_level;
     render_unit.reset(new SegmentationRenderUnit(render_options));
     render_unit->AttachTo(input);
     render_sink.AttachTo(render_unit.get());
@@ -1570,6 +1589,34 @@ int main(int argc, char** argv) {
   if (render_unit) {
     std::printf("render_frames=%d render_fnv1a32=%08x render_level=%d\n", render_sink.frames(), render_sink.hash(),
                 render_unit->hierarchy_level());
+  }
+  if (render_unit && FLAGS.volume_level >= 0) {
+    std::vector<vsg_render_volume_row> rows;
+    std::vector<vsg_render_volume_col> cols;
+    std::vector<vsg_render_volume_pair> pairs;
+    if (!render_unit->VolumeTable(&rows, &cols, &pairs)) {
+      std::fprintf(stderr, "ERROR: could not read the volume table: %s\n", vsg_render_last_error());
+      return 1;
+    }
+    uint32_t hash = 2166136261u;
+    const unsigned char* bytes = reinterpret_cast<const unsigned char*>(rows.data());
+    for (size_t k = 0; k < rows.size() * sizeof(vsg_render_volume_row); ++k) hash = (hash ^ bytes[k]) * 16777619u;
+    long long voxels = 0;
+    for (const vsg_render_volume_row& r : rows) voxels += r.volume;
+    std::printf("volume_level=%d volume_frames=%d volume_supervoxels=%zu volume_voxels=%lld volume_fnv1a32=%08x\n",
+                FLAGS.volume_level, render_sink.frames(), rows.size(), voxels, hash);
+    FILE* out = FLAGS.volume_out.empty() ? stdout : std::fopen(FLAGS.volume_out.c_str(), "w");
+    if (!out) {
+      std::fprintf(stderr, "ERROR: could not open %s\n", FLAGS.volume_out.c_str());
+      return 1;
+    }
+    for (const vsg_render_volume_row& r : rows) {
+      std::fprintf(out, "%s%d %d %d %d %lld %d %d %d %d %lld %lld %lld %lld %lld %lld\n",
+                   FLAGS.volume_out.empty() ? "supervoxel " : "", r.id, r.first_frame, r.last_frame, r.frames,
+                   (long long)r.volume, r.min_x, r.min_y, r.max_x, r.max_y, (long long)r.sum_x, (long long)r.sum_y,
+                   (long long)r.sum_t, (long long)r.sum[0], (long long)r.sum[1], (long long)r.sum[2]);
+    }
+    if (out != stdout) std::fclose(out);
   }
   if (level_sink) {
     std::printf("level_regions=%ld level_intervals=%ld level_fnv1a32=%08x\n", level_sink->regions(),

@@ -73,6 +73,11 @@ bool SegmentationRenderUnit::OpenStreams(StreamSet* set) {
     std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
     return false;
   }
+  if (options_.volume_level >= 0 &&
+      vsg_render_volume_begin(render_, options_.volume_level, vid_stream_idx_ >= 0 ? 1 : 0, 0) != VSG_OK) {
+    std::fprintf(stderr, "ERROR: could not begin the volume session: %s\n", vsg_render_last_error());
+    return false;
+  }
   return true;
 }
 
@@ -94,6 +99,11 @@ void SegmentationRenderUnit::ProcessFrame(FrameSetPtr input, std::list<FrameSetP
                             stride, VSG_MEM_HOST, render_frame->mutable_data(), (size_t)frame_width_step_,
                             VSG_MEM_HOST) == VSG_OK,
            vsg_render_last_error());
+  if (options_.volume_level >= 0) {   // after the render: a desc without a hierarchy uses the kept one
+    VF_CHECK(vsg_render_volume_add(render_, reinterpret_cast<const uint8_t*>(desc.wire.data()), desc.wire.size(),
+                                   frame_number_, bgr, stride, VSG_MEM_HOST, nullptr, 0, VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+  }
   input->push_back(render_frame);
   output->push_back(input);
   ++frame_number_;
@@ -103,6 +113,22 @@ int SegmentationRenderUnit::hierarchy_level() const {
   int level = -1;
   if (!render_ || vsg_render_level(render_, &level) != VSG_OK) return -1;
   return level;
+}
+
+bool SegmentationRenderUnit::VolumeTable(std::vector<vsg_render_volume_row>* rows,
+                                         std::vector<vsg_render_volume_col>* cols,
+                                         std::vector<vsg_render_volume_pair>* pairs) const {
+  if (!render_ || options_.volume_level < 0) return false;
+  size_t nr = 0, nc = 0, np = 0;
+  if (vsg_render_volume_table(render_, nullptr, 0, &nr, nullptr, 0, &nc, nullptr, 0, &np, VSG_MEM_HOST) != VSG_OK) {
+    return false;
+  }
+  rows->resize(nr);
+  cols->resize(nc);
+  pairs->resize(np);
+  if (nr + nc + np == 0) return true;
+  return vsg_render_volume_table(render_, rows->data(), nr, &nr, cols->data(), nc, &nc, pairs->data(), np, &np,
+                                 VSG_MEM_HOST) == VSG_OK;
 }
 
 }  // namespace segmentation

@@ -10,6 +10,7 @@
 
 #include <list>
 #include <string>
+#include <vector>
 
 #include "../../include/vsg_render.h"
 #include "segmentation_unit.h"
@@ -30,6 +31,10 @@ struct SegmentationRenderUnitOptions {
   bool draw_shape_descriptors = false;   // not offered: OpenStreams fails when set
   bool concat_with_source = false;
   int device = -1;                       // HIP device ordinal (-1: current)
+  // Not in the reference.  >= 0: a volume session (vsg_render_volume_begin) at this hierarchy level accumulates
+  // every frame the unit renders, with the colour sums when there is a video stream and without labels; the
+  // frame index is the unit's frame number.  < 0: none.
+  int volume_level = -1;
 };
 
 class SegmentationRenderUnit : public VideoUnit {
@@ -42,6 +47,11 @@ class SegmentationRenderUnit : public VideoUnit {
 
   // The level resolved on the first frame (-1 before it).
   int hierarchy_level() const;
+
+  // The table of the volume session over the frames rendered so far (options.volume_level >= 0): one row per
+  // supervoxel; cols and pairs stay empty, the session has no labels.  false without a session or on a failure.
+  bool VolumeTable(std::vector<vsg_render_volume_row>* rows, std::vector<vsg_render_volume_col>* cols,
+                   std::vector<vsg_render_volume_pair>* pairs) const;
 
  private:
   SegmentationRenderUnitOptions options_;

@@ -110,6 +110,17 @@ class VsgRenderColorStats(_capi.Structure):
     ]
 
 
+class VsgRenderVolumeStats(_capi.Structure):
+    _fields_ = [
+        ("frames", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("pairs", C.c_int64),
+        ("new_rows", C.c_int64), ("new_cols", C.c_int64), ("new_pairs", C.c_int64), ("resorts", C.c_int64),
+        ("covered", C.c_int64), ("labelled", C.c_int64), ("both", C.c_int64),
+        ("frame_us", C.c_float), ("geometry_us", C.c_float), ("merge_us", C.c_float), ("sort_us", C.c_float),
+        ("table_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 class VsgRenderContourStats(_capi.Structure):
     _fields_ = [
         ("cracks", C.c_int64), ("vertices", C.c_int64), ("contours", C.c_int64), ("holes", C.c_int64),
@@ -232,6 +243,35 @@ LEVEL_COLOR_DTYPE = np.dtype([
 assert LEVEL_COLOR_DTYPE.itemsize == 72
 LEVEL_COLOR_WORDS = 18
 
+# vsg_render_volume_row: 152 bytes, no padding
+VOLUME_ROW_DTYPE = np.dtype([
+    ("id", np.int32), ("first_frame", np.int32), ("last_frame", np.int32), ("frames", np.int32),
+    ("min_x", np.int32), ("min_y", np.int32), ("max_x", np.int32), ("max_y", np.int32),
+    ("first_pair", np.int32), ("num_pairs", np.int32), ("best_label", np.int32), ("reserved0", np.int32),
+    ("volume", np.int64), ("unlabelled", np.int64), ("best_count", np.int64),
+    ("sum_x", np.int64), ("sum_y", np.int64), ("sum_t", np.int64),
+    ("sum", np.int64, (3,)), ("sum_sq", np.int64, (3,)),
+    ("min", np.uint8, (3,)), ("max", np.uint8, (3,)), ("reserved1", np.uint8, (2,)),
+])
+assert VOLUME_ROW_DTYPE.itemsize == 152
+VOLUME_ROW_WORDS = 38
+
+# vsg_render_volume_col: 48 bytes, no padding
+VOLUME_COL_DTYPE = np.dtype([
+    ("label", np.int32), ("num_pairs", np.int32), ("best_row", np.int32),
+    ("first_frame", np.int32), ("last_frame", np.int32), ("frames", np.int32),
+    ("volume", np.int64), ("uncovered", np.int64), ("best_count", np.int64),
+])
+assert VOLUME_COL_DTYPE.itemsize == 48
+VOLUME_COL_WORDS = 12
+
+# vsg_render_volume_pair: 24 bytes, no padding
+VOLUME_PAIR_DTYPE = np.dtype([
+    ("row", np.int32), ("col", np.int32), ("label", np.int32), ("frames", np.int32), ("count", np.int64),
+])
+assert VOLUME_PAIR_DTYPE.itemsize == 24
+VOLUME_PAIR_WORDS = 6
+
 # vsg_render_level_contour: 48 bytes, no padding
 LEVEL_CONTOUR_DTYPE = np.dtype([
     ("id", np.int32), ("component", np.int32), ("group", np.int32),
@@ -286,6 +326,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_persistence_image", "vsg_render_persistence_frame", "vsg_render_persistence_graph",
     "vsg_render_last_persistence_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
+    "vsg_render_volume_begin", "vsg_render_volume_add", "vsg_render_volume_table", "vsg_render_last_volume_stats",
     "vsg_render_level_contours", "vsg_render_last_contour_stats",
     "vsg_render_level_mesh", "vsg_render_last_mesh_stats",
     "vsg_render_level_mesh_simplified", "vsg_render_last_simplify_stats",
@@ -353,6 +394,12 @@ def lib():
     L.vsg_render_mean_frame.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp,
                                         C.c_size_t, C.c_int]
     L.vsg_render_last_color_stats.argtypes = [vp, C.POINTER(VsgRenderColorStats)]
+    L.vsg_render_volume_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
+    L.vsg_render_volume_add.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t,
+                                        C.c_int]
+    L.vsg_render_volume_table.argtypes = [vp, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.c_size_t,
+                                          C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_last_volume_stats.argtypes = [vp, C.POINTER(VsgRenderVolumeStats)]
     L.vsg_render_level_contours.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t,
                                             C.POINTER(C.c_size_t), vp, C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_contour_stats.argtypes = [vp, C.POINTER(VsgRenderContourStats)]
@@ -914,6 +961,75 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_color_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def volume_begin(self, level=0, colors=False, labels=False):
+        """Starts, or restarts and empties, the renderer's volume session: the table of the supervoxels (region ids)
+        of hierarchy level `level` that volume_add merges every frame into on the device.  colors: every add
+        brings the BGR24 frame and the rows carry the colour sums; labels: every add brings a label plane and
+        the table has columns and pairs."""
+        check(lib().vsg_render_volume_begin(self.h, int(level), int(bool(colors)), int(bool(labels))))
+
+    def volume_add(self, seg_bytes, frame, bgr=None, other=None):
+        """Adds the desc of frame index `frame` (>= 0, in any order; an index added twice counts twice) to the
+        volume session.  bgr: the H x W x 3 uint8 frame as in level_colors, needed with colors; other: the
+        H x W int32 label plane as in level_overlap, needed with labels.  Either is ignored when the session
+        does not ask for it.  A failed add leaves the session as it was."""
+        seg_bytes = bytes(seg_bytes)
+        p_bgr, stride, mem_in = None, 0, VSG_MEM_HOST
+        if bgr is not None:
+            p_bgr, stride, mem_in = _frame_ptr(bgr, self.H, self.W, "bgr")
+        po, pitch, mem_other = None, 0, VSG_MEM_HOST
+        if other is not None:
+            po, pitch, mem_other = self._other_ptr(other)
+        check(lib().vsg_render_volume_add(self.h, seg_bytes, len(seg_bytes), int(frame), p_bgr, stride, mem_in, po,
+                                          pitch, mem_other))
+
+    def volume_table(self, rows_out=None, cols_out=None, pairs_out=None):
+        """The volume session's table so far: (rows, cols, pairs).  rows: a VOLUME_ROW_DTYPE array, one per region
+        id that painted a pixel in any added frame, ascending by id, with its life span, box, volume, sums of x,
+        y and t, colour sums, its slice of `pairs` and the label it overlaps most; cols: a VOLUME_COL_DTYPE
+        array, one per label by ascending label; pairs: a VOLUME_PAIR_DTYPE array, one per (id, label) with a
+        common voxel, grouped by row, within a row by ascending label.  The session goes on.  Without outputs
+        the arrays are allocated exactly.  rows_out / cols_out / pairs_out (all or none): buffers to fill
+        instead, all numpy (arrays of the three dtypes) or all torch CUDA tensors ((capacity, 38), (capacity, 12)
+        and (capacity, 6) int32); the filled parts of them are returned."""
+        nr, nc, npairs = C.c_size_t(), C.c_size_t(), C.c_size_t()
+        outs = (rows_out, cols_out, pairs_out)
+        if any(o is None for o in outs) and not all(o is None for o in outs):
+            raise ValueError("pass all three outputs or none")
+        if rows_out is None:
+            check(lib().vsg_render_volume_table(self.h, None, 0, C.byref(nr), None, 0, C.byref(nc), None, 0,
+                                                C.byref(npairs), VSG_MEM_HOST))
+            rows_out = np.empty(nr.value, VOLUME_ROW_DTYPE)
+            cols_out = np.empty(nc.value, VOLUME_COL_DTYPE)
+            pairs_out = np.empty(npairs.value, VOLUME_PAIR_DTYPE)
+            if nr.value == 0 and nc.value == 0:
+                return rows_out, cols_out, pairs_out
+        outs = (rows_out, cols_out, pairs_out)
+        if len({_capi.is_torch(o) for o in outs}) != 1:
+            raise ValueError("all outputs have to be numpy arrays or all torch tensors")
+        specs = (("rows_out", VOLUME_ROW_DTYPE, VOLUME_ROW_WORDS), ("cols_out", VOLUME_COL_DTYPE, VOLUME_COL_WORDS),
+                 ("pairs_out", VOLUME_PAIR_DTYPE, VOLUME_PAIR_WORDS))
+        for o, (name, dtype, words) in zip(outs, specs):
+            if _capi.is_torch(o):
+                if o.dim() != 2 or o.shape[1] != words or str(o.dtype) != "torch.int32":
+                    raise ValueError("%s has to be (capacity, %d) int32" % (name, words))
+            elif o.dtype != dtype or o.ndim != 1:
+                raise ValueError("%s has to be a one-dimensional array of its dtype" % name)
+        ptrs = [_capi.contiguous_ptr(o) for o in outs]
+        if len({mem for _, mem in ptrs}) != 1:
+            raise ValueError("all outputs have to be in the same kind of memory")
+        check(lib().vsg_render_volume_table(self.h, ptrs[0][0], rows_out.shape[0], C.byref(nr), ptrs[1][0],
+                                            cols_out.shape[0], C.byref(nc), ptrs[2][0], pairs_out.shape[0],
+                                            C.byref(npairs), ptrs[0][1]))
+        return rows_out[:nr.value], cols_out[:nc.value], pairs_out[:npairs.value]
+
+    def last_volume_stats(self):
+        """vsg_render_last_volume_stats: the volume session's totals and what its last add and table call did, as
+        a dict."""
+        s = VsgRenderVolumeStats()
+        check(lib().vsg_render_last_volume_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def level_contours(self, seg_bytes, level=0, connectedness=0, contours_out=None, vertices_out=None):
         """The closed outlines of every region of hierarchy level `level` (connectedness 0) or of every connected
         component of its regions (N4 or N8), traced along the pixel sides: (contours, vertices).  contours: a
@@ -1132,6 +1248,46 @@ def overlap_scores(rows, pairs):
     ue_sum = int(np.minimum(count, inside - count).sum())
     return {"n": n, "asa_sum": asa_sum, "ue_sum": ue_sum,
             "asa": asa_sum / n if n else None, "ue": ue_sum / n if n else None}
+
+
+def volume_scores(rows, cols, pairs):
+    """The scores supervoxel benchmarks report, from the host arrays of volume_table, as Python floats (None
+    where the denominator is 0), with N = the sum of pairs.count (the voxels both covered and labelled):
+    ue_3d, the 3-D undersegmentation error (Neubert-Protzel): the sum over the pairs of
+    min(count, (row.volume - row.unlabelled) - count), over N;
+    sa_3d, the 3-D segmentation accuracy: the mean over the columns with a pair of (the sum of the counts of its
+    pairs whose row has that column's label as best_label) / (col.volume - col.uncovered);
+    mean_duration: the mean over the rows of `frames`;
+    explained_variation: the mean over the three channels of
+    sum over rows of volume * (row mean - global mean)^2 / sum over voxels of (value - global mean)^2, from the
+    colour sums (None for a session without colours or without variance).
+    The integers n, ue_sum and supervoxels are returned as well.  Host numpy only."""
+    rows, cols, pairs = np.asarray(rows), np.asarray(cols), np.asarray(pairs)
+    count = pairs["count"].astype(np.int64)
+    n = int(count.sum())
+    inside = (rows["volume"] - rows["unlabelled"]).astype(np.int64)[pairs["row"]] if len(pairs) else count
+    ue_sum = int(np.minimum(count, inside - count).sum())
+    sa = None
+    if len(pairs):
+        right = rows["best_label"][pairs["row"]] == pairs["label"]
+        hit = np.bincount(pairs["col"][right], weights=count[right].astype(np.float64), minlength=len(cols))
+        covered = (cols["volume"] - cols["uncovered"]).astype(np.float64)
+        with_pair = covered > 0
+        sa = float(np.mean(hit[with_pair] / covered[with_pair])) if with_pair.any() else None
+    ev = None
+    volume = rows["volume"].astype(np.float64)
+    total = float(volume.sum())
+    if total > 0 and rows["sum_sq"].any():
+        s1 = rows["sum"].astype(np.float64)
+        mean = s1.sum(axis=0) / total
+        between = (s1 * s1 / volume[:, None]).sum(axis=0) - total * mean * mean
+        whole = rows["sum_sq"].astype(np.float64).sum(axis=0) - total * mean * mean
+        ok = whole > 0
+        ev = float(np.mean(between[ok] / whole[ok])) if ok.any() else None
+    return {"n": n, "ue_sum": ue_sum, "supervoxels": int(len(rows)),
+            "ue_3d": ue_sum / n if n else None, "sa_3d": sa,
+            "mean_duration": float(rows["frames"].mean()) if len(rows) else None,
+            "explained_variation": ev}
 
 
 def boundary_scores(scores):

@@ -2,10 +2,11 @@
 namespace {
 
 // vsg_render_level_colors (picture == nullptr) and vsg_render_mean_frame (colors == nullptr) behind their
-// argument checks that need no handle.
+// argument checks that need no handle.  keep (vsg_render_volume_add; connectedness 0, no outputs): the records
+// are written to h->color.records all the same, and *keep receives the front half, whose lists stay in h->lvl.
 void LevelColors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness, const uint8_t* bgr,
                  size_t stride, int mem_in, vsg_render_level_color* colors, size_t capacity_colors, size_t* num_colors,
-                 uint8_t* picture, size_t out_stride, int mem_out) {
+                 uint8_t* picture, size_t out_stride, int mem_out, LevelFront* keep = nullptr) {
   using namespace vsg_render_impl;
   static_assert(sizeof(vsg_render_level_color) == kLevelColorWords * sizeof(int32_t), "moved as int32 words");
   static_assert(sizeof(vsg_render_color_stats) == 56, "as the header says");
@@ -42,6 +43,7 @@ void LevelColors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, i
     table_words = kLevelRegionWords;
     d_count = &f.status->regions;
     cap_records = f.cap_regions;
+    if (keep) *keep = f;
     ks.plane_us = h->stats.clear_us + h->stats.fill_us + ls.runs_us;
     h->stats.launches += ls.launches;
   } else {
@@ -74,7 +76,7 @@ void LevelColors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, i
   h->color.seen.Reserve(sizeof(Seen) + (host_table ? record_bytes : 0), &h->allocations);
   h->color.partials.Reserve((size_t)n * kColorPartialWords * sizeof(uint32_t), &h->allocations);
   h->color.acc.Reserve((size_t)cap_records * kColorAccBytes, &h->allocations);
-  if (host_table || picture) h->color.records.Reserve(record_bytes, &h->allocations);
+  if (host_table || picture || keep) h->color.records.Reserve(record_bytes, &h->allocations);
   if (picture) h->color.intervals.Reserve((size_t)n * sizeof(Interval), &h->allocations);
   ColorStatus* status = h->color.status.As<ColorStatus>();
   Seen* seen = h->color.seen.As<Seen>();
@@ -97,7 +99,7 @@ void LevelColors(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, i
   // handle's block; nowhere in a count-only call
   int32_t* records = nullptr;
   uint32_t capacity = 0;
-  if (picture || host_table) {
+  if (picture || host_table || keep) {
     records = h->color.records.As<int32_t>();
     capacity = cap_records;
   } else if (colors) {

@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip, distance.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip, distance.hip, volume.hip),
 // called by the parts of render_capi.cpp (render_handle.h and the capi_*.inc files).
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -651,6 +651,70 @@ void LaunchDistDisc(const int32_t* q, const uint32_t* words, int width, int heig
 // int64, l in [0, levels).
 void LaunchDistScores(const uint32_t* hist_all, const uint32_t* hist_near, const uint32_t* hist_disc, int levels,
                       const DistStatus* status, long long* scores, hipStream_t stream);
+
+// ---- volume session (volume.hip): a level's regions accumulated over frames ---------------------------------
+
+constexpr size_t kVolumeRowBytes = 152;   // vsg_render_volume_row
+constexpr size_t kVolumeColBytes = 48;    // vsg_render_volume_col
+constexpr size_t kVolumePairBytes = 24;   // vsg_render_volume_pair
+constexpr size_t kVolumeGeoBytes = 40;    // what a region of a frame gathers: area, two sums, the box
+
+enum VolumeFlag {
+  VOLUME_FLAG_RANGE = 1,   // a record, a key or a slot was out of range, or the frame's lists disagree
+};
+
+// Written by the volume kernels; read by the host after the merge of an add and at the end of a table call.
+struct VolumeStatus {
+  unsigned long long covered;             // sum of the areas of the frame's regions
+  uint32_t new_rows, new_cols, new_pairs;   // keys the merge did not find
+  uint32_t flags;
+};
+
+// Area, sum of x, sum of y and box of every record of the interval list (rank[i] - 1 is the record of interval
+// i, records contiguous).  geo: `capacity` entries of kVolumeGeoBytes, cleared to zero before.
+void LaunchVolumeGeometry(const Interval* intervals, const uint32_t* rank, uint32_t n, uint32_t capacity, void* geo,
+                          VolumeStatus* status, hipStream_t stream);
+
+// One frame's lists on the device.  regions: kLevelRegionWords per region, word 0 its id.  colors (may be null):
+// kLevelColorWords per region.  overlap_rows / _cols / _pairs (null without labels): the overlap table's.
+struct VolumeFrame {
+  int frame;
+  const int32_t* regions;
+  const void* geo;
+  const int32_t* colors;
+  const int32_t* overlap_rows;
+  uint32_t n_rows;
+  const int32_t* overlap_cols;
+  uint32_t n_cols;
+  const int32_t* overlap_pairs;
+  uint32_t n_pairs;
+};
+
+// The session's three tables: n sorted keys and their records, room for cap of each.
+struct VolumeTables {
+  unsigned long long* row_keys;
+  void* rows;
+  uint32_t n_rows, cap_rows;
+  unsigned long long* col_keys;
+  void* cols;
+  uint32_t n_cols, cap_cols;
+  unsigned long long* pair_keys;
+  void* pairs;
+  uint32_t n_pairs, cap_pairs;
+};
+
+// Adds the frame's records to the tables: a key that is there is added to in place, a new one is written behind
+// the sorted part, n + status->new_* entries afterwards.  Returns the number of launches (one per non-empty list).
+int LaunchVolumeMerge(const VolumeFrame& frame, const VolumeTables& tables, VolumeStatus* status, hipStream_t stream);
+// perm[i] = i.
+void LaunchVolumeIota(uint32_t* perm, uint32_t n, hipStream_t stream);
+// dst record i = src record perm[i]; record_bytes is a multiple of 8.
+void LaunchVolumeGather(const void* src, void* dst, const uint32_t* perm, uint32_t n, size_t record_bytes,
+                        hipStream_t stream);
+// rows, cols, pairs: copies of the tables' records; fills first_pair, num_pairs, best_label and best_count of the
+// rows, num_pairs, best_row and best_count of the columns, row and col of the pairs.  Returns the launches.
+int LaunchVolumeReadout(const VolumeTables& tables, void* rows, void* cols, void* pairs, VolumeStatus* status,
+                        hipStream_t stream);
 
 }  // namespace vsg_render_impl
 

@@ -20,6 +20,7 @@ using vsg_render_impl::PersStatus;
 using vsg_render_impl::SimplifyStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
+using vsg_render_impl::VolumeStatus;
 
 enum Stage { STAGE_CLEAR = 0, STAGE_FILL, STAGE_COMPOSE, STAGE_COUNT };
 enum VecStage { VEC_WALK = 0, VEC_SORT, VEC_PAIRS, VEC_COUNT };
@@ -37,6 +38,7 @@ enum MeshStage { MSH_SPLIT = 0, MSH_TABLE, MSH_STAGES };
 enum SimplifyStage { SMP_DP = 0, SMP_CLEAN, SMP_TABLE, SMP_STAGES };
 // DST_PLANE: the upload of a host label plane
 enum DistStage { DST_PLANE = 0, DST_CLASSIFY, DST_COLUMNS, DST_ROWS, DST_MATCH, DST_STAGES };
+enum VolumeStage { VOL_GEOMETRY = 0, VOL_MERGE, VOL_SORT, VOL_TABLE, VOL_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -180,6 +182,24 @@ struct SimplifyState {
   void Init() { InitFamily(this, SMP_STAGES); }
 };
 
+// volume session: what begin fixed; the three accumulated tables, each sorted keys and records in twin blocks
+// (`at` says which twin holds the table; the other receives a re-sort); the number of entries and the largest
+// key of each; the permutation of a re-sort (in, out); what the regions of a frame gather; the copies a table
+// call fills in; the status words and the pinned block they and host outputs come back through.  The blocks
+// are the family's own: no other call touches them.
+struct VolumeState {
+  StageClock clock;
+  bool active = false, with_colors = false, with_labels = false;
+  int level = 0;
+  uint32_t n_rows = 0, n_cols = 0, n_pairs = 0;
+  uint32_t max_id = 0, max_label = 0;
+  int rows_at = 0, cols_at = 0, pairs_at = 0;
+  Block row_keys[2], rows[2], col_keys[2], cols[2], pair_keys[2], pairs[2];
+  Block perm, geo, out_rows, out_cols, out_pairs, status, seen;
+  vsg_render_volume_stats stats;
+  void Init() { InitFamily(this, VOL_STAGES); }
+};
+
 // The number of bits of a sort key's field that holds values up to `value`: at least 1, at most `limit`.
 int BitsFor(uint64_t value, int limit) {
   int bits = 1;
@@ -220,6 +240,7 @@ struct vsg_render {
   DistanceState dist;
   MeshState mesh;
   SimplifyState simp;
+  VolumeState vol;
 
   ~vsg_render() {
     if (!stream) return;
