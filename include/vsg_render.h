@@ -62,7 +62,11 @@
  * image; the quotients (precision, recall, F) are left to the caller.
  * Appearance descriptors (Lab histograms, the hierarchical stage's) are not offered; the exact colour sums
  * of every group of a level and the mean-colour picture are: vsg_render_level_colors and
- * vsg_render_mean_frame.  All of the above is per frame; what a region id sums up to over the frames of a video
+ * vsg_render_mean_frame.  Appearance beyond the 8-bit picture is the caller's own per-pixel data: a float
+ * feature map of C channels (activations, flow, depth, logits) is pooled by the groups of a level, and group
+ * values are painted back into feature planes, by vsg_render_level_pool and vsg_render_level_unpool; what is
+ * derived from the pooled sums (means, variances, histograms, any colour space) is left to the caller.
+ * All of the above is per frame; what a region id sums up to over the frames of a video
  * (life span, volume, trajectory, colour sums, overlap with ground-truth labels: the inputs of the 3-D
  * supervoxel scores) is accumulated on the device by a volume session: vsg_render_volume_begin, _add, _table.
  *
@@ -675,6 +679,96 @@ typedef struct vsg_render_color_stats {
   int launches;
 } vsg_render_color_stats;                 /* 56 bytes with the tail padding */
 int vsg_render_last_color_stats(vsg_render* h, vsg_render_color_stats* s);
+
+/* ---- Level pooling: float feature planes pooled by group, group values painted back ----
+ *
+ * One group of the pooled table, as vsg_render_level_pool returns it. */
+typedef struct vsg_render_pool_group {   /* 16 bytes, no padding */
+  int32_t id;            /* region id at `level` */
+  int32_t component;     /* index among its region's components; -1 with connectedness 0 */
+  int32_t area;          /* pixels of the group */
+  int32_t reserved;      /* written as 0 */
+} vsg_render_pool_group;
+
+#define VSG_POOL_F32 0    /* IEEE binary32 */
+#define VSG_POOL_F16 1    /* IEEE binary16 */
+#define VSG_POOL_BF16 2   /* bfloat16: the upper 16 bits of a binary32 */
+
+/* A float feature map of C channels pooled by the groups of hierarchy level `level`, the float, C-channel
+ * sibling of vsg_render_level_colors, and its inverse, which paints one value per group and channel back into
+ * feature planes.  Computed on the device.
+ *
+ * The plane.  P is the plane of vsg_render_level_overlap, exactly as for vsg_render_level_colors: the id plane
+ * of the level for connectedness 0, the component label image for VSG_RENDER_CONNECT_N4 / _N8 (that call is
+ * made internally).  Pixels with P < 0 enter no group, and their feature values are never read.
+ *
+ * The features.  `dtype` is one of VSG_POOL_F32, VSG_POOL_F16, VSG_POOL_BF16; `features` has to be aligned to
+ * its element size.  Strides are in elements: element (c, y, x) is at
+ * features[c * chan_stride + y * row_stride + x * pixel_stride], in mem_in memory, independent of mem_out.  Two
+ * layouts are accepted.  Planar: pixel_stride == 1, with any row and channel stride that keep rows and planes
+ * disjoint (row_stride >= W; the planes behind one another or interleaved row by row).  Channels-last:
+ * chan_stride == 1 and pixel_stride >= channels (row_stride >= (W - 1) * pixel_stride + channels).  A layout that
+ * is both (one channel) is read as planar.  Anything else, and any negative stride, is VSG_ERR_INVALID.
+ * 1 <= channels <= 65535.  A host map is copied to the device first, through a block of the handle that only
+ * grows, with its strides and its address modulo 16 kept.
+ *
+ * The table.  One group per group of P, in the order of the sibling calls: groups[k] has the id, component and
+ * area of record k of vsg_render_level_regions (connectedness 0) or vsg_render_level_components.  sum, sum_sq,
+ * min and max are dense row-major [capacity_groups][channels] matrices in mem_out memory; each may be NULL,
+ * which means not wanted, and a statistic that is not wanted is not computed.  groups may be NULL likewise.
+ * Every element is first widened exactly to f64.  sum[k][c] is the f64 sum of the group's values of channel c,
+ * sum_sq[k][c] the f64 sum of their squares (the square of an f32, f16 or bf16 value is exact in f64).  Both are
+ * accumulated in f64 in an order that is a function of the interval list and the layout only (the strides and
+ * the address modulo 16), never of the scheduling: there are no floating-point atomics anywhere, and the same
+ * call returns the same bits; a host map and a device copy of it do when their addresses agree modulo 16 (a
+ * sliced view copied to another offset may differ in the last bits of a sum).  min[k][c] and max[k][c] are the extreme non-NaN values as f32, +inf and -inf when
+ * the group has none.  A NaN in a group's channel makes that channel's sum and sum_sq NaN and touches nothing
+ * else.  Nothing else is derived on the device: mean and variance are left to the caller.
+ *
+ * Decode, hierarchy rules, level refusals, the non-negative ids and the handling of vector-only descs are those
+ * of vsg_render_level_regions.  *num_groups is always set on VSG_OK and when the capacity is too small; in that
+ * case the call fails with VSG_ERR_INVALID and nothing is written.  Every output NULL with capacity 0 asks for
+ * the count only (VSG_OK; needs the device).  A null handle, a null count pointer, null features, a dtype other
+ * than the three, channels outside [1, 65535], strides that are neither layout, a negative stride, a memory kind
+ * other than the two, or a connectedness other than 0, VSG_RENDER_CONNECT_N4 and VSG_RENDER_CONNECT_N8 is
+ * VSG_ERR_INVALID, answered before the handle is dereferenced, and touches no device.  Disjointness is the
+ * exception: it is compared with the handle's size, so it is answered after the handle is read.  A frame with
+ * no covered pixel returns zero groups.  The call neither resolves nor changes the level the handle keeps for
+ * vsg_render_frame (vsg_render_level). */
+int vsg_render_level_pool(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                          const void* features, int dtype, int channels,
+                          ptrdiff_t chan_stride, ptrdiff_t row_stride, ptrdiff_t pixel_stride, int mem_in,
+                          vsg_render_pool_group* groups, double* sum, double* sum_sq, float* min, float* max,
+                          size_t capacity_groups, size_t* num_groups, int mem_out);
+
+/* Unpool.  values is [num_values][channels] f32, dense, in mem_in memory; num_values has to equal the number of
+ * groups of the level, otherwise the call fails with VSG_ERR_INVALID and out stays untouched.
+ * out(c, y, x) = values[record(P(y, x))][c], converted to `dtype` with round-to-nearest-even; where P < 0 the
+ * output is `fill`, converted likewise.  out accepts the same two layouts, in mem_out memory.  Only the W
+ * elements of a row (planar) or the `channels` elements of a pixel (channels-last) are written: padding is
+ * never touched.  A host output goes through a block of the handle: the span from its first to its last element
+ * is copied to the device as it is, written into there and copied back whole, so what lies between the map's
+ * elements is rewritten with its own bytes.  The
+ * refusals are those of vsg_render_level_pool, with out for features and values for the count pointer. */
+int vsg_render_level_unpool(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
+                            const float* values, size_t num_values, int channels, int mem_in, float fill,
+                            void* out, int dtype, ptrdiff_t chan_stride, ptrdiff_t row_stride,
+                            ptrdiff_t pixel_stride, int mem_out);
+
+/* What the last vsg_render_level_pool or vsg_render_level_unpool call of the handle did.  groups, intervals,
+ * covered, largest_group_intervals: as in vsg_render_color_stats.  feature_bytes: the bytes of features the
+ * sums stage read, covered * channels * the element size (0 when no statistic was wanted).  Device times are
+ * HIP events around the stages: plane_us, everything that makes the interval list and bringing a host input
+ * to the device; sums_us, k_pool_sums_planar or k_pool_sums_last; table_us, k_pool_combine, the clear,
+ * k_pool_count and k_pool_finish; paint_us (unpool), k_pool_intervals, the plane's clear, k_render_fill and
+ * k_pool_gather_planar or k_pool_gather_last.  launches does not depend on H, on the number of groups, on the
+ * number of intervals or on the number of channels. */
+typedef struct vsg_render_pool_stats {
+  int64_t groups, intervals, covered, largest_group_intervals, feature_bytes;
+  float plane_us, sums_us, table_us, paint_us;
+  int launches;
+} vsg_render_pool_stats;                  /* 64 bytes with the tail padding */
+int vsg_render_last_pool_stats(vsg_render* h, vsg_render_pool_stats* s);
 
 /* ---- Volume session: a level's supervoxels accumulated over frames ----
  *

@@ -44,6 +44,12 @@
 // persistence_levels=<L of the last frame> persistence_edge_pixels=<sum> persistence_edges=<sum>
 // persistence_fnv1a32=<hash of every frame's plane, then persistence, then level_sides bytes>.
 //
+//   --level_pool <level> [--pool_components [--components_n8]]
+// asks vsg_render_level_pool for the sums, sums of squares, minima and maxima of five planar f32 channels (the
+// frame's B, G, R, then x and y) over that level's regions, or their connected components, in every frame, and
+// prints level_pool_groups=<sum> level_pool_sums=<the five channels' sums over all groups, comma separated>
+// level_pool_fnv1a32=<hash of every frame's groups and four matrices>.
+//
 //   --level_colors <level> [--colors_components [--components_n8]]
 // asks vsg_render_level_colors for the colour sums of that level's regions, or of their connected components
 // (N4, or N8), in every frame of the video, and vsg_render_mean_frame for the level painted in their mean
@@ -1005,6 +1011,99 @@ class LevelColorsSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --level_pool: a planar f32 feature map of five channels, the frame's B, G, R, then x and y, pooled by a level's
+// regions or by their connected components (vsg_render_level_pool): the groups and the four matrices of every
+// frame are hashed, the sums of every channel over all groups added up.
+class LevelPoolSinkUnit : public VideoUnit {
+ public:
+  static constexpr int kChannels = 5;
+  LevelPoolSinkUnit(int level, int connectedness, int device)
+      : level_(level), connect_(connectedness), device_(device) {}
+  ~LevelPoolSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    vid_idx_ = FindStreamIdx("VideoStream", set);
+    if (seg_idx_ < 0 || vid_idx_ < 0) return false;
+    const VideoStream& v = set->at(vid_idx_)->As<VideoStream>();
+    if (v.pixel_format() != PIXEL_FORMAT_BGR24) {
+      std::fprintf(stderr, "ERROR: --level_pool needs a BGR24 video stream\n");
+      return false;
+    }
+    width_ = v.frame_width();
+    height_ = v.frame_height();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.device = device_;
+    if (vsg_render_create(&o, width_, height_, &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    features_.resize((size_t)kChannels * width_ * height_);
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    VF_CHECK(input->at(vid_idx_) != nullptr, "the video frame was freed before the pool sink");
+    const VideoFrame& frame = input->at(vid_idx_)->As<VideoFrame>();
+    const size_t plane = (size_t)width_ * height_;
+    for (int y = 0; y < height_; ++y) {
+      const uint8_t* row = frame.data() + (size_t)y * frame.width_step();
+      for (int x = 0; x < width_; ++x) {
+        const size_t at = (size_t)y * width_ + x;
+        for (int c = 0; c < 3; ++c) features_[c * plane + at] = (float)row[3 * x + c];
+        features_[3 * plane + at] = (float)x;
+        features_[4 * plane + at] = (float)y;
+      }
+    }
+    auto pool = [&](vsg_render_pool_group* g, double* s, double* q, float* lo, float* hi, size_t cap, size_t* n) {
+      VF_CHECK(vsg_render_level_pool(render_, seg, desc.wire.size(), level_, connect_, features_.data(), VSG_POOL_F32,
+                                     kChannels, (ptrdiff_t)plane, (ptrdiff_t)width_, 1, VSG_MEM_HOST, g, s, q, lo, hi,
+                                     cap, n, VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+    };
+    size_t n = 0;
+    pool(nullptr, nullptr, nullptr, nullptr, nullptr, 0, &n);
+    groups_buf_.resize(n);
+    sum_.resize(n * kChannels);
+    sum_sq_.resize(n * kChannels);
+    min_.resize(n * kChannels);
+    max_.resize(n * kChannels);
+    if (n) pool(groups_buf_.data(), sum_.data(), sum_sq_.data(), min_.data(), max_.data(), n, &n);
+    Hash(groups_buf_.data(), n * sizeof(vsg_render_pool_group));
+    Hash(sum_.data(), n * kChannels * sizeof(double));
+    Hash(sum_sq_.data(), n * kChannels * sizeof(double));
+    Hash(min_.data(), n * kChannels * sizeof(float));
+    Hash(max_.data(), n * kChannels * sizeof(float));
+    for (size_t k = 0; k < n; ++k) {
+      for (int c = 0; c < kChannels; ++c) totals_[c] += sum_[k * kChannels + c];   // integers: exact
+    }
+    groups_ += (long)n;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long groups() const { return groups_; }
+  const double* totals() const { return totals_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int level_, connect_, device_, seg_idx_ = -1, vid_idx_ = -1, width_ = 0, height_ = 0;
+  vsg_render* render_ = nullptr;
+  std::vector<float> features_, min_, max_;
+  std::vector<double> sum_, sum_sq_;
+  std::vector<vsg_render_pool_group> groups_buf_;
+  double totals_[kChannels] = {0, 0, 0, 0, 0};
+  long groups_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 }  // namespace
 
 // --read_pb FILE: reads a segmentation container back with SegmentationReader and prints what the
@@ -1120,6 +1219,10 @@ struct Flags {
   // regions, or of the components (N4, or N8 with --components_n8) with --colors_components
   int level_colors = -1;
   bool colors_components = false;
+  // vsg_render_level_pool at this level for every frame; < 0: off.  Of the regions, or of the components (N4, or
+  // N8 with --components_n8) with --pool_components
+  int level_pool = -1;
+  bool pool_components = false;
   // vsg_render_level_contours at this level for every frame; < 0: off.  Of the regions, or of the components
   // (N4, or N8 with --components_n8) with --contours_components
   int level_contours = -1;
@@ -1175,6 +1278,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
                                    "compute_flow", "remove_rasterization", "run_on_server", "components_n8",
                                    "boundaries_outer", "boundaries_components", "adjacency_n8",
                                    "adjacency_components", "overlap_components", "persistence", "colors_components",
+                                   "pool_components",
                                    "contours_components", "mesh_components",
                                    "help"};
     bool is_bool = false, negated = false;
@@ -1234,6 +1338,8 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "persistence") f->persistence = bv;
     else if (a == "level_colors") f->level_colors = atoi(v.c_str());
     else if (a == "colors_components") f->colors_components = bv;
+    else if (a == "level_pool") f->level_pool = atoi(v.c_str());
+    else if (a == "pool_components") f->pool_components = bv;
     else if (a == "level_contours") f->level_contours = atoi(v.c_str());
     else if (a == "boundary_distance") f->boundary_distance = atoi(v.c_str());
     else if (a == "boundary_benchmark") f->boundary_benchmark = atoi(v.c_str());
@@ -1520,6 +1626,15 @@ int main(int argc, char** argv) {
     colors_sink->AttachTo(input);
     input = colors_sink.get();
   }
+  std::unique_ptr<LevelPoolSinkUnit> pool_sink;
+  if (FLAGS.level_pool >= 0) {
+    const int connectedness = !FLAGS.pool_components ? 0
+                              : FLAGS.components_n8  ? VSG_RENDER_CONNECT_N8
+                                                     : VSG_RENDER_CONNECT_N4;
+    pool_sink.reset(new LevelPoolSinkUnit(FLAGS.level_pool, connectedness, FLAGS.device));
+    pool_sink->AttachTo(input);
+    input = pool_sink.get();
+  }
   std::unique_ptr<LevelContoursSinkUnit> contours_sink;
   if (FLAGS.level_contours >= 0) {
     const int connectedness = !FLAGS.contours_components ? 0
@@ -1645,6 +1760,11 @@ int main(int argc, char** argv) {
   }
   if (colors_sink) {
     std::printf("level_colors_groups=%ld level_colors_fnv1a32=%08x\n", colors_sink->groups(), colors_sink->hash());
+  }
+  if (pool_sink) {
+    const double* t = pool_sink->totals();
+    std::printf("level_pool_groups=%ld level_pool_sums=%.17g,%.17g,%.17g,%.17g,%.17g level_pool_fnv1a32=%08x\n",
+                pool_sink->groups(), t[0], t[1], t[2], t[3], t[4], pool_sink->hash());
   }
   if (contours_sink) {
     std::printf("level_contours_count=%ld level_contours_fnv1a32=%08x\n", contours_sink->contours(),

@@ -110,6 +110,15 @@ class VsgRenderColorStats(_capi.Structure):
     ]
 
 
+class VsgRenderPoolStats(_capi.Structure):
+    _fields_ = [
+        ("groups", C.c_int64), ("intervals", C.c_int64), ("covered", C.c_int64),
+        ("largest_group_intervals", C.c_int64), ("feature_bytes", C.c_int64),
+        ("plane_us", C.c_float), ("sums_us", C.c_float), ("table_us", C.c_float), ("paint_us", C.c_float),
+        ("launches", C.c_int),
+    ]
+
+
 class VsgRenderVolumeStats(_capi.Structure):
     _fields_ = [
         ("frames", C.c_int64), ("rows", C.c_int64), ("cols", C.c_int64), ("pairs", C.c_int64),
@@ -243,6 +252,16 @@ LEVEL_COLOR_DTYPE = np.dtype([
 assert LEVEL_COLOR_DTYPE.itemsize == 72
 LEVEL_COLOR_WORDS = 18
 
+# vsg_render_pool_group: 16 bytes, no padding
+POOL_GROUP_DTYPE = np.dtype([("id", np.int32), ("component", np.int32), ("area", np.int32), ("reserved", np.int32)])
+assert POOL_GROUP_DTYPE.itemsize == 16
+POOL_GROUP_WORDS = 4
+
+# VSG_POOL_F32 / _F16 / _BF16, and the statistics of level_pool in the order of the C arguments
+POOL_F32, POOL_F16, POOL_BF16 = 0, 1, 2
+POOL_STATS = ("sum", "sum_sq", "min", "max")
+_POOL_DTYPES = {"float32": POOL_F32, "float16": POOL_F16, "bfloat16": POOL_BF16, "bf16": POOL_BF16}
+
 # vsg_render_volume_row: 152 bytes, no padding
 VOLUME_ROW_DTYPE = np.dtype([
     ("id", np.int32), ("first_frame", np.int32), ("last_frame", np.int32), ("frames", np.int32),
@@ -327,6 +346,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_last_persistence_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
     "vsg_render_volume_begin", "vsg_render_volume_add", "vsg_render_volume_table", "vsg_render_last_volume_stats",
+    "vsg_render_level_pool", "vsg_render_level_unpool", "vsg_render_last_pool_stats",
     "vsg_render_level_contours", "vsg_render_last_contour_stats",
     "vsg_render_level_mesh", "vsg_render_last_mesh_stats",
     "vsg_render_level_mesh_simplified", "vsg_render_last_simplify_stats",
@@ -394,6 +414,13 @@ def lib():
     L.vsg_render_mean_frame.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int, vp,
                                         C.c_size_t, C.c_int]
     L.vsg_render_last_color_stats.argtypes = [vp, C.POINTER(VsgRenderColorStats)]
+    L.vsg_render_level_pool.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_int, C.c_int,
+                                        C.c_ssize_t, C.c_ssize_t, C.c_ssize_t, C.c_int, vp, vp, vp, vp, vp,
+                                        C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
+    L.vsg_render_level_unpool.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, C.c_int, vp, C.c_size_t, C.c_int,
+                                          C.c_int, C.c_float, vp, C.c_int, C.c_ssize_t, C.c_ssize_t, C.c_ssize_t,
+                                          C.c_int]
+    L.vsg_render_last_pool_stats.argtypes = [vp, C.POINTER(VsgRenderPoolStats)]
     L.vsg_render_volume_begin.argtypes = [vp, C.c_int, C.c_int, C.c_int]
     L.vsg_render_volume_add.argtypes = [vp, C.c_char_p, C.c_size_t, C.c_int, vp, C.c_size_t, C.c_int, vp, C.c_size_t,
                                         C.c_int]
@@ -961,6 +988,148 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_color_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def _feature_layout(self, x, what, dtype=None):
+        """(pointer, dtype code, channels, chan_stride, row_stride, pixel_stride, mem kind) of a (C, H, W) or
+        (H, W) float array or tensor, the layout read from its strides (in elements).  A ValueError for anything
+        that is neither planar nor channels-last; never a copy."""
+        name = str(x.dtype).replace("torch.", "")
+        if dtype is not None:
+            wanted = _POOL_DTYPES.get(str(dtype).replace("torch.", ""))
+            if name == "uint16" and wanted == POOL_BF16:
+                name = "bfloat16"
+            elif wanted is None or _POOL_DTYPES.get(name) != wanted:
+                raise TypeError("dtype= names the format of a uint16 array ('bf16'), or the array's own")
+        if name not in _POOL_DTYPES:
+            raise TypeError("%s has to be float32, float16 or bfloat16 (a uint16 array with dtype='bf16'), got %s"
+                            % (what, name))
+        shape = tuple(x.shape)
+        if shape[-2:] != (self.H, self.W) or len(shape) not in (2, 3) or (len(shape) == 3 and shape[0] < 1):
+            raise ValueError("%s has to be (C, %d, %d) or (%d, %d), got %s" % (what, self.H, self.W, self.H, self.W,
+                                                                              shape))
+        ptr, strides, mem = _capi._memory(x)
+        if not _capi.is_torch(x):
+            if any(s % x.itemsize for s in strides):
+                raise ValueError("%s: strides have to be multiples of the element size" % what)
+            strides = tuple(s // x.itemsize for s in strides)
+        channels = shape[0] if len(shape) == 3 else 1
+        cs = strides[0] if len(shape) == 3 else 0
+        rs, ps = strides[-2:]
+        if min(cs, rs, ps) < 0:
+            raise ValueError("%s: negative strides are not accepted" % what)
+        # the stride of an axis of length 1 says nothing
+        if self.W == 1:
+            ps = channels if (channels > 1 and cs == 1) else 1
+        if channels == 1:
+            cs = 1 if ps != 1 else self.H * max(rs, self.W)
+        if self.H == 1:
+            rs = (self.W - 1) * ps + channels if cs == 1 and ps != 1 else self.W
+        if not (ps == 1 or (cs == 1 and ps >= channels)):
+            raise ValueError("%s is neither planar (x stride 1) nor channels-last (channel stride 1, x stride >= C): "
+                             "strides %s" % (what, (cs, rs, ps)))
+        W, H = self.W, self.H
+        if ps != 1:
+            disjoint = H == 1 or rs >= (W - 1) * ps + channels
+        else:
+            disjoint = (H == 1 or rs >= W) and (channels == 1 or cs >= (H - 1) * rs + W
+                                                or (cs >= W and (H == 1 or rs >= (channels - 1) * cs + W)))
+        if not disjoint:
+            raise ValueError("%s: rows or planes overlap or are not in (channel, row, x) order: strides %s"
+                             % (what, (cs, rs, ps)))
+        _capi._drain(x)
+        return C.c_void_p(ptr), _POOL_DTYPES[name], channels, cs, rs, ps, mem
+
+    def level_pool(self, seg_bytes, level=0, features=None, connectedness=0, stats=("sum",), dtype=None,
+                   capacity=None):
+        """A float feature map pooled by the groups of hierarchy level `level`: (groups, {name: matrix}).
+        features: a (C, H, W) or (H, W) float32, float16 or bfloat16 array or tensor (numpy has no bfloat16: a
+        uint16 array with dtype='bf16'), planar or channels-last as its strides say; anything else is a
+        ValueError, never a silent copy.  stats: which of "sum", "sum_sq" (float64) and "min", "max" (float32)
+        to compute, each an (R, C) matrix; record k belongs to record k of level_regions or level_components.
+        groups: a POOL_GROUP_DTYPE array.  A torch CUDA tensor gives torch tensors on its device (groups as an
+        (R, 4) int32 tensor), anything else numpy arrays.  Without capacity the count is asked for first and the
+        outputs are allocated exactly; capacity: rows to allocate instead, which saves that call."""
+        if features is None:
+            raise ValueError("features are needed")
+        stats = tuple(stats)
+        if any(s not in POOL_STATS for s in stats):
+            raise ValueError("stats has to be a subset of %s" % (POOL_STATS,))
+        seg_bytes = bytes(seg_bytes)
+        p, code, channels, cs, rs, ps, mem_in = self._feature_layout(features, "features", dtype)
+        n = C.c_size_t()
+
+        def call(groups, mats, cap, mem_out):
+            check(lib().vsg_render_level_pool(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness), p,
+                                              code, channels, cs, rs, ps, mem_in, groups, mats[0], mats[1], mats[2],
+                                              mats[3], cap, C.byref(n), mem_out))
+
+        if capacity is None:
+            call(None, [None] * 4, 0, VSG_MEM_HOST)
+            capacity = n.value
+        on_device = _capi.is_torch(features) and features.is_cuda
+        if on_device:
+            import torch
+            kinds = {"sum": torch.float64, "sum_sq": torch.float64, "min": torch.float32, "max": torch.float32}
+            groups = torch.empty((capacity, POOL_GROUP_WORDS), dtype=torch.int32, device=features.device)
+            out = {s: torch.empty((capacity, channels), dtype=kinds[s], device=features.device) for s in stats}
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else None   # noqa: E731
+            mem_out = VSG_MEM_DEVICE
+        else:
+            kinds = {"sum": np.float64, "sum_sq": np.float64, "min": np.float32, "max": np.float32}
+            groups = np.empty(capacity, POOL_GROUP_DTYPE)
+            out = {s: np.empty((capacity, channels), kinds[s]) for s in stats}
+            ptr = lambda a: C.c_void_p(a.ctypes.data) if a is not None and a.size else None   # noqa: E731
+            mem_out = VSG_MEM_HOST
+        if capacity:
+            call(ptr(groups), [ptr(out.get(s)) for s in POOL_STATS], capacity, mem_out)
+        return groups[:n.value], {s: out[s][:n.value] for s in stats}
+
+    def level_unpool(self, seg_bytes, level=0, values=None, connectedness=0, fill=0.0, out=None, dtype=None,
+                     channels_last=False):
+        """One value per group and channel painted back into feature planes: out[c, y, x] = values[k, c] for the
+        group k of pixel (x, y), `fill` where there is none.  values: (R, C) float32, contiguous, numpy or torch;
+        R has to be the number of groups of the level.  out: a (C, H, W) or (H, W) float32, float16 or bfloat16
+        array or tensor to write, planar or channels-last as its strides say (only its own elements are written);
+        without it a new one where values live: dtype "float32" (the default), "float16" or "bf16" (numpy: a
+        uint16 array), channels_last choosing its memory layout.  Returns out."""
+        if values is None:
+            raise ValueError("values are needed")
+        if len(values.shape) != 2 or str(values.dtype).replace("torch.", "") != "float32":
+            raise ValueError("values has to be (R, C) float32")
+        rows, channels = int(values.shape[0]), int(values.shape[1])
+        p_val, mem_in = _capi.contiguous_ptr(values)
+        if out is None:
+            name = str(dtype or "float32").replace("torch.", "")
+            if name not in _POOL_DTYPES:
+                raise TypeError("dtype has to be float32, float16 or bf16")
+            shape = (self.H, self.W, channels) if channels_last else (channels, self.H, self.W)
+            if _capi.is_torch(values):
+                import torch
+                kind = {POOL_F32: torch.float32, POOL_F16: torch.float16, POOL_BF16: torch.bfloat16}[_POOL_DTYPES[name]]
+                out = torch.empty(shape, dtype=kind, device=values.device)
+                out = out.permute(2, 0, 1) if channels_last else out
+                out_dtype = None
+            else:
+                kind = {POOL_F32: np.float32, POOL_F16: np.float16, POOL_BF16: np.uint16}[_POOL_DTYPES[name]]
+                out = np.empty(shape, kind)
+                out = out.transpose(2, 0, 1) if channels_last else out
+                out_dtype = "bf16" if kind is np.uint16 else None
+        else:
+            out_dtype = dtype
+        p_out, code, out_channels, cs, rs, ps, mem_out = self._feature_layout(out, "out", out_dtype)
+        if out_channels != channels:
+            raise ValueError("out has %d channels, values %d" % (out_channels, channels))
+        seg_bytes = bytes(seg_bytes)
+        check(lib().vsg_render_level_unpool(self.h, seg_bytes, len(seg_bytes), int(level), int(connectedness),
+                                            p_val if rows else None, rows, channels, mem_in, float(fill), p_out, code,
+                                            cs, rs, ps, mem_out))
+        return out
+
+    def last_pool_stats(self):
+        """vsg_render_last_pool_stats of the last level_pool or level_unpool call, as a dict."""
+        s = VsgRenderPoolStats()
+        check(lib().vsg_render_last_pool_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def volume_begin(self, level=0, colors=False, labels=False):
         """Starts, or restarts and empties, the renderer's volume session: the table of the supervoxels (region ids)
         of hierarchy level `level` that volume_add merges every frame into on the device.  colors: every add
@@ -1316,6 +1485,61 @@ def color_moments(records):
     mean = records["sum"].astype(np.float64) / area
     variance = np.maximum(records["sum_sq"].astype(np.float64) / area - mean * mean, 0.0)
     return mean, variance
+
+
+def pool_moments(groups, sum, sum_sq):
+    """(mean, variance) of every group and channel of level_pool, two (R, C) float64 arrays: sum / area and
+    sum_sq / area - (sum / area)^2 (the population variance; never below 0).  Host numpy only."""
+    groups = np.asarray(groups)
+    area = groups["area"].astype(np.float64)[:, None]
+    mean = np.asarray(sum, np.float64) / area
+    variance = np.maximum(np.asarray(sum_sq, np.float64) / area - mean * mean, 0.0)
+    return mean, variance
+
+
+def region_pool(renderer, seg_bytes, level=0, connectedness=0):
+    """(pool, unpool) of one frame's segmentation at one level for use in a torch model, both differentiable:
+    pool maps (C, H, W) float32 CUDA features to the (R, C) float32 means of the R groups, unpool maps (R, C)
+    values to the (C, H, W) planes that hold every pixel's group value (0 where there is no group).  The
+    backward of pool is the unpool of grad / area, the backward of unpool the pooled sum of grad: the two calls
+    of SegmentationRenderer are all there is to it."""
+    import torch
+    seg_bytes = bytes(seg_bytes)
+
+    def sums(x):
+        x = x.detach()
+        try:   # a gradient may be a broadcast view (a stride of 0) or anything else that is no layout: copy it
+            renderer._feature_layout(x, "features")
+        except ValueError:
+            x = x.contiguous()
+        groups, out = renderer.level_pool(seg_bytes, level, x, connectedness, ("sum",))
+        return groups[:, 2:3].to(torch.float64), out["sum"]
+
+    def paint(values):
+        return renderer.level_unpool(seg_bytes, level, values.detach().contiguous(), connectedness)
+
+    class Pool(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, features):
+            area, total = sums(features)
+            ctx.save_for_backward(area)
+            return (total / area).to(torch.float32)
+
+        @staticmethod
+        def backward(ctx, grad):
+            area, = ctx.saved_tensors
+            return paint(grad.to(torch.float32) / area.to(torch.float32))
+
+    class Unpool(torch.autograd.Function):
+        @staticmethod
+        def forward(ctx, values):
+            return paint(values.to(torch.float32))
+
+        @staticmethod
+        def backward(ctx, grad):
+            return sums(grad.to(torch.float32))[1].to(torch.float32)
+
+    return Pool.apply, Unpool.apply
 
 
 def contour_polygons(contours, vertices):

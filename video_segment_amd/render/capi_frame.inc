@@ -57,6 +57,7 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->ovl.Init();
     h->pers.Init();
     h->color.Init();
+    h->pool.Init();
     h->cont.Init();
     h->dist.Init();
     h->mesh.Init();

@@ -1,5 +1,5 @@
 // render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, contours.hip, distance.hip, volume.hip),
+// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, pool.hip, contours.hip, distance.hip, volume.hip),
 // called by the parts of render_capi.cpp (render_handle.h and the capi_*.inc files).
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
@@ -391,6 +391,76 @@ void LaunchColorTable(const Interval* intervals, const uint32_t* rank, const uin
 // out[i] = interval i with the packed mean of its record as its value.
 void LaunchColorIntervals(const Interval* intervals, const uint32_t* rank, uint32_t n, const int32_t* records,
                           uint32_t capacity, Interval* out, hipStream_t stream);
+
+// ---- level pooling (pool.hip): float feature planes pooled by group, group values painted back ---------
+
+constexpr int kPoolGroupWords = 4;          // vsg_render_pool_group as int32 words
+constexpr int kPoolPlanarChannels = 8;      // channels a wavefront of the planar sums kernel takes
+constexpr int kPoolLastChannels = 64;       // channels a wavefront of the channels-last sums kernel takes
+constexpr int kPoolLongInterval = 64;       // planar: from this length on the whole wavefront sums one interval,
+constexpr int kPoolGroupInterval = 16;      // from this one on 16 lanes do, from this one on four; a shorter one is
+constexpr int kPoolQuadInterval = 4;        // summed by its own lane
+constexpr uint32_t kPoolWaves = 1024;       // the slices the sums kernels want before a slice takes more intervals
+
+enum PoolDtype { POOL_F32 = 0, POOL_F16 = 1, POOL_BF16 = 2 };
+enum PoolStat { POOL_SUM = 1, POOL_SUM_SQ = 2, POOL_MIN = 4, POOL_MAX = 8 };
+enum PoolFlag {
+  POOL_FLAG_RANGE = 1,   // an interval's record was out of range, or a record had no pixel
+};
+
+// Written by the pool kernels; read by the host at the end of a call.
+struct PoolStatus {
+  unsigned long long covered;   // sum of the records' areas
+  uint32_t largest;             // most intervals of one record
+  uint32_t flags;
+};
+
+// Where the elements of a feature map are (strides in elements) and what they are.  channels_last: lanes go
+// along the channels of a pixel (chan_stride 1); otherwise along x (pixel_stride 1).
+struct PoolLayout {
+  long long chan_stride, row_stride, pixel_stride;
+  int channels, dtype;
+  bool channels_last;
+};
+
+// The four statistics as dense [records][channels] matrices; null where one is not wanted.
+struct PoolMatrices {
+  double* sum;
+  double* sum_sq;
+  float* min;
+  float* max;
+};
+
+// The intervals a slice of the list has: 64, or fewer (a power of two) while the list is short.  A function of
+// n alone, so that the order of every sum is one of the list.
+uint32_t PoolSlice(uint32_t n);
+inline uint32_t PoolSlices(uint32_t n) {
+  const uint32_t s = PoolSlice(n);
+  return (n + s - 1) / s;
+}
+// Sums of every record that lies inside one slice into `out`, of every part of a record that goes on into
+// another slice into `spill`: [slices][2][channels] per statistic, [s][0] the part that began before slice s,
+// [s][1] the part that goes on behind it.  mask: the PoolStat bits wanted; the matrices of both have them.
+// Only the elements of covered pixels are read.  No launch when n == 0.
+void LaunchPoolSums(const Interval* intervals, const uint32_t* rank, uint32_t n, int width, int height,
+                    const void* features, const PoolLayout& layout, int mask, const PoolMatrices& out,
+                    const PoolMatrices& spill, hipStream_t stream);
+// The records that span slices: their parts combined in slice order.
+void LaunchPoolCombine(const uint32_t* rank, uint32_t n, int channels, int mask, const PoolMatrices& spill,
+                       const PoolMatrices& out, hipStream_t stream);
+// Area and interval count of every record (acc: two uint32 per record, cleared before), then the groups
+// {id, component or -1, area, 0} and the status' totals.  table, table_words, has_component as for the colours.
+void LaunchPoolGroups(const Interval* intervals, const uint32_t* rank, uint32_t n, uint32_t records, uint32_t* acc,
+                      const int32_t* table, int table_words, bool has_component, int32_t* groups, PoolStatus* status,
+                      hipStream_t stream);
+// out[i] = interval i with its 1-based record as its value.
+void LaunchPoolIntervals(const Interval* intervals, const uint32_t* rank, uint32_t n, Interval* out,
+                         hipStream_t stream);
+// out(c, y, x) = values[plane(y, x) - 1][c] converted to the layout's dtype (round to nearest even), `fill`
+// where the plane holds 0 or a record beyond num_values.  Only the W elements of a row (planar) or the
+// channels of a pixel (channels-last) are written.
+void LaunchPoolGather(const uint32_t* plane, int pitch, int width, int height, const float* values,
+                      uint32_t num_values, float fill, void* out, const PoolLayout& layout, hipStream_t stream);
 
 // ---- level contours (contours.hip): the traced closed contours of every group of an int32 plane --------
 

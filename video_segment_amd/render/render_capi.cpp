@@ -17,6 +17,7 @@
 //   capi_overlap.inc       vsg_render_level_overlap
 //   capi_persistence.inc   vsg_render_persistence_image, _frame, _graph
 //   capi_colors.inc        vsg_render_level_colors, vsg_render_mean_frame
+//   capi_pool.inc          vsg_render_level_pool, vsg_render_level_unpool
 //   capi_volume.inc        vsg_render_volume_begin, _add, _table
 //   capi_contours.inc      vsg_render_level_contours, vsg_render_level_mesh
 //   capi_simplify.inc      vsg_render_level_mesh_simplified
@@ -45,6 +46,7 @@
 #include "capi_overlap.inc"
 #include "capi_persistence.inc"
 #include "capi_colors.inc"
+#include "capi_pool.inc"
 #include "capi_volume.inc"
 #include "capi_contours.inc"
 #include "capi_simplify.inc"

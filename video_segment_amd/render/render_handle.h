@@ -17,6 +17,7 @@ using vsg_render_impl::LevelStatus;
 using vsg_render_impl::MeshStatus;
 using vsg_render_impl::OvlStatus;
 using vsg_render_impl::PersStatus;
+using vsg_render_impl::PoolStatus;
 using vsg_render_impl::SimplifyStatus;
 using vsg_render_impl::VecLine;
 using vsg_render_impl::VecStatus;
@@ -33,6 +34,7 @@ enum OvlStage { OVL_UPLOAD = 0, OVL_COUNT, OVL_EMIT, OVL_SORT, OVL_TABLE, OVL_ST
 // PRS_WAIT: the source frame's upload between the two kernels of a picture; reported with no stage
 enum PersStage { PRS_PERSIST = 0, PRS_COMPOSE, PRS_WAIT, PRS_STAGES };
 enum ColorStage { CLR_UPLOAD = 0, CLR_SUMS, CLR_TABLE, CLR_PAINT, CLR_STAGES };
+enum PoolStage { POOL_UPLOAD = 0, POOL_SUMS, POOL_TABLE, POOL_PAINT, POOL_STAGES };
 enum ContourStage { CNT_CLASSIFY = 0, CNT_TRACE, CNT_TABLE, CNT_STAGES };
 enum MeshStage { MSH_SPLIT = 0, MSH_TABLE, MSH_STAGES };
 enum SimplifyStage { SMP_DP = 0, SMP_CLEAN, SMP_TABLE, SMP_STAGES };
@@ -138,6 +140,17 @@ struct ColorState {
   void Init() { InitFamily(this, CLR_STAGES); }
 };
 
+// level pooling: a host feature map or a host output's span on the device; host values on the device; the parts
+// of the records that span slices; area and interval count of every record; groups and matrices of a host
+// output; the interval list with the records as values; the status words and the pinned block the status, the
+// number of records and host outputs come back through
+struct PoolState {
+  StageClock clock;
+  Block features, values, spill, acc, out, intervals, status, seen;
+  vsg_render_pool_stats stats;
+  void Init() { InitFamily(this, POOL_STAGES); }
+};
+
 // level contours: the pixels' crack masks and offsets; what there is per crack (the two doubling states, key,
 // successor, leader, place, the vertices' owners; the vertices take the doubling state that is free at the
 // end); what there is per contour slot (unsorted and sorted keys, group ranks, vertex counts and offsets); the
@@ -236,6 +249,7 @@ struct vsg_render {
   OverlapState ovl;
   PersistenceState pers;
   ColorState color;
+  PoolState pool;
   ContourState cont;
   DistanceState dist;
   MeshState mesh;
