@@ -1,6 +1,6 @@
 """vsg_render_level_adjacency on the MI355X (libvsg_render.so: the id plane or the component label image,
 k_adj_classify's count and emit passes, the key sort, the scan, k_adj_table, k_adj_finish, k_adj_resolve,
-k_adj_copy) against level_adjacency_model.py.  Nodes and edges are compared as raw bytes: there is no
+k_copy_lists) against level_adjacency_model.py.  Nodes and edges are compared as raw bytes: there is no
 tolerance anywhere in this file."""
 import ctypes as C
 import os

@@ -1,5 +1,5 @@
 """vsg_render_level_boundaries on the MI355X (libvsg_render.so: the id plane or the component label image,
-k_bound_classify's count and emit passes, the key sort, k_bound_table, k_bound_finish, k_bound_copy) against
+k_bound_classify's count and emit passes, the key sort, k_bound_table, k_bound_finish, k_copy_lists) against
 level_boundaries_model.py.  Records and points are compared as raw bytes: there is no tolerance anywhere in
 this file."""
 import ctypes as C

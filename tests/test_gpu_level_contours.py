@@ -1,6 +1,6 @@
 """vsg_render_level_contours on the MI355X (libvsg_render.so: the id plane or the component label image,
 k_contour_classify and its scan, k_contour_emit, the two pointer doublings, the contours' sort, the vertex
-scatter, k_contour_table, k_contour_measure, k_contour_finish, k_contour_copy) against
+scatter, k_contour_table, k_contour_measure, k_contour_finish, k_copy_lists) against
 level_contours_model.py.  Records and vertices are compared as raw bytes: there is no tolerance anywhere in
 this file."""
 import ctypes as C

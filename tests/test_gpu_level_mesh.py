@@ -1,6 +1,6 @@
 """vsg_render_level_mesh on the MI355X (libvsg_render.so: the contour stages, then k_mesh_junctions, k_mesh_seed,
 the third pointer doubling, k_mesh_loop_counts, k_mesh_halves, the segments' sort, k_mesh_seg_heads,
-k_mesh_vertices, k_mesh_records, k_mesh_links, k_mesh_measure, k_mesh_finish, k_mesh_copy) against
+k_mesh_vertices, k_mesh_records, k_mesh_links, k_mesh_measure, k_mesh_finish, k_copy_lists) against
 level_mesh_model.py, and against the contours, adjacency and rasterize calls of the same handle.  All four lists
 are compared as raw bytes: there is no tolerance anywhere in this file."""
 import ctypes as C

@@ -1,6 +1,6 @@
 """vsg_render_level_mesh_simplified on the MI355X (libvsg_render.so: the contour and mesh stages, then
 k_simplify_dp_wave, k_simplify_dp_block, k_simplify_clean, the scan, k_simplify_compact, k_simplify_records,
-k_simplify_copy) against level_mesh_simplify_model.py, which applies boundary_oracle.approx_poly_dp to every
+k_copy_lists) against level_mesh_simplify_model.py, which applies boundary_oracle.approx_poly_dp to every
 segment's full lattice point list, and against the mesh and rasterize calls of the same handle.  All four lists
 are compared as raw bytes: there is no tolerance anywhere in this file.  The device takes a fraction of a second
 on every case; the slowest case, comb_8192, spends its time in the Python model, whose recursion on 49 146 lattice

@@ -1,6 +1,6 @@
 """vsg_render_level_overlap on the MI355X (libvsg_render.so: the id plane or the component label image,
 k_overlap_runs' count and emit passes, the sort of the runs, the scans, k_overlap_table, k_overlap_pairs,
-k_overlap_rows, the sort by label, k_overlap_col_heads, k_overlap_cols, k_overlap_copy) against
+k_overlap_rows, the sort by label, k_overlap_col_heads, k_overlap_cols, k_copy_lists) against
 level_overlap_model.py.  Rows, cols and pairs are compared as raw bytes: there is no tolerance anywhere in
 this file."""
 import ctypes as C

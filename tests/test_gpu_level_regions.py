@@ -211,6 +211,54 @@ def test_device_outputs_equal_host_outputs(vsg):
     r.close()
 
 
+def test_device_outputs_one_entry_short_in_turn_stay_untouched(vsg):
+    import torch
+    from video_segment_amd import render
+    c = BY_NAME["three_levels"]
+    seg = c.msg.SerializeToString()
+    dev = torch.device("cuda", 0)
+    r = vsg.SegmentationRenderer(c.W, c.H)
+    for level in c.levels:
+        nr_, ni_ = (len(a) for a in r.level_regions(seg, level))
+        d_regions = torch.full((nr_ + 3, render.LEVEL_REGION_WORDS), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        d_intervals = torch.full((ni_ + 3, 4), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+        # one region, then one interval too few: refused, nothing written
+        for cut_r, cut_i in ((1, 0), (0, 1)):
+            with pytest.raises(render.VsgError):
+                r.level_regions(seg, level, regions_out=d_regions[:nr_ - cut_r],
+                                intervals_out=d_intervals[:ni_ - cut_i])
+            assert bool((d_regions == 0x5A5A5A5A).all()) and bool((d_intervals == 0x5A5A5A5A).all()), (cut_r, cut_i)
+    r.close()
+
+
+def test_device_outputs_larger_than_one_pass_of_the_copy_grid(vsg):
+    """768 x 256 in one-pixel vertical stripes of two ids: 196 608 intervals, 786 432 copied words, more than the
+    2048 x 256 threads of the copy's grid take in one pass of its stride loop."""
+    import torch
+    from video_segment_amd import render
+    W, H = 768, 256
+    ids = np.tile(np.arange(W, dtype=np.int32) % 2 + 5, (H, 1))
+    seg = lc.desc_from_ids(ids).SerializeToString()
+    dev = torch.device("cuda", 0)
+    r = vsg.SegmentationRenderer(W, H, has_video=False)
+    host_r, host_i = r.level_regions(seg, 0)
+    nr_, ni_ = len(host_r), len(host_i)
+    assert (nr_, ni_) == (2, W * H) and nr_ * render.LEVEL_REGION_WORDS + ni_ * 4 > 2048 * 256
+    # region 5 has the even columns, row after row, region 6 the odd ones
+    yy, xx = np.divmod(np.arange(W * H // 2), W // 2)
+    for k, rid in enumerate((5, 6)):
+        want = np.stack([yy, 2 * xx + k, 2 * xx + k, np.full_like(yy, rid)], 1)
+        assert np.array_equal(host_i[k * len(yy):(k + 1) * len(yy)], want), rid
+    d_regions = torch.full((nr_ + 3, render.LEVEL_REGION_WORDS), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    d_intervals = torch.full((ni_ + 3, 4), 0x5A5A5A5A, dtype=torch.int32, device=dev)
+    got_r, got_i = r.level_regions(seg, 0, regions_out=d_regions, intervals_out=d_intervals)
+    assert got_r.shape == (nr_, render.LEVEL_REGION_WORDS) and got_i.shape == (ni_, 4)
+    assert got_r.cpu().numpy().tobytes() == host_r.tobytes()
+    assert got_i.cpu().numpy().tobytes() == host_i.tobytes()
+    assert bool((d_regions[nr_:] == 0x5A5A5A5A).all()) and bool((d_intervals[ni_:] == 0x5A5A5A5A).all())
+    r.close()
+
+
 def test_vector_only_desc(vsg):
     W, H = 64, 48
     m = vc.vector_only(vc.l1_voronoi(11, W, H, 12))

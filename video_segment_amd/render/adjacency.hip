@@ -15,7 +15,7 @@
 //   k_adj_finish           one thread per node: num_edges; the largest of them
 //   k_adj_resolve          region planes only, one thread per edge: the neighbour's id -> its node index,
 //                          by binary search in the node ids
-//   k_adj_copy             nodes and edges to the caller's device memory, if both fit
+//   k_copy_lists           of lists.hip: nodes and edges to the caller's device memory, if both fit
 //
 // Key layout, gb = the bits of the largest group (1..31):
 //   bit 0                kind: 0 a pixel side, 1 a diagonal contact
@@ -26,8 +26,8 @@
 // per diagonal neighbour of another group: every key counts once, for the group of the position that
 // emitted it, so the graph is symmetric without a single atomic on a count shared by two groups.
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
+#include "render_scan.h"
 
 namespace vsg_render_impl {
 
@@ -96,17 +96,8 @@ __global__ __launch_bounds__(kAdjBlock) void k_adj_classify(const int32_t* __res
       offset[j] = in_wave + (uint32_t)__popcll(b & below);
       in_wave += (uint32_t)__popcll(b);
     }
-    if (lane == 0) s_wave[wave] = in_wave;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kAdjWaves; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (t == 0 && total) s_base = atomicAdd(&status->emitted, total);
-    __syncthreads();
-    if (total) {
+    uint32_t before;
+    if (BlockReserve<kAdjWaves>(in_wave, s_wave, &s_base, &status->emitted, &before)) {
       const uint32_t base = s_base;
       const unsigned long long mine = (unsigned long long)(uint32_t)c << (group_bits + 2);
 #pragma unroll
@@ -121,7 +112,7 @@ __global__ __launch_bounds__(kAdjBlock) void k_adj_classify(const int32_t* __res
     }
   }
   if (!kEmit) {
-    for (int s = 32; s > 0; s >>= 1) counted += __shfl_xor(counted, s);
+    counted = WaveSum(counted);
     if (lane == 0) s_wave[wave] = counted;
     __syncthreads();
     if (t == 0) {
@@ -132,34 +123,6 @@ __global__ __launch_bounds__(kAdjBlock) void k_adj_classify(const int32_t* __res
     }
   }
 }
-
-// The fields of a key.
-__device__ __host__ __forceinline__ unsigned long long AdjGroup(unsigned long long key, int group_bits) {
-  return key >> (group_bits + 2);
-}
-__device__ __host__ __forceinline__ uint32_t AdjOther(unsigned long long key, int group_bits) {
-  return (uint32_t)(key >> 1) & (uint32_t)((1ull << (group_bits + 1)) - 1);
-}
-__device__ __host__ __forceinline__ bool AdjReserved(unsigned long long key, int group_bits) {
-  return (key >> (group_bits + 1)) & 1;
-}
-
-// Sorted key i -> 1 << 32 if it is the first of its group, + 1 if it is the first of its (group, other)
-// and other is a group.
-struct AdjHeads {
-  const unsigned long long* keys;
-  int group_bits;
-  __host__ __device__ unsigned long long operator()(uint32_t i) const {
-    const unsigned long long key = keys[i];
-    const bool first = i == 0;
-    const unsigned long long prev = first ? 0ull : keys[i - 1];
-    const bool node = first || AdjGroup(key, group_bits) != AdjGroup(prev, group_bits);
-    const bool edge = (first || (key >> 1) != (prev >> 1)) && !AdjReserved(key, group_bits);
-    return (node ? 1ull << 32 : 0ull) | (edge ? 1ull : 0ull);
-  }
-};
-typedef hipcub::TransformInputIterator<unsigned long long, AdjHeads, hipcub::CountingInputIterator<uint32_t>>
-    AdjHeadIterator;
 
 // One thread per sorted key i < n.  heads[i] = node heads << 32 | edge heads in [0, i].  What the sort
 // hands back is checked before it is used as an index: a group or a neighbour above max_group, a
@@ -229,7 +192,7 @@ __global__ __launch_bounds__(256) void k_adj_finish(int32_t* __restrict__ nodes,
     else atomicOr(&status->flags, (uint32_t)ADJ_FLAG_RANGE);
     node[3] = (int32_t)mine;
   }
-  for (int s = 32; s > 0; s >>= 1) mine = max(mine, (uint32_t)__shfl_xor(mine, s));
+  mine = WaveMax(mine);
   if ((threadIdx.x & 63) == 0 && mine) atomicMax(&status->largest, mine);
 }
 
@@ -253,23 +216,6 @@ __global__ __launch_bounds__(256) void k_adj_resolve(const int32_t* __restrict__
   else atomicOr(&status->flags, (uint32_t)ADJ_FLAG_RANGE);
 }
 
-// Both lists to the caller's device memory, or neither: their lengths are known on the device only.
-// Dword copies, grid-stride.
-__global__ __launch_bounds__(256) void k_adj_copy(const int32_t* __restrict__ nodes,
-                                                  const int32_t* __restrict__ edges, uint32_t capacity_nodes,
-                                                  uint32_t capacity_edges, int32_t* __restrict__ nodes_out,
-                                                  int32_t* __restrict__ edges_out,
-                                                  const AdjStatus* __restrict__ status) {
-  const uint32_t n_nodes = status->nodes, n_edges = status->edges;
-  if (n_nodes > capacity_nodes || n_edges > capacity_edges || status->flags) return;
-  const size_t node_words = (size_t)n_nodes * kLevelNodeWords, edge_words = (size_t)n_edges * kLevelEdgeWords;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < node_words + edge_words; k += step) {
-    if (k < node_words) nodes_out[k] = nodes[k];
-    else edges_out[k - node_words] = edges[k - node_words];
-  }
-}
-
 }  // namespace
 
 void LaunchAdjClassify(const int32_t* plane, int width, int height, int group_bits, bool diagonal, bool emit,
@@ -290,27 +236,6 @@ void LaunchAdjClassify(const int32_t* plane, int width, int height, int group_bi
   }
 }
 
-size_t AdjTempBytes(int64_t n, int end_bit) {
-  size_t sort_bytes = 0, scan_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const unsigned long long*)nullptr,
-                                          (unsigned long long*)nullptr, n, 0, end_bit, (hipStream_t) nullptr);
-  AdjHeadIterator heads(hipcub::CountingInputIterator<uint32_t>(0), AdjHeads{nullptr, 1});
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, heads, (unsigned long long*)nullptr, n,
-                                         (hipStream_t) nullptr);
-  return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-}
-
-hipError_t AdjSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                   int64_t n, int end_bit, hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, keys_in, keys_out, n, 0, end_bit, stream);
-}
-
-hipError_t AdjRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, int group_bits,
-                   unsigned long long* heads, int64_t n, hipStream_t stream) {
-  AdjHeadIterator it(hipcub::CountingInputIterator<uint32_t>(0), AdjHeads{keys_sorted, group_bits});
-  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, it, heads, n, stream);
-}
-
 void LaunchAdjTable(const unsigned long long* keys_sorted, const unsigned long long* heads, uint32_t n, int group_bits,
                     uint32_t max_group, uint32_t capacity_nodes, uint32_t capacity_edges, const int32_t* comp_table,
                     int32_t* nodes, int32_t* edges, AdjStatus* status, hipStream_t stream) {
@@ -325,15 +250,6 @@ void LaunchAdjTable(const unsigned long long* keys_sorted, const unsigned long l
     hipLaunchKernelGGL(k_adj_resolve, dim3((capacity_edges + 255) / 256), dim3(256), 0, stream, nodes, capacity_nodes,
                        edges, capacity_edges, status);
   }
-}
-
-void LaunchAdjCopy(const int32_t* nodes, const int32_t* edges, uint32_t capacity_nodes, uint32_t capacity_edges,
-                   int32_t* nodes_out, int32_t* edges_out, const AdjStatus* status, hipStream_t stream) {
-  const size_t words = (size_t)capacity_nodes * kLevelNodeWords + (size_t)capacity_edges * kLevelEdgeWords;
-  if (words == 0) return;
-  const size_t groups = (words + 255) / 256;
-  hipLaunchKernelGGL(k_adj_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, nodes, edges,
-                     capacity_nodes, capacity_edges, nodes_out, edges_out, status);
 }
 
 }  // namespace vsg_render_impl

@@ -9,19 +9,19 @@
 //   k_bound_classify<emit>   the same walk: the keys group << 32 | padded position, in no order; one
 //                            add per block and step of 256 positions reserves their slots
 //   radix sort               keys only, into (group, y, x) order
-//   scan                     rank of every key's group among the groups (LevelRank of level.hip)
+//   scan                     rank of every key's group among the groups (HeadFlag of render_scan.h)
 //   k_bound_table            one thread per sorted key: its point {x, y}; a segment head also writes
 //                            its record's id, component and first point
 //   k_bound_finish           one thread per record: its number of points; the largest of them
-//   k_bound_copy             records and points to the caller's device memory, if the records fit
+//   k_copy_lists             of lists.hip: records and points to the caller's device memory, if the
+//                            records fit
 //
 // inner: a position with P = g >= 0 and a neighbour != g emits (g, position).  outer: a position emits
 // (g, position) for every distinct g >= 0 among its four neighbours that is not its own value; the
 // neighbours are compared pairwise, so a position flanked by one group on several sides emits once.
 // Keys are unique, which leaves the order of the slots free.
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -29,11 +29,6 @@ namespace {
 
 constexpr int kBoundBlock = 256;
 constexpr int kBoundWaves = kBoundBlock / 64;
-
-// P at frame position (x, y); -1 outside the frame.
-__device__ __forceinline__ int32_t PlaneAt(const int32_t* __restrict__ plane, int W, int H, int x, int y) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? plane[(size_t)y * W + x] : -1;
-}
 
 // One block walks padded row blockIdx.x (frame row y = blockIdx.x - 1) in steps of kBoundBlock padded
 // positions, a thread a position.  The row itself goes through LDS with a halo of one position on each
@@ -92,17 +87,8 @@ __global__ __launch_bounds__(kBoundBlock) void k_bound_classify(const int32_t* _
       offset[j] = in_wave + (uint32_t)__popcll(b & below);
       in_wave += (uint32_t)__popcll(b);
     }
-    if (lane == 0) s_wave[wave] = in_wave;
-    __syncthreads();
-    uint32_t before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < kBoundWaves; ++w) {
-      if (w < wave) before += s_wave[w];
-      total += s_wave[w];
-    }
-    if (t == 0 && total) s_base = atomicAdd(&status->emitted, total);
-    __syncthreads();
-    if (total) {
+    uint32_t before;
+    if (BlockReserve<kBoundWaves>(in_wave, s_wave, &s_base, &status->emitted, &before)) {
       const uint32_t base = s_base;
       const uint32_t pos = (uint32_t)py * (uint32_t)PW + (uint32_t)px;
 #pragma unroll
@@ -115,7 +101,7 @@ __global__ __launch_bounds__(kBoundBlock) void k_bound_classify(const int32_t* _
     }
   }
   if (!kEmit) {
-    for (int s = 32; s > 0; s >>= 1) counted += __shfl_xor(counted, s);
+    counted = WaveSum(counted);
     if (lane == 0) s_wave[wave] = counted;
     __syncthreads();
     if (t == 0) {
@@ -178,25 +164,8 @@ __global__ __launch_bounds__(256) void k_bound_finish(int32_t* __restrict__ reco
     if (!mine) atomicOr(&status->flags, (uint32_t)BOUND_FLAG_RANGE);
     out[3] = (int32_t)mine;
   }
-  for (int s = 32; s > 0; s >>= 1) mine = max(mine, (uint32_t)__shfl_xor(mine, s));
+  mine = WaveMax(mine);
   if ((threadIdx.x & 63) == 0 && mine) atomicMax(&status->largest, mine);
-}
-
-// Both lists to the caller's device memory, or neither: the number of records is known on the device
-// only.  Dword copies, grid-stride.
-__global__ __launch_bounds__(256) void k_bound_copy(const int32_t* __restrict__ records,
-                                                    const int32_t* __restrict__ points, uint32_t n,
-                                                    uint32_t capacity_records, int32_t* __restrict__ records_out,
-                                                    int32_t* __restrict__ points_out,
-                                                    const BoundStatus* __restrict__ status) {
-  const uint32_t n_records = status->boundaries;
-  if (n_records > capacity_records || status->flags) return;
-  const size_t record_words = (size_t)n_records * kLevelBoundaryWords, point_words = (size_t)n * 2;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < record_words + point_words; k += step) {
-    if (k < record_words) records_out[k] = records[k];
-    else points_out[k - record_words] = points[k - record_words];
-  }
 }
 
 }  // namespace
@@ -219,19 +188,6 @@ void LaunchBoundClassify(const int32_t* plane, int width, int height, bool outer
   }
 }
 
-size_t BoundTempBytes(int64_t n, int end_bit) {
-  size_t sort_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort_bytes, (const unsigned long long*)nullptr,
-                                          (unsigned long long*)nullptr, n, 0, end_bit, (hipStream_t) nullptr);
-  const size_t rank_bytes = LevelTempBytes(n, end_bit);   // of LevelRank, which the scan is
-  return sort_bytes > rank_bytes ? sort_bytes : rank_bytes;
-}
-
-hipError_t BoundSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                     int64_t n, int end_bit, hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, keys_in, keys_out, n, 0, end_bit, stream);
-}
-
 void LaunchBoundTable(const unsigned long long* keys_sorted, const uint32_t* rank, uint32_t n, int width, int height,
                       uint32_t max_group, uint32_t capacity_records, const int32_t* comp_table, int32_t* points,
                       int32_t* records, BoundStatus* status, hipStream_t stream) {
@@ -242,15 +198,6 @@ void LaunchBoundTable(const unsigned long long* keys_sorted, const uint32_t* ran
   // status->boundaries of them leave at once
   hipLaunchKernelGGL(k_bound_finish, dim3((capacity_records + 255) / 256), dim3(256), 0, stream, records, n,
                      capacity_records, status);
-}
-
-void LaunchBoundCopy(const int32_t* records, const int32_t* points, uint32_t n, uint32_t capacity_records,
-                     int32_t* records_out, int32_t* points_out, const BoundStatus* status, hipStream_t stream) {
-  if (n == 0) return;
-  const size_t words = (size_t)n * 2 + (size_t)capacity_records * kLevelBoundaryWords;
-  const size_t groups = (words + 255) / 256;
-  hipLaunchKernelGGL(k_bound_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, records,
-                     points, n, capacity_records, records_out, points_out, status);
 }
 
 }  // namespace vsg_render_impl

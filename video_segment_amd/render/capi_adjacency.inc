@@ -60,7 +60,7 @@ void LevelAdjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level
   if (cap_nodes == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
   const uint32_t cap_edges = n;                                               // every edge has a key
   const int end_bit = 2 * group_bits + 2;
-  const size_t temp_bytes = std::max<size_t>(AdjTempBytes(n, end_bit), 16);
+  const size_t temp_bytes = MaxBytes({SortKeysU64TempBytes(n, end_bit), HeadScanTempBytes<AdjHeads>(n)});
   const size_t node_bytes = (size_t)cap_nodes * sizeof(vsg_render_level_node);
   const size_t edge_bytes = (size_t)cap_edges * sizeof(vsg_render_level_edge);
   h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
@@ -77,11 +77,11 @@ void LevelAdjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level
   LaunchAdjClassify(lp.plane, W, H, group_bits, diagonal, true, n, keys, status, h->stream);
   VSG_HIP(hipGetLastError());
   h->adj.clock.Mark(ADJ_EMIT);
-  VSG_HIP(AdjSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
+  VSG_HIP(SortKeysU64(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
   h->adj.clock.Mark(ADJ_SORT);
   VSG_HIP(hipMemsetAsync(d_nodes, 0, node_bytes, h->stream));   // the counts are summed into them
   VSG_HIP(hipMemsetAsync(d_edges, 0, edge_bytes, h->stream));
-  VSG_HIP(AdjRank(h->d_sort_temp.p, temp_bytes, keys_sorted, group_bits, heads, n, h->stream));
+  VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, AdjHeads{keys_sorted, group_bits}, heads, n, h->stream));
   LaunchAdjTable(keys_sorted, heads, n, group_bits, lp.max_group, cap_nodes, cap_edges, lp.comp_table, d_nodes, d_edges,
                  status, h->stream);
   VSG_HIP(hipGetLastError());
@@ -91,9 +91,13 @@ void LevelAdjacency(vsg_render* h, const uint8_t* seg, size_t seg_len, int level
   const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && nodes && edges;
   if (to_device) {
     // the lengths of both lists are on the device: the copy decides there whether they fit
-    LaunchAdjCopy(d_nodes, d_edges, (uint32_t)std::min<size_t>(capacity_nodes, cap_nodes),
-                  (uint32_t)std::min<size_t>(capacity_edges, cap_edges), reinterpret_cast<int32_t*>(nodes),
-                  reinterpret_cast<int32_t*>(edges), status, h->stream);
+    CopyLists lists = {};
+    lists.list[0] = {d_nodes, reinterpret_cast<int32_t*>(nodes), kLevelNodeWords, &status->nodes, 0,
+                     (uint32_t)std::min<size_t>(capacity_nodes, cap_nodes)};
+    lists.list[1] = {d_edges, reinterpret_cast<int32_t*>(edges), kLevelEdgeWords, &status->edges, 0,
+                     (uint32_t)std::min<size_t>(capacity_edges, cap_edges)};
+    lists.flags = &status->flags;
+    LaunchCopyLists(lists, h->stream);
     VSG_HIP(hipGetLastError());
     ++launches;
   }

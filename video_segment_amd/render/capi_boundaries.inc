@@ -61,7 +61,7 @@ int vsg_render_level_boundaries(vsg_render* h, const uint8_t* seg, size_t seg_le
     const bool deliver = !count_only && points_fit;
     if (deliver && (!boundaries || !points)) Throw(VSG_ERR_INVALID, "an output is null");
     const int end_bit = 32 + BitsFor(lp.max_group, 32);
-    const size_t temp_bytes = std::max<size_t>(BoundTempBytes(n, end_bit), 16);
+    const size_t temp_bytes = MaxBytes({SortKeysU64TempBytes(n, end_bit), LevelTempBytes(n, end_bit)});
     const size_t record_bytes = (size_t)cap_records * sizeof(vsg_render_level_boundary);
     const size_t point_bytes = (size_t)n * 2 * sizeof(int32_t);
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
@@ -78,9 +78,9 @@ int vsg_render_level_boundaries(vsg_render* h, const uint8_t* seg, size_t seg_le
     LaunchBoundClassify(lp.plane, W, H, outer, true, n, keys, status, h->stream);
     VSG_HIP(hipGetLastError());
     h->bound.clock.Mark(BND_EMIT);
-    VSG_HIP(BoundSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
+    VSG_HIP(SortKeysU64(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, n, end_bit, h->stream));
     h->bound.clock.Mark(BND_SORT);
-    VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, keys_sorted, rank, n, h->stream));
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, HeadFlag{keys_sorted}, rank, n, h->stream));
     LaunchBoundTable(keys_sorted, rank, n, W, H, lp.max_group, cap_records, lp.comp_table, d_points, d_records, status,
                      h->stream);
     VSG_HIP(hipGetLastError());
@@ -88,8 +88,12 @@ int vsg_render_level_boundaries(vsg_render* h, const uint8_t* seg, size_t seg_le
     launches += 5;   // emit, the sort and the scan counted as one each, table, finish
     if (deliver && mem_out == VSG_MEM_DEVICE) {
       // the number of boundaries is on the device: the copy decides there whether they fit
-      LaunchBoundCopy(d_records, d_points, n, (uint32_t)std::min<size_t>(capacity_boundaries, cap_records),
-                      reinterpret_cast<int32_t*>(boundaries), points, status, h->stream);
+      CopyLists lists = {};
+      lists.list[0] = {d_records, reinterpret_cast<int32_t*>(boundaries), kLevelBoundaryWords, &status->boundaries, 0,
+                       (uint32_t)std::min<size_t>(capacity_boundaries, cap_records)};
+      lists.list[1] = {d_points, points, 2, nullptr, n, n};
+      lists.flags = &status->flags;
+      LaunchCopyLists(lists, h->stream);
       VSG_HIP(hipGetLastError());
       ++launches;
     } else if (deliver) {

@@ -11,6 +11,14 @@ struct ContourRun {
   int rounds;
 };
 
+// Work space of a contour call: the scan over `pixels` mask bytes, and the sort, both scans and the ranks of
+// `contours` contour slots.
+size_t ContourTempBytes(uint32_t pixels, int64_t contours, int end_bit) {
+  using namespace vsg_render_impl;
+  return MaxBytes({ContourClassifyTempBytes(pixels), SortKeysU64TempBytes(contours, end_bit),
+                   ExclusiveSumU32TempBytes((int)contours), LevelTempBytes(contours, end_bit)});
+}
+
 // vsg_render_level_contours; run: null, or what the mesh call goes on with.
 void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
                    vsg_render_level_contour* contours, size_t capacity_contours, size_t* num_contours,
@@ -35,7 +43,7 @@ void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
     vsg_render_contour_stats& ts = h->cont.stats;
     std::memset(&ts, 0, sizeof(ts));
     // the offsets' scan runs before the first synchronisation: its work space before anything is enqueued
-    const size_t scan_bytes = std::max<size_t>(ContourTempBytes(pixels, 1, 64), 16);
+    const size_t scan_bytes = ContourTempBytes(pixels, 1, 64);
     h->d_sort_temp.Reserve(scan_bytes, &h->allocations);
 
     // ---- the plane: the level's ids, or the indices of its regions' components ----
@@ -79,7 +87,7 @@ void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
     const int rounds = ContourRounds(n);
     const uint32_t cap = n / 4;   // a contour has four cracks or more
     const int end_bit = 32 + BitsFor(lp.max_group, 32);
-    const size_t temp_bytes = std::max<size_t>(ContourTempBytes(pixels, cap, end_bit), 16);
+    const size_t temp_bytes = ContourTempBytes(pixels, cap, end_bit);
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
     h->cont.cracks.Reserve((size_t)n * 36, &h->allocations);
     h->cont.slots.Reserve((size_t)cap * 28, &h->allocations);
@@ -107,8 +115,8 @@ void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
     VSG_HIP(hipMemsetAsync(ckeys, 0xff, (size_t)cap * sizeof(unsigned long long), h->stream));   // unused: last
     LaunchContourLeaders(leader, key, lp.plane, n, cap, ckeys, status, h->stream);
     VSG_HIP(hipGetLastError());
-    VSG_HIP(ContourSort(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cap, end_bit, h->stream));
-    VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, ckeys_sorted, crank, cap, h->stream));
+    VSG_HIP(SortKeysU64(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cap, end_bit, h->stream));
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, HeadFlag{ckeys_sorted}, crank, cap, h->stream));
     VSG_HIP(ContourVertices(h->d_sort_temp.p, temp_bytes, ckeys_sorted, key, succ, leader, ranked, n, cap, W, place,
                             count, first, d_vertices, owner, status, h->stream));
     VSG_HIP(hipGetLastError());
@@ -123,9 +131,12 @@ void LevelContours(vsg_render* h, const uint8_t* seg, size_t seg_len, int level,
     const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE && contours && vertices;
     if (to_device) {
       // the lengths of both lists are on the device: the copy decides there whether they fit
-      LaunchContourCopy(d_records, d_vertices, cap, n, (uint32_t)std::min<size_t>(capacity_contours, cap),
-                        (uint32_t)std::min<size_t>(capacity_vertices, n), reinterpret_cast<int32_t*>(contours),
-                        vertices, status, h->stream);
+      CopyLists lists = {};
+      lists.list[0] = {d_records, reinterpret_cast<int32_t*>(contours), kLevelContourWords, &status->contours, 0,
+                       (uint32_t)std::min<size_t>(capacity_contours, cap)};
+      lists.list[1] = {d_vertices, vertices, 2, &status->vertices, 0, (uint32_t)std::min<size_t>(capacity_vertices, n)};
+      lists.flags = &status->flags;
+      LaunchCopyLists(lists, h->stream);
       VSG_HIP(hipGetLastError());
       ++launches;
     }
@@ -217,6 +228,12 @@ struct MeshRun {
   uint32_t segments, vertices, loops, refs;
 };
 
+// Work space of the sort of `items` segment keys and of a scan over as many counts.
+size_t MeshTempBytes(int64_t items, int end_bit) {
+  using namespace vsg_render_impl;
+  return MaxBytes({SortKeysU64TempBytes(items, end_bit), ExclusiveSumU32TempBytes((int)items)});
+}
+
 // vsg_render_level_mesh; left: null, or what the simplified call goes on with.
 void LevelMesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int connectedness,
                vsg_render_mesh_segment* segments, size_t capacity_segments, size_t* num_segments, int32_t* vertices,
@@ -268,7 +285,7 @@ void LevelMesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int
     // ---- split: junctions, the third doubling, halves, owners ----
     // sized for every crack and for what is scanned here: the library's need is not promised to grow with the
     // number of items
-    size_t temp_bytes = std::max<size_t>(std::max(MeshTempBytes(n, end_bit), MeshTempBytes(C, end_bit)), 16);
+    size_t temp_bytes = std::max(MeshTempBytes(n, end_bit), MeshTempBytes(C, end_bit));
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
     // seen: [0] after the split, [1] at the end
     auto [status, seen] = ReserveStatusPair<MeshStatus>(h, &h->mesh.status, &h->mesh.seen);
@@ -331,9 +348,14 @@ void LevelMesh(vsg_render* h, const uint8_t* seg, size_t seg_len, int level, int
       // the number of vertices is on the device: the copy decides there whether they fit.  Counted whether or
       // not the other three lists fit
       if (fits) {
-        LaunchMeshCopy(t, S, C, R, (uint32_t)std::min<size_t>(capacity_vertices, slots),
-                       reinterpret_cast<int32_t*>(segments), vertices, reinterpret_cast<int32_t*>(loops), refs, status,
-                       h->stream);
+        CopyLists lists = {};
+        lists.list[0] = {t.segments, reinterpret_cast<int32_t*>(segments), kMeshSegmentWords, nullptr, S, S};
+        lists.list[1] = {t.vertices, vertices, 2, &status->vertices, 0,
+                         (uint32_t)std::min<size_t>(capacity_vertices, slots)};
+        lists.list[2] = {t.loops, reinterpret_cast<int32_t*>(loops), kMeshLoopWords, nullptr, C, C};
+        lists.list[3] = {t.refs, refs, 1, nullptr, R, R};
+        lists.flags = &status->flags;
+        LaunchCopyLists(lists, h->stream);
         VSG_HIP(hipGetLastError());
       }
       ++launches;

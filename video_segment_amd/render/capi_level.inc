@@ -178,7 +178,7 @@ void SortLevelRuns(vsg_render* h, LevelFront* f, vsg_render_level_stats* ls) {
   using namespace vsg_render_impl;
   const uint32_t n = f->n;
   const int end_bit = 32 + BitsFor((uint64_t)f->max_id, 31);
-  const size_t temp_bytes = std::max<size_t>(LevelTempBytes(n, end_bit), 16);
+  const size_t temp_bytes = LevelTempBytes(n, end_bit);
   h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
   h->lvl.sorted.Reserve((size_t)n * 16, &h->allocations);
   h->lvl.regions.Reserve((size_t)f->cap_regions * sizeof(vsg_render_level_region), &h->allocations);
@@ -189,10 +189,10 @@ void SortLevelRuns(vsg_render* h, LevelFront* f, vsg_render_level_stats* ls) {
   f->regions = h->lvl.regions.As<int32_t>();
   f->intervals = h->lvl.intervals.As<Interval>();
   h->lvl.clock.Begin(h->stream);
-  VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, f->keys, f->keys_sorted, f->rights, f->rights_sorted, n, end_bit,
-                    h->stream));
+  VSG_HIP(SortPairsU64U32(h->d_sort_temp.p, temp_bytes, f->keys, f->keys_sorted, f->rights, f->rights_sorted, n,
+                          end_bit, h->stream));
   h->lvl.clock.Mark(LVL_SORT);
-  VSG_HIP(LevelRank(h->d_sort_temp.p, temp_bytes, f->keys_sorted, f->rank, n, h->stream));
+  VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, HeadFlag{f->keys_sorted}, f->rank, n, h->stream));
   LaunchLevelTable(f->keys_sorted, f->rights_sorted, f->rank, n, h->W, f->cap_regions, f->intervals, f->regions,
                    f->status, h->stream);
   VSG_HIP(hipGetLastError());
@@ -243,7 +243,7 @@ void LevelComponents(vsg_render* h, const uint8_t* seg, size_t seg_len, int leve
   if (n) {
     // ---- the runs sorted by (id, y, left_x), as vsg_render_level_regions has them ----
     const int label_bits = BitsFor((uint64_t)(n - 1), 32);
-    const size_t temp_bytes = std::max<size_t>(CompTempBytes(n, label_bits), 16);
+    const size_t temp_bytes = MaxBytes({SortPairsU32U32TempBytes(n, label_bits), HeadScanTempBytes<LabelHead>(n)});
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);   // before anything that uses the block is enqueued
     SortLevelRuns(h, &f, &ls);
 
@@ -268,8 +268,8 @@ void LevelComponents(vsg_render* h, const uint8_t* seg, size_t seg_len, int leve
                    label, index, status, h->stream);
     VSG_HIP(hipGetLastError());
     h->comp.clock.Mark(CMP_LINK);
-    VSG_HIP(CompSort(h->d_sort_temp.p, temp_bytes, label, label_sorted, index, order, n, label_bits, h->stream));
-    VSG_HIP(CompRank(h->d_sort_temp.p, temp_bytes, label_sorted, comp_rank, n, h->stream));
+    VSG_HIP(SortPairsU32U32(h->d_sort_temp.p, temp_bytes, label, label_sorted, index, order, n, label_bits, h->stream));
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, LabelHead{label_sorted}, comp_rank, n, h->stream));
     // a run has at most one component: n slots hold them all
     LaunchCompTable(label_sorted, order, comp_rank, f.rank, f.intervals, n, n, f.cap_regions, ordered, fill, table,
                     h->comp.first.As<uint32_t>(), f.status, status, h->stream);
@@ -451,8 +451,11 @@ int vsg_render_level_regions(vsg_render* h, const uint8_t* seg, size_t seg_len, 
       }
       if (deliver && mem_out == VSG_MEM_DEVICE) {
         // the number of regions is on the device: the copy decides there whether they fit
-        LaunchLevelCopy(d_regions, d_intervals, n, (uint32_t)std::min<size_t>(capacity_regions, cap_regions),
-                        reinterpret_cast<int32_t*>(regions), intervals, status, h->stream);
+        CopyLists lists = {};
+        lists.list[0] = {d_regions, reinterpret_cast<int32_t*>(regions), kLevelRegionWords, &status->regions, 0,
+                         (uint32_t)std::min<size_t>(capacity_regions, cap_regions)};
+        lists.list[1] = {reinterpret_cast<const int32_t*>(d_intervals), intervals, 4, nullptr, n, n};
+        LaunchCopyLists(lists, h->stream);
         VSG_HIP(hipGetLastError());
         ++h->lvl.stats.launches;
       } else if (deliver) {

@@ -78,7 +78,8 @@ int vsg_render_level_overlap(vsg_render* h, const uint8_t* seg, size_t seg_len, 
     const uint32_t m = (uint32_t)std::min<uint64_t>(n, (lp.groups_bound + 1) * ((uint64_t)max_label + 2));
     const uint32_t cap_rows = (uint32_t)std::min<uint64_t>(lp.groups_bound, n);   // every group has a run
     if (seen[0].covered && cap_rows == 0) Throw(VSG_ERR_INTERNAL, "the plane has groups the desc has no ids for");
-    const size_t temp_bytes = std::max<size_t>(std::max(LevelTempBytes(n, end_bit), OverlapScanTempBytes(n)), 16);
+    const size_t temp_bytes = MaxBytes({LevelTempBytes(n, end_bit), HeadScanTempBytes<OvlRowHeads>(n),
+                                        HeadScanTempBytes<OvlKeyHeads>(n), HeadScanTempBytes<OvlColHeads>(n)});
     const size_t row_bytes = (size_t)cap_rows * sizeof(vsg_render_overlap_row);
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
     h->ovl.runs.Reserve((size_t)n * 2 * 12, &h->allocations);
@@ -114,18 +115,19 @@ int vsg_render_level_overlap(vsg_render* h, const uint8_t* seg, size_t seg_len, 
                       status, h->stream);
     VSG_HIP(hipGetLastError());
     h->ovl.clock.Mark(OVL_EMIT);
-    VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, lengths, lengths_sorted, n, end_bit,
-                      h->stream));
+    VSG_HIP(SortPairsU64U32(h->d_sort_temp.p, temp_bytes, keys, keys_sorted, lengths, lengths_sorted, n, end_bit,
+                            h->stream));
     h->ovl.clock.Mark(OVL_SORT);
     if (row_bytes) VSG_HIP(hipMemsetAsync(d_rows, 0, row_bytes, h->stream));   // `unlabelled` of a row without any
-    VSG_HIP(OverlapRank(h->d_sort_temp.p, temp_bytes, keys_sorted, lengths_sorted, group_bits, label_bits, row_heads,
-                        key_heads, n, h->stream));
+    const OvlBits bits{group_bits, label_bits};
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, OvlRowHeads{keys_sorted, bits}, row_heads, n, h->stream));
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, OvlKeyHeads{keys_sorted, lengths_sorted}, key_heads, n, h->stream));
     LaunchOverlapTable(keys_sorted, lengths_sorted, row_heads, key_heads, n, m, group_bits, label_bits, lp.max_group,
                        cap_rows, lp.comp_table, dkey, dstart, drank, d_rows, d_pairs, ckeys, cvals, status, h->stream);
     VSG_HIP(hipGetLastError());
-    VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cvals, cvals_sorted, m, end_bit, h->stream));
-    VSG_HIP(OverlapColRank(h->d_sort_temp.p, temp_bytes, ckeys_sorted, group_bits, label_bits, col_rank, m,
-                           h->stream));
+    VSG_HIP(SortPairsU64U32(h->d_sort_temp.p, temp_bytes, ckeys, ckeys_sorted, cvals, cvals_sorted, m, end_bit,
+                            h->stream));
+    VSG_HIP(HeadScan(h->d_sort_temp.p, temp_bytes, OvlColHeads{ckeys_sorted, bits}, col_rank, m, h->stream));
     LaunchOverlapCols(ckeys_sorted, cvals_sorted, col_rank, dstart, drank, m, group_bits, label_bits, cfirst, d_cols,
                       d_pairs, status, h->stream);
     VSG_HIP(hipGetLastError());
@@ -135,10 +137,15 @@ int vsg_render_level_overlap(vsg_render* h, const uint8_t* seg, size_t seg_len, 
     const bool to_device = !count_only && mem_out == VSG_MEM_DEVICE;
     if (to_device) {
       // the lengths of the lists are on the device: the copy decides there whether they fit
-      LaunchOverlapCopy(d_rows, d_cols, d_pairs, rows ? (uint32_t)std::min<size_t>(capacity_rows, cap_rows) : 0u,
-                        cols ? (uint32_t)std::min<size_t>(capacity_cols, m) : 0u,
-                        pairs ? (uint32_t)std::min<size_t>(capacity_pairs, m) : 0u, reinterpret_cast<int32_t*>(rows),
-                        reinterpret_cast<int32_t*>(cols), reinterpret_cast<int32_t*>(pairs), status, h->stream);
+      CopyLists lists = {};
+      lists.list[0] = {d_rows, reinterpret_cast<int32_t*>(rows), kOverlapRowWords, &status->rows, 0,
+                       rows ? (uint32_t)std::min<size_t>(capacity_rows, cap_rows) : 0u};
+      lists.list[1] = {d_cols, reinterpret_cast<int32_t*>(cols), kOverlapColWords, &status->cols, 0,
+                       cols ? (uint32_t)std::min<size_t>(capacity_cols, m) : 0u};
+      lists.list[2] = {d_pairs, reinterpret_cast<int32_t*>(pairs), kOverlapPairWords, &status->pairs, 0,
+                       pairs ? (uint32_t)std::min<size_t>(capacity_pairs, m) : 0u};
+      lists.flags = &status->flags;
+      LaunchCopyLists(lists, h->stream);
       VSG_HIP(hipGetLastError());
       ++launches;
     }

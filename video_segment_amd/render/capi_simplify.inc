@@ -43,7 +43,7 @@ int vsg_render_level_mesh_simplified(vsg_render* h, const uint8_t* seg, size_t s
     // ---- blocks: a segment keeps one vertex more than it has at the most ----
     if ((uint64_t)V + S > 0xffffffffull) Throw(VSG_ERR_INVALID, "the level has more than 2^32 - 1 vertices and segments");
     const uint32_t slots = V + S;
-    const size_t temp_bytes = std::max<size_t>(SimplifyTempBytes(S), 16);
+    const size_t temp_bytes = MaxBytes({ExclusiveSumU32TempBytes((int)S)});
     h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
     // seen: [1] at the end
     auto [status, seen] = ReserveStatusPair<SimplifyStatus>(h, &h->simp.status, &h->simp.seen);
@@ -87,9 +87,14 @@ int vsg_render_level_mesh_simplified(vsg_render* h, const uint8_t* seg, size_t s
       // the number of vertices is on the device: the copy decides there whether they fit.  Counted whether or
       // not the other three lists fit
       if (fits) {
-        LaunchSimplifyCopy(d_segments, d_vertices, run.t.loops, run.t.refs, S, C, R, slots,
-                           (uint32_t)std::min<size_t>(capacity_vertices, slots), reinterpret_cast<int32_t*>(segments),
-                           vertices, reinterpret_cast<int32_t*>(loops), refs, status, h->stream);
+        CopyLists lists = {};
+        lists.list[0] = {d_segments, reinterpret_cast<int32_t*>(segments), kMeshSegmentWords, nullptr, S, S};
+        lists.list[1] = {d_vertices, vertices, 2, &status->vertices_out, 0,
+                         (uint32_t)std::min<size_t>(capacity_vertices, slots)};
+        lists.list[2] = {run.t.loops, reinterpret_cast<int32_t*>(loops), kMeshLoopWords, nullptr, C, C};
+        lists.list[3] = {run.t.refs, refs, 1, nullptr, R, R};
+        lists.flags = &status->flags;
+        LaunchCopyLists(lists, h->stream);
         VSG_HIP(hipGetLastError());
       }
       ++launches;

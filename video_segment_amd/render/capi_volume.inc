@@ -57,7 +57,7 @@ int ResortVolumeTable(vsg_render* h, Block (&keys)[2], Block (&records)[2], int*
   using namespace vsg_render_impl;
   VolumeState& v = h->vol;
   const int from = *at, to = 1 - from;
-  const size_t temp_bytes = std::max<size_t>(LevelTempBytes(n, end_bit), 16);
+  const size_t temp_bytes = LevelTempBytes(n, end_bit);
   h->d_sort_temp.Reserve(temp_bytes, &h->allocations);
   keys[to].Reserve(keys[from].cap, &h->allocations);
   records[to].Reserve(records[from].cap, &h->allocations);
@@ -65,8 +65,8 @@ int ResortVolumeTable(vsg_render* h, Block (&keys)[2], Block (&records)[2], int*
   uint32_t* perm_in = v.perm.As<uint32_t>();
   uint32_t* perm_out = perm_in + n;
   LaunchVolumeIota(perm_in, n, h->stream);
-  VSG_HIP(LevelSort(h->d_sort_temp.p, temp_bytes, keys[from].As<unsigned long long>(),
-                    keys[to].As<unsigned long long>(), perm_in, perm_out, n, end_bit, h->stream));
+  VSG_HIP(SortPairsU64U32(h->d_sort_temp.p, temp_bytes, keys[from].As<unsigned long long>(),
+                          keys[to].As<unsigned long long>(), perm_in, perm_out, n, end_bit, h->stream));
   LaunchVolumeGather(records[from].p, records[to].p, perm_out, n, record_bytes, h->stream);
   VSG_HIP(hipGetLastError());
   *at = to;

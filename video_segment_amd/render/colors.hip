@@ -2,7 +2,7 @@
 //
 // Input is what the level and component pipelines leave on the device: the interval list
 // {y, left_x, right_x, id} grouped by record in record order, and the 1-based record of every interval
-// (LevelRank's or CompRank's scan).  The plane P is not read again; the frame F is read once.
+// (the scan of HeadFlag or LabelHead).  The plane P is not read again; the frame F is read once.
 //
 //   k_color_runs       a wavefront per 64 intervals (fewer when the list is short, so that the chip is
 //                      filled all the same): one partial per interval (three sums, three sums of
@@ -17,6 +17,7 @@
 //
 // Everything is integer arithmetic; no result depends on the order of execution.
 #include "render.h"
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -292,11 +293,8 @@ __global__ __launch_bounds__(256) void k_color_finish(const ColorAcc* __restrict
       out[17] = (int32_t)(a.hi[1] | a.hi[2] << 8);   // reserved1 = 0
     }
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) {
-    covered += __shfl_xor(covered, s);
-    largest = max(largest, __shfl_xor(largest, s));
-  }
+  covered = WaveSum(covered);
+  largest = WaveMax(largest);
   if ((threadIdx.x & 63) == 0 && covered) {
     atomicAdd(&status->covered, covered);
     atomicMax(&status->largest, largest);

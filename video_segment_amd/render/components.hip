@@ -23,8 +23,7 @@
 // the same root, of which there are fewer than n in a launch.  Both loops are counted against n and
 // give up with COMP_FLAG_BOUND when the count runs out; no thread waits for another.
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -109,7 +108,7 @@ __global__ __launch_bounds__(256) void k_comp_link(const unsigned long long* __r
     }
   }
   // one add per wavefront
-  for (int s = 32; s > 0; s >>= 1) links += __shfl_xor(links, s);
+  links = WaveSum(links);
   if ((threadIdx.x & 63) == 0 && links) atomicAdd(&status->links, (unsigned long long)links);
 }
 
@@ -122,14 +121,6 @@ __global__ __launch_bounds__(256) void k_comp_flatten(uint32_t* __restrict__ par
   label[i] = root == kNoRoot ? i : root;   // a label is always a run index; the flag fails the call
   index[i] = i;
 }
-
-struct LabelHead {
-  const uint32_t* label;
-  __host__ __device__ uint32_t operator()(uint32_t k) const {
-    return (k == 0 || label[k] != label[k - 1]) ? 1u : 0u;
-  }
-};
-typedef hipcub::TransformInputIterator<uint32_t, LabelHead, hipcub::CountingInputIterator<uint32_t>> LabelHeadIterator;
 
 // One thread per ordered position k.  order[k] < n is the sorted run there, label[k] its component's
 // root, comp_rank[k] the number of heads in [0, k], region_rank[i] the (1-based) region of sorted run i.
@@ -203,27 +194,6 @@ void LaunchCompLink(const unsigned long long* keys_sorted, const uint32_t* right
   hipLaunchKernelGGL(k_comp_init, grid, block, 0, stream, parent, n);
   hipLaunchKernelGGL(k_comp_link, grid, block, 0, stream, keys_sorted, rights_sorted, n, width, slack, parent, status);
   hipLaunchKernelGGL(k_comp_flatten, grid, block, 0, stream, parent, n, label, index, status);
-}
-
-size_t CompTempBytes(int64_t n, int end_bit) {
-  size_t sort_bytes = 0, scan_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const uint32_t*)nullptr, (uint32_t*)nullptr,
-                                           (const uint32_t*)nullptr, (uint32_t*)nullptr, n, 0, end_bit,
-                                           (hipStream_t) nullptr);
-  LabelHeadIterator heads(hipcub::CountingInputIterator<uint32_t>(0), LabelHead{nullptr});
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, heads, (uint32_t*)nullptr, n, (hipStream_t) nullptr);
-  return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-}
-
-hipError_t CompSort(void* temp, size_t temp_bytes, const uint32_t* label, uint32_t* label_sorted,
-                    const uint32_t* index, uint32_t* order, int64_t n, int end_bit, hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, label, label_sorted, index, order, n, 0, end_bit, stream);
-}
-
-hipError_t CompRank(void* temp, size_t temp_bytes, const uint32_t* label_sorted, uint32_t* comp_rank, int64_t n,
-                    hipStream_t stream) {
-  LabelHeadIterator heads(hipcub::CountingInputIterator<uint32_t>(0), LabelHead{label_sorted});
-  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, heads, comp_rank, n, stream);
 }
 
 void LaunchCompTable(const uint32_t* label_sorted, const uint32_t* order, const uint32_t* comp_rank,

@@ -15,7 +15,7 @@
 //                        other crack at its successor with weight 1 when it is a turn
 //   k_contour_round<1>   the same rounds: {next, turn cracks from here up to the leader}
 //   k_contour_leaders    one key group << 32 | leader per contour, in no order; one add per wavefront
-//   radix sort, scan     the contours in (group, leader) order; their groups' ranks (LevelRank of level.hip)
+//   radix sort, scan     the contours in (group, leader) order; their groups' ranks (HeadFlag of render_scan.h)
 //   k_contour_heads      one thread per contour: its number of vertices, its place for its leader to find
 //   scan                 first_vertex
 //   k_contour_vertices   one thread per crack: a turn crack writes its start corner at first_vertex + rank
@@ -24,13 +24,14 @@
 //                        reduced per contour inside the wavefront, then integer atomics per wavefront and
 //                        contour
 //   k_contour_finish     holes and the longest contour
-//   k_contour_copy       records and vertices to the caller's device memory, if both fit
+//   k_copy_lists         of lists.hip: records and vertices to the caller's device memory, if both fit
 //
 // No thread follows a contour: every kernel is one thread per pixel, crack, contour or vertex with a bounded
 // amount of work.  Everything is an integer; sums are exact and the atomics (add, min, max) commute, so the
 // result does not depend on the order of execution.  Every index that was read from memory is checked
 // against its array before it is used.
 #include "render.h"
+#include "render_device.h"
 
 #include <algorithm>
 #include <utility>
@@ -44,16 +45,6 @@ namespace {
 constexpr int kContourBlock = 256;
 constexpr uint32_t kTurnBit = 0x80000000u;
 constexpr uint32_t kNone = 0xffffffffu;
-
-// direction of travel along side s of a pixel: top +x, right +y, bottom -x, left -y.  The pixel across
-// side s lies at Dx(s + 3), Dy(s + 3).
-__device__ __forceinline__ int Dx(int s) { return (s & 3) == 0 ? 1 : (s & 3) == 2 ? -1 : 0; }
-__device__ __forceinline__ int Dy(int s) { return (s & 3) == 1 ? 1 : (s & 3) == 3 ? -1 : 0; }
-
-// P at frame position (x, y); -1 outside the frame.
-__device__ __forceinline__ int32_t PlaneAt(const int32_t* __restrict__ plane, int W, int H, int x, int y) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? plane[(size_t)y * W + x] : -1;
-}
 
 __global__ __launch_bounds__(kContourBlock) void k_contour_classify(const int32_t* __restrict__ plane, int W, int H,
                                                                     uint8_t* __restrict__ mask,
@@ -72,7 +63,7 @@ __global__ __launch_bounds__(kContourBlock) void k_contour_classify(const int32_
     mask[p] = (uint8_t)m;
   }
   uint32_t count = (uint32_t)__popc(m);
-  for (int s = 32; s > 0; s >>= 1) count += __shfl_xor(count, s);
+  count = WaveSum(count);
   if ((threadIdx.x & 63) == 0) s_wave[threadIdx.x >> 6] = count;
   __syncthreads();
   if (threadIdx.x == 0) {
@@ -356,29 +347,10 @@ __global__ __launch_bounds__(kContourBlock) void k_contour_finish(const int32_t*
     hole = rec[11] < 0;   // the high word of area2
   }
   const uint32_t holes = (uint32_t)__popcll(__ballot(hole));
-  for (int s = 32; s > 0; s >>= 1) length = max(length, (uint32_t)__shfl_xor(length, s));
+  length = WaveMax(length);
   if ((threadIdx.x & 63) == 0) {
     if (holes) atomicAdd(&status->holes, holes);
     if (length) atomicMax(&status->largest, length);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_contour_copy(const int32_t* __restrict__ records,
-                                                      const int32_t* __restrict__ vertices, uint32_t capacity,
-                                                      uint32_t n, uint32_t capacity_records, uint32_t capacity_vertices,
-                                                      int32_t* __restrict__ records_out,
-                                                      int32_t* __restrict__ vertices_out,
-                                                      const ContourStatus* __restrict__ status) {
-  const uint32_t n_records = status->contours, n_vertices = status->vertices;
-  if (n_records > capacity_records || n_vertices > capacity_vertices || n_records > capacity || n_vertices > n ||
-      status->flags) {
-    return;
-  }
-  const size_t record_words = (size_t)n_records * kLevelContourWords, vertex_words = (size_t)n_vertices * 2;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < record_words + vertex_words; k += step) {
-    if (k < record_words) records_out[k] = records[k];
-    else vertices_out[k - record_words] = vertices[k - record_words];
   }
 }
 
@@ -386,16 +358,11 @@ inline dim3 GridOf(uint32_t n) { return dim3((n + kContourBlock - 1) / kContourB
 
 }  // namespace
 
-size_t ContourTempBytes(uint32_t pixels, int64_t contours, int end_bit) {
-  size_t offsets = 0, sort = 0, firsts = 0;
+size_t ContourClassifyTempBytes(uint32_t pixels) {
+  size_t offsets = 0;
   (void)hipcub::DeviceScan::ExclusiveSum(nullptr, offsets, MaskIterator((const uint8_t*)nullptr, MaskCount()), (uint32_t*)nullptr,
                                          (int)pixels, (hipStream_t) nullptr);
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort, (const unsigned long long*)nullptr,
-                                          (unsigned long long*)nullptr, contours, 0, end_bit, (hipStream_t) nullptr);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, firsts, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)contours,
-                                         (hipStream_t) nullptr);
-  const size_t rank = LevelTempBytes(contours, end_bit);
-  return std::max(std::max(offsets, sort), std::max(firsts, rank));
+  return offsets;
 }
 
 hipError_t ContourClassify(void* temp, size_t temp_bytes, const int32_t* plane, int width, int height, uint8_t* mask,
@@ -451,18 +418,13 @@ void LaunchContourLeaders(const uint32_t* leader, const uint32_t* key, const int
                      ckeys, status);
 }
 
-hipError_t ContourSort(void* temp, size_t temp_bytes, const unsigned long long* ckeys, unsigned long long* ckeys_sorted,
-                       int64_t capacity, int end_bit, hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, ckeys, ckeys_sorted, capacity, 0, end_bit, stream);
-}
-
 hipError_t ContourVertices(void* temp, size_t temp_bytes, const unsigned long long* ckeys_sorted, const uint32_t* key,
                            const uint32_t* succ, const uint32_t* leader, const uint2* ranked, uint32_t n,
                            uint32_t capacity, int width, uint32_t* place, uint32_t* count, uint32_t* first,
                            int32_t* vertices, uint32_t* owner, ContourStatus* status, hipStream_t stream) {
   hipLaunchKernelGGL(k_contour_heads, GridOf(capacity), dim3(kContourBlock), 0, stream, ckeys_sorted, succ, ranked, n,
                      capacity, count, place, status);
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, count, first, (int)capacity, stream);
+  const hipError_t e = ExclusiveSumU32(temp, temp_bytes, count, first, (int)capacity, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_contour_vertices, GridOf(n), dim3(kContourBlock), 0, stream, key, leader, ranked, place, count,
                      first, n, capacity, width, reinterpret_cast<int2*>(vertices), owner, status);
@@ -478,15 +440,6 @@ void LaunchContourTable(const unsigned long long* ckeys_sorted, const uint32_t* 
   hipLaunchKernelGGL(k_contour_measure, GridOf(n), dim3(kContourBlock), 0, stream,
                      reinterpret_cast<const int2*>(vertices), owner, count, first, n, capacity, records, status);
   hipLaunchKernelGGL(k_contour_finish, GridOf(capacity), dim3(kContourBlock), 0, stream, records, capacity, status);
-}
-
-void LaunchContourCopy(const int32_t* records, const int32_t* vertices, uint32_t capacity, uint32_t n,
-                       uint32_t capacity_records, uint32_t capacity_vertices, int32_t* records_out,
-                       int32_t* vertices_out, const ContourStatus* status, hipStream_t stream) {
-  const size_t words = (size_t)capacity_vertices * 2 + (size_t)capacity_records * kLevelContourWords;
-  const size_t groups = std::max<size_t>((words + 255) / 256, 1);
-  hipLaunchKernelGGL(k_contour_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, records,
-                     vertices, capacity, n, capacity_records, capacity_vertices, records_out, vertices_out, status);
 }
 
 }  // namespace vsg_render_impl

@@ -10,13 +10,12 @@
 //                    also writes its region's id and first interval
 //   k_level_moments  one wavefront per region: area, bounding box, and the reference's six f32 sums
 //                    in interval order (also run per connected component, on the table of components.hip)
-//   k_level_copy     regions and intervals to the caller's device memory, if the regions fit
+//   k_copy_lists     of lists.hip: regions and intervals to the caller's device memory, if the regions fit
 //
 // The moments' arithmetic is the reference's, operation for operation; every operation is rounded on
 // its own (the file is compiled with -ffp-contract=off, and the rounding intrinsics say so again).
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -97,14 +96,6 @@ __global__ __launch_bounds__(kRunsBlock) void k_level_runs(const int32_t* __rest
 __device__ __forceinline__ bool IsHead(const unsigned long long* keys, uint32_t i) {
   return i == 0 || (uint32_t)(keys[i] >> 32) != (uint32_t)(keys[i - 1] >> 32);
 }
-
-struct HeadFlag {
-  const unsigned long long* keys;
-  __host__ __device__ uint32_t operator()(uint32_t i) const {
-    return (i == 0 || (uint32_t)(keys[i] >> 32) != (uint32_t)(keys[i - 1] >> 32)) ? 1u : 0u;
-  }
-};
-typedef hipcub::TransformInputIterator<uint32_t, HeadFlag, hipcub::CountingInputIterator<uint32_t>> HeadIterator;
 
 // One thread per sorted run.  rank[i] = number of segment heads in [0, i]: the region of run i is
 // rank[i] - 1.  n <= capacity of every array; a region index is below n.
@@ -193,13 +184,11 @@ __global__ __launch_bounds__(256) void k_level_moments(const int4* __restrict__ 
       moment_xx = __fadd_rn(moment_xx, LaneValue(t_xx, j));
     }
   }
-  for (int s = 32; s > 0; s >>= 1) {
-    area += __shfl_xor(area, s);
-    min_x = min(min_x, __shfl_xor(min_x, s));
-    min_y = min(min_y, __shfl_xor(min_y, s));
-    max_x = max(max_x, __shfl_xor(max_x, s));
-    max_y = max(max_y, __shfl_xor(max_y, s));
-  }
+  area = WaveSum(area);
+  min_x = WaveMin(min_x);
+  min_y = WaveMin(min_y);
+  max_x = WaveMax(max_x);
+  max_y = WaveMax(max_y);
   if (lane == 0) {
     const float inv_area = __fdiv_rn(1.0f, area_sum);
     out[2] = (int32_t)(end - first);
@@ -218,51 +207,12 @@ __global__ __launch_bounds__(256) void k_level_moments(const int4* __restrict__ 
   }
 }
 
-// Both lists to the caller's device memory, or neither: the number of regions is known on the device
-// only.  Dword copies, grid-stride.
-__global__ __launch_bounds__(256) void k_level_copy(const int32_t* __restrict__ regions,
-                                                    const int32_t* __restrict__ intervals, uint32_t n,
-                                                    uint32_t capacity_regions, int32_t* __restrict__ regions_out,
-                                                    int32_t* __restrict__ intervals_out,
-                                                    const LevelStatus* __restrict__ status) {
-  const uint32_t n_regions = status->regions;
-  if (n_regions > capacity_regions) return;
-  const size_t region_words = (size_t)n_regions * kLevelRegionWords, interval_words = (size_t)n * 4;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < region_words + interval_words; k += step) {
-    if (k < region_words) regions_out[k] = regions[k];
-    else intervals_out[k - region_words] = intervals[k - region_words];
-  }
-}
-
 }  // namespace
 
 void LaunchLevelRuns(const int32_t* plane, int pitch, int width, int height, uint32_t capacity,
                      unsigned long long* keys, uint32_t* rights, LevelStatus* status, hipStream_t stream) {
   hipLaunchKernelGGL(k_level_runs, dim3(height), dim3(kRunsBlock), 0, stream, plane, pitch, width, capacity, keys,
                      rights, status);
-}
-
-size_t LevelTempBytes(int64_t n, int end_bit) {
-  size_t sort_bytes = 0, scan_bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, sort_bytes, (const unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (const uint32_t*)nullptr,
-                                           (uint32_t*)nullptr, n, 0, end_bit, (hipStream_t) nullptr);
-  HeadIterator heads(hipcub::CountingInputIterator<uint32_t>(0), HeadFlag{nullptr});
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, scan_bytes, heads, (uint32_t*)nullptr, n, (hipStream_t) nullptr);
-  return sort_bytes > scan_bytes ? sort_bytes : scan_bytes;
-}
-
-hipError_t LevelSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                     const uint32_t* rights_in, uint32_t* rights_out, int64_t n, int end_bit, hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, rights_in, rights_out, n, 0, end_bit,
-                                            stream);
-}
-
-hipError_t LevelRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, uint32_t* rank, int64_t n,
-                     hipStream_t stream) {
-  HeadIterator heads(hipcub::CountingInputIterator<uint32_t>(0), HeadFlag{keys_sorted});
-  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, heads, rank, n, stream);
 }
 
 void LaunchLevelTable(const unsigned long long* keys_sorted, const uint32_t* rights_sorted, const uint32_t* rank,
@@ -289,16 +239,6 @@ void LaunchComponentMoments(const Interval* intervals, uint32_t n, uint32_t capa
   hipLaunchKernelGGL((k_level_moments<kLevelComponentWords, 3>), dim3(blocks), dim3(256), 0, stream,
                      reinterpret_cast<const int4*>(intervals), n, capacity_components, components,
                      &status->components, &status->largest);
-}
-
-void LaunchLevelCopy(const int32_t* regions, const Interval* intervals, uint32_t n, uint32_t capacity_regions,
-                     int32_t* regions_out, int32_t* intervals_out, const LevelStatus* status, hipStream_t stream) {
-  if (n == 0) return;
-  const size_t words = (size_t)n * (4 + kLevelRegionWords);   // regions <= n
-  const size_t groups = (words + 255) / 256;
-  hipLaunchKernelGGL(k_level_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, regions,
-                     reinterpret_cast<const int32_t*>(intervals), n, capacity_regions, regions_out, intervals_out,
-                     status);
 }
 
 }  // namespace vsg_render_impl

@@ -27,16 +27,15 @@
 //   k_mesh_measure      one thread per vertex: its side's length, reduced per segment inside the wavefront,
 //                       then one integer add per wavefront and segment
 //   k_mesh_finish       one thread per segment: closed, shared and the longest, one atomic each per wavefront
-//   k_mesh_copy         the four lists to the caller's device memory, if all four fit
+//   k_copy_lists        of lists.hip: the four lists to the caller's device memory, if all four fit
 //
 // No thread walks a contour or a segment.  Everything is an integer, the atomics are add and max, and where
 // several threads store to one word they store the same value.  Every index read from memory is checked
 // against its array before it is used.
 #include "render.h"
+#include "render_device.h"
 
 #include <algorithm>
-
-#include <hipcub/hipcub.hpp>
 
 namespace vsg_render_impl {
 
@@ -46,13 +45,6 @@ constexpr int kMeshBlock = 256;
 constexpr uint32_t kNone = 0xffffffffu;
 constexpr uint32_t kKeyMask = 0x7fffffffu;
 constexpr uint8_t kHeadBit = 0x80;
-
-__device__ __forceinline__ int Dx(int s) { return (s & 3) == 0 ? 1 : (s & 3) == 2 ? -1 : 0; }
-__device__ __forceinline__ int Dy(int s) { return (s & 3) == 1 ? 1 : (s & 3) == 3 ? -1 : 0; }
-
-__device__ __forceinline__ int32_t PlaneAt(const int32_t* __restrict__ plane, int W, int H, int x, int y) {
-  return (x >= 0 && x < W && y >= 0 && y < H) ? plane[(size_t)y * W + x] : -1;
-}
 
 __device__ __forceinline__ void Flag(MeshStatus* status) { atomicOr(&status->flags, (uint32_t)MESH_FLAG_RANGE); }
 
@@ -436,31 +428,11 @@ __global__ __launch_bounds__(kMeshBlock) void k_mesh_finish(const int32_t* __res
     shared = rec[1] >= 0;
   }
   const uint32_t n_closed = (uint32_t)__popcll(__ballot(closed)), n_shared = (uint32_t)__popcll(__ballot(shared));
-  for (int d = 32; d > 0; d >>= 1) length = max(length, (uint32_t)__shfl_xor(length, d));
+  length = WaveMax(length);
   if ((threadIdx.x & 63) == 0) {
     if (n_closed) atomicAdd(&status->closed, n_closed);
     if (n_shared) atomicAdd(&status->shared, n_shared);
     if (length) atomicMax(&status->longest, length);
-  }
-}
-
-__global__ __launch_bounds__(256) void k_mesh_copy(const int32_t* __restrict__ segments, const int32_t* __restrict__ vertices,
-                                                   const int32_t* __restrict__ loops, const int32_t* __restrict__ refs,
-                                                   uint32_t n_segments, uint32_t n_loops, uint32_t n_refs,
-                                                   uint32_t vertex_slots, uint32_t capacity_vertices,
-                                                   int32_t* __restrict__ segments_out, int32_t* __restrict__ vertices_out,
-                                                   int32_t* __restrict__ loops_out, int32_t* __restrict__ refs_out,
-                                                   const MeshStatus* __restrict__ status) {
-  const uint32_t n_vertices = status->vertices;
-  if (n_vertices > capacity_vertices || n_vertices > vertex_slots || status->flags) return;
-  const size_t a = (size_t)n_segments * kMeshSegmentWords, b = a + (size_t)n_vertices * 2;
-  const size_t c = b + (size_t)n_loops * kMeshLoopWords, d = c + n_refs;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < d; k += step) {
-    if (k < a) segments_out[k] = segments[k];
-    else if (k < b) vertices_out[k - a] = vertices[k - a];
-    else if (k < c) loops_out[k - b] = loops[k - b];
-    else refs_out[k - c] = refs[k - c];
   }
 }
 
@@ -491,15 +463,6 @@ MeshView ViewOf(const MeshInput& in) {
 
 }  // namespace
 
-size_t MeshTempBytes(int64_t items, int end_bit) {
-  size_t sort = 0, scan = 0;
-  (void)hipcub::DeviceRadixSort::SortKeys(nullptr, sort, (const unsigned long long*)nullptr,
-                                          (unsigned long long*)nullptr, items, 0, end_bit, (hipStream_t) nullptr);
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)items,
-                                         (hipStream_t) nullptr);
-  return std::max(sort, scan);
-}
-
 hipError_t MeshSplit(void* temp, size_t temp_bytes, const MeshInput& in, const unsigned long long* ckeys_sorted,
                      int rounds, MeshCrackSpace* wp, MeshStatus* status, hipStream_t stream) {
   MeshCrackSpace& w = *wp;
@@ -513,7 +476,7 @@ hipError_t MeshSplit(void* temp, size_t temp_bytes, const MeshInput& in, const u
   w.heads = m.heads = LaunchContourSums(w.state_a, w.state_b, n, rounds, stream);
   hipLaunchKernelGGL(k_mesh_loop_counts, GridOf(in.contours), dim3(kMeshBlock), 0, stream, m, ckeys_sorted, w.nrefs,
                      status);
-  e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, w.nrefs, w.first_ref, (int)in.contours, stream);
+  e = ExclusiveSumU32(temp, temp_bytes, w.nrefs, w.first_ref, (int)in.contours, stream);
   if (e != hipSuccess) return e;
   m.nrefs = w.nrefs;
   m.first_ref = w.first_ref;
@@ -537,11 +500,11 @@ hipError_t MeshTables(void* temp, size_t temp_bytes, const MeshInput& in, const 
   const uint32_t* last_of = w.head_of + n;
   hipError_t e = hipMemsetAsync(w.seg_of, 0xff, (size_t)n_halves * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
-  e = hipcub::DeviceRadixSort::SortKeys(temp, temp_bytes, w.skeys, t.skeys_sorted, (int64_t)n_segments, 0, end_bit, stream);
+  e = SortKeysU64(temp, temp_bytes, w.skeys, t.skeys_sorted, (int64_t)n_segments, end_bit, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_mesh_seg_heads, GridOf(n_segments), dim3(kMeshBlock), 0, stream, m, t.skeys_sorted, n_segments,
                      n_halves, w.half, last_of, w.seg_of, t.scount, status);
-  e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, t.scount, t.sfirst, (int)n_segments, stream);
+  e = ExclusiveSumU32(temp, temp_bytes, t.scount, t.sfirst, (int)n_segments, stream);
   if (e != hipSuccess) return e;
   e = hipMemsetAsync(t.vseg, 0xff, (size_t)t.vertex_slots * sizeof(uint32_t), stream);
   if (e != hipSuccess) return e;
@@ -556,17 +519,6 @@ hipError_t MeshTables(void* temp, size_t temp_bytes, const MeshInput& in, const 
                      reinterpret_cast<const int2*>(t.vertices), t.vseg, n_segments, t.vertex_slots, t.segments, status);
   hipLaunchKernelGGL(k_mesh_finish, GridOf(n_segments), dim3(kMeshBlock), 0, stream, t.segments, n_segments, status);
   return hipGetLastError();
-}
-
-void LaunchMeshCopy(const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_loops, uint32_t n_refs,
-                    uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
-                    int32_t* refs_out, const MeshStatus* status, hipStream_t stream) {
-  const size_t words = (size_t)n_segments * kMeshSegmentWords + (size_t)t.vertex_slots * 2 +
-                       (size_t)n_loops * kMeshLoopWords + n_refs;
-  const size_t groups = std::max<size_t>((words + 255) / 256, 1);
-  hipLaunchKernelGGL(k_mesh_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, t.segments,
-                     t.vertices, t.loops, t.refs, n_segments, n_loops, n_refs, t.vertex_slots, capacity_vertices,
-                     segments_out, vertices_out, loops_out, refs_out, status);
 }
 
 }  // namespace vsg_render_impl

@@ -23,15 +23,15 @@
 //   k_overlap_col_heads    one thread per distinct key: the head of a label writes it and where it starts
 //   k_overlap_cols         one wavefront per column: area, uncovered, num_pairs, the arg-max over its keys,
 //                          and `col` of every pair of the column
-//   k_overlap_copy         the three lists to the caller's device memory, if all of them fit
+//   k_copy_lists           of lists.hip: the three lists to the caller's device memory, if all of them fit
 //
 // Key layout, gb = the bits of the largest group and lb = the bits of the largest label (1..31 each):
 //   bits [0, lb + 1)               code(B): the label, or 1 << lb for "none", which sorts behind every label
 //   bits [lb + 1, lb + gb + 2)     code(P): the group, or 1 << gb for "none", which sorts behind every group
 // The column sort's key holds the same two fields the other way round.
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
+#include "render_scan.h"
 
 namespace vsg_render_impl {
 
@@ -153,13 +153,11 @@ __global__ __launch_bounds__(kOvlBlock) void k_overlap_runs(const int32_t* __res
     if (first >= 0) open = last_is_head;   // a step without a break changes nothing
   }
   if (!kEmit) {
-    for (int s = 32; s > 0; s >>= 1) {
-      n_heads += __shfl_xor(n_heads, s);
-      n_covered += __shfl_xor(n_covered, s);
-      n_labelled += __shfl_xor(n_labelled, s);
-      n_both += __shfl_xor(n_both, s);
-      max_label = max(max_label, (uint32_t)__shfl_xor(max_label, s));
-    }
+    n_heads = WaveSum(n_heads);
+    n_covered = WaveSum(n_covered);
+    n_labelled = WaveSum(n_labelled);
+    n_both = WaveSum(n_both);
+    max_label = WaveMax(max_label);
     if (lane == 0) {
       s_sum[wave][0] = n_heads;
       s_sum[wave][1] = n_covered;
@@ -191,10 +189,8 @@ __global__ __launch_bounds__(kOvlBlock) void k_overlap_totals(const uint32_t* __
     for (int k = 0; k < 4; ++k) sum[k] += row_totals[(size_t)y * kOvlTotals + k];
     sum[4] = max(sum[4], row_totals[(size_t)y * kOvlTotals + 4]);
   }
-  for (int s = 32; s > 0; s >>= 1) {
-    for (int k = 0; k < 4; ++k) sum[k] += __shfl_xor(sum[k], s);
-    sum[4] = max(sum[4], (uint32_t)__shfl_xor(sum[4], s));
-  }
+  for (int k = 0; k < 4; ++k) sum[k] = WaveSum(sum[k]);
+  sum[4] = WaveMax(sum[4]);
   if (lane == 0) {
     for (int k = 0; k < kOvlTotals; ++k) s_sum[wave][k] = sum[k];
   }
@@ -211,64 +207,6 @@ __global__ __launch_bounds__(kOvlBlock) void k_overlap_totals(const uint32_t* __
     status->max_label = sum[4];
   }
 }
-
-// The fields of a key and of a column key.
-struct OvlBits {
-  int group_bits, label_bits;
-  __host__ __device__ unsigned long long P(unsigned long long key) const { return key >> (label_bits + 1); }
-  __host__ __device__ unsigned long long B(unsigned long long key) const {
-    return key & ((1ull << (label_bits + 1)) - 1);
-  }
-  __host__ __device__ bool NoP(unsigned long long key) const { return (key >> (label_bits + 1 + group_bits)) & 1; }
-  __host__ __device__ bool NoB(unsigned long long key) const { return (key >> label_bits) & 1; }
-  __host__ __device__ unsigned long long Swapped(unsigned long long key) const {
-    return B(key) << (group_bits + 1) | P(key);
-  }
-  __host__ __device__ unsigned long long ColB(unsigned long long ckey) const { return ckey >> (group_bits + 1); }
-  __host__ __device__ bool ColNoB(unsigned long long ckey) const {
-    return (ckey >> (group_bits + 1 + label_bits)) & 1;
-  }
-  __host__ __device__ bool ColNoP(unsigned long long ckey) const { return (ckey >> group_bits) & 1; }
-};
-
-// Sorted run i -> 1 << 32 if it is the first of a group, + 1 if it is the first of a (group, label).
-struct OvlRowHeads {
-  const unsigned long long* keys;
-  OvlBits bits;
-  __host__ __device__ unsigned long long operator()(uint32_t i) const {
-    const unsigned long long key = keys[i];
-    if (bits.NoP(key)) return 0ull;
-    const bool first = i == 0;
-    const unsigned long long prev = first ? 0ull : keys[i - 1];
-    const bool row = first || bits.P(prev) != bits.P(key);
-    const bool pair = !bits.NoB(key) && (first || prev != key);
-    return (row ? 1ull << 32 : 0ull) | (pair ? 1ull : 0ull);
-  }
-};
-// Sorted run i -> 1 << 32 if it is the first of its key, + its length.  The lengths of a frame sum to
-// less than 2^32: the low half never carries into the high one.
-struct OvlKeyHeads {
-  const unsigned long long* keys;
-  const uint32_t* lengths;
-  __host__ __device__ unsigned long long operator()(uint32_t i) const {
-    const bool head = i == 0 || keys[i - 1] != keys[i];
-    return (head ? 1ull << 32 : 0ull) | lengths[i];
-  }
-};
-// Sorted column key j -> 1 if it is the first of a label.
-struct OvlColHeads {
-  const unsigned long long* ckeys;
-  OvlBits bits;
-  __host__ __device__ uint32_t operator()(uint32_t j) const {
-    const unsigned long long ckey = ckeys[j];
-    if (bits.ColNoB(ckey)) return 0u;
-    return (j == 0 || bits.ColB(ckeys[j - 1]) != bits.ColB(ckey)) ? 1u : 0u;
-  }
-};
-typedef hipcub::CountingInputIterator<uint32_t> OvlCounter;
-typedef hipcub::TransformInputIterator<unsigned long long, OvlRowHeads, OvlCounter> OvlRowHeadIterator;
-typedef hipcub::TransformInputIterator<unsigned long long, OvlKeyHeads, OvlCounter> OvlKeyHeadIterator;
-typedef hipcub::TransformInputIterator<uint32_t, OvlColHeads, OvlCounter> OvlColHeadIterator;
 
 // One thread per sorted run i < n.  row_heads[i] = rows << 32 | pairs, key_heads[i] = distinct keys << 32 |
 // pixels, each in [0, i].  The head of distinct key d writes key[d], start[d] = the pixels before it and
@@ -386,7 +324,7 @@ __global__ __launch_bounds__(256) void k_overlap_rows(int32_t* __restrict__ rows
     sum += count;
     best = OvlBest(best, (unsigned long long)count << 32 | (uint32_t)~e);
   }
-  for (int s = 32; s > 0; s >>= 1) sum += __shfl_xor(sum, s);
+  sum = WaveSum(sum);
   best = OvlWaveBest(best);
   if (lane == 0) {
     row[3] = (int32_t)(end - first);
@@ -468,7 +406,7 @@ __global__ __launch_bounds__(256) void k_overlap_cols(const unsigned long long* 
     pairs[(size_t)e * kOverlapPairWords + 1] = (int32_t)c;
   }
   if (bad) atomicOr(&status->flags, (uint32_t)OVL_FLAG_RANGE);
-  for (int s = 32; s > 0; s >>= 1) {
+  for (int s = 32; s > 0; s >>= 1) {   // one loop: as three WaveSum calls the kernel's register count changes
     area += __shfl_xor(area, s);
     uncovered += __shfl_xor(uncovered, s);
     n_pairs += __shfl_xor(n_pairs, s);
@@ -481,27 +419,6 @@ __global__ __launch_bounds__(256) void k_overlap_cols(const unsigned long long* 
     col[3] = (int32_t)n_pairs;
     col[4] = n_pairs ? (int32_t)~(uint32_t)best : -1;
     col[5] = (int32_t)(uint32_t)(best >> 32);
-  }
-}
-
-// All three lists to the caller's device memory, or none: their lengths are known on the device only.
-// Dword copies, grid-stride.
-__global__ __launch_bounds__(256) void k_overlap_copy(const int32_t* __restrict__ rows,
-                                                      const int32_t* __restrict__ cols,
-                                                      const int32_t* __restrict__ pairs, uint32_t capacity_rows,
-                                                      uint32_t capacity_cols, uint32_t capacity_pairs,
-                                                      int32_t* __restrict__ rows_out, int32_t* __restrict__ cols_out,
-                                                      int32_t* __restrict__ pairs_out,
-                                                      const OvlStatus* __restrict__ status) {
-  const uint32_t n_rows = status->rows, n_cols = status->cols, n_pairs = status->pairs;
-  if (n_rows > capacity_rows || n_cols > capacity_cols || n_pairs > capacity_pairs || status->flags) return;
-  const size_t row_words = (size_t)n_rows * kOverlapRowWords, col_words = (size_t)n_cols * kOverlapColWords;
-  const size_t pair_words = (size_t)n_pairs * kOverlapPairWords;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < row_words + col_words + pair_words; k += step) {
-    if (k < row_words) rows_out[k] = rows[k];
-    else if (k < row_words + col_words) cols_out[k - row_words] = cols[k - row_words];
-    else pairs_out[k - row_words - col_words] = pairs[k - row_words - col_words];
   }
 }
 
@@ -519,29 +436,6 @@ void LaunchOverlapRuns(const int32_t* plane, const int32_t* other, size_t other_
                        nullptr, nullptr, row_totals, status);
     hipLaunchKernelGGL(k_overlap_totals, dim3(1), block, 0, stream, row_totals, height, status);
   }
-}
-
-size_t OverlapScanTempBytes(int64_t n) {
-  size_t a = 0, b = 0, c = 0;
-  const OvlBits bits{1, 1};
-  OvlRowHeadIterator rows(OvlCounter(0), OvlRowHeads{nullptr, bits});
-  OvlKeyHeadIterator keys(OvlCounter(0), OvlKeyHeads{nullptr, nullptr});
-  OvlColHeadIterator cols(OvlCounter(0), OvlColHeads{nullptr, bits});
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, a, rows, (unsigned long long*)nullptr, n, (hipStream_t) nullptr);
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, b, keys, (unsigned long long*)nullptr, n, (hipStream_t) nullptr);
-  (void)hipcub::DeviceScan::InclusiveSum(nullptr, c, cols, (uint32_t*)nullptr, n, (hipStream_t) nullptr);
-  return a > b ? (a > c ? a : c) : (b > c ? b : c);
-}
-
-hipError_t OverlapRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted,
-                       const uint32_t* lengths_sorted, int group_bits, int label_bits, unsigned long long* row_heads,
-                       unsigned long long* key_heads, int64_t n, hipStream_t stream) {
-  const OvlBits bits{group_bits, label_bits};
-  OvlRowHeadIterator rows(OvlCounter(0), OvlRowHeads{keys_sorted, bits});
-  const hipError_t e = hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, rows, row_heads, n, stream);
-  if (e != hipSuccess) return e;
-  OvlKeyHeadIterator keys(OvlCounter(0), OvlKeyHeads{keys_sorted, lengths_sorted});
-  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, keys, key_heads, n, stream);
 }
 
 void LaunchOverlapTable(const unsigned long long* keys_sorted, const uint32_t* lengths_sorted,
@@ -563,12 +457,6 @@ void LaunchOverlapTable(const unsigned long long* keys_sorted, const uint32_t* l
   }
 }
 
-hipError_t OverlapColRank(void* temp, size_t temp_bytes, const unsigned long long* ckeys_sorted, int group_bits,
-                          int label_bits, uint32_t* rank, int64_t m, hipStream_t stream) {
-  OvlColHeadIterator cols(OvlCounter(0), OvlColHeads{ckeys_sorted, OvlBits{group_bits, label_bits}});
-  return hipcub::DeviceScan::InclusiveSum(temp, temp_bytes, cols, rank, m, stream);
-}
-
 void LaunchOverlapCols(const unsigned long long* ckeys_sorted, const uint32_t* cvals_sorted, const uint32_t* col_rank,
                        const uint32_t* start, const unsigned long long* rank, uint32_t m, int group_bits,
                        int label_bits, uint32_t* first, int32_t* cols, int32_t* pairs, OvlStatus* status,
@@ -579,17 +467,6 @@ void LaunchOverlapCols(const unsigned long long* ckeys_sorted, const uint32_t* c
                      bits, m, cols, first, status);
   hipLaunchKernelGGL(k_overlap_cols, dim3((m + 3) / 4), dim3(256), 0, stream, ckeys_sorted, cvals_sorted, first,
                      start, rank, m, bits, m, m, cols, pairs, status);
-}
-
-void LaunchOverlapCopy(const int32_t* rows, const int32_t* cols, const int32_t* pairs, uint32_t capacity_rows,
-                       uint32_t capacity_cols, uint32_t capacity_pairs, int32_t* rows_out, int32_t* cols_out,
-                       int32_t* pairs_out, const OvlStatus* status, hipStream_t stream) {
-  const size_t words = (size_t)capacity_rows * kOverlapRowWords + (size_t)capacity_cols * kOverlapColWords +
-                       (size_t)capacity_pairs * kOverlapPairWords;
-  if (words == 0) return;
-  const size_t groups = (words + 255) / 256;
-  hipLaunchKernelGGL(k_overlap_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, rows, cols,
-                     pairs, capacity_rows, capacity_cols, capacity_pairs, rows_out, cols_out, pairs_out, status);
 }
 
 }  // namespace vsg_render_impl

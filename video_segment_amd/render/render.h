@@ -1,6 +1,8 @@
-// render.h -- launchers of the render kernels (render.hip, vector.hip, level.hip, components.hip,
-// boundaries.hip, adjacency.hip, overlap.hip, persistence.hip, colors.hip, pool.hip, contours.hip, distance.hip, volume.hip),
-// called by the parts of render_capi.cpp (render_handle.h and the capi_*.inc files).
+// render.h -- launchers of the render kernels, one section per .hip file (render, vector, lists, level,
+// components, boundaries, adjacency, overlap, persistence, colors, pool, contours, mesh, simplify, distance,
+// volume), called by the parts of render_capi.cpp (render_handle.h and the capi_*.inc files).  The library sorts,
+// the plain scan and the copy of a call's lists to device memory are lists.hip's, shared by every family; the
+// scans over segment heads are render_scan.h's; the device helpers the kernels share are render_device.h's.
 #ifndef VSG_RENDER_RENDER_H_
 #define VSG_RENDER_RENDER_H_
 
@@ -64,16 +66,52 @@ struct VecStatus {
 
 void LaunchVecWalk(const VecLine* lines, int n_lines, unsigned long long* keys, unsigned long long* vals,
                    VecStatus* status, hipStream_t stream);
-// The library radix sort on bits [0, end_bit) of the keys.
-size_t VecSortTempBytes(int64_t n, int end_bit);
-hipError_t VecSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                   const unsigned long long* vals_in, unsigned long long* vals_out, int64_t n, int end_bit,
-                   hipStream_t stream);
 // n sorted crossings (n even) -> n / 2 intervals, dense, in region / row / left-to-right order.
 // `intervals` has to be cleared to zero before.  value = region_value[region index].
 void LaunchVecPairs(const unsigned long long* keys, const unsigned long long* vals, const VecLine* lines,
                     uint32_t n_lines, const uint32_t* region_value, uint32_t n_regions, int64_t n, int width,
                     int height, Interval* intervals, VecStatus* status, hipStream_t stream);
+
+// ---- lists (lists.hip): the library sorts and scan, the copy of a call's lists to device memory ------
+
+// The library radix sort on bits [0, end_bit) of n keys (with their values), and its work space.  U64U32:
+// 64-bit keys, 32-bit values.
+size_t SortKeysU64TempBytes(int64_t n, int end_bit);
+hipError_t SortKeysU64(void* temp, size_t temp_bytes, const unsigned long long* in, unsigned long long* out, int64_t n,
+                       int end_bit, hipStream_t stream);
+size_t SortPairsU64U32TempBytes(int64_t n, int end_bit);
+hipError_t SortPairsU64U32(void* temp, size_t temp_bytes, const unsigned long long* keys_in,
+                           unsigned long long* keys_out, const uint32_t* vals_in, uint32_t* vals_out, int64_t n,
+                           int end_bit, hipStream_t stream);
+size_t SortPairsU64U64TempBytes(int64_t n, int end_bit);
+hipError_t SortPairsU64U64(void* temp, size_t temp_bytes, const unsigned long long* keys_in,
+                           unsigned long long* keys_out, const unsigned long long* vals_in,
+                           unsigned long long* vals_out, int64_t n, int end_bit, hipStream_t stream);
+size_t SortPairsU32U32TempBytes(int64_t n, int end_bit);
+hipError_t SortPairsU32U32(void* temp, size_t temp_bytes, const uint32_t* keys_in, uint32_t* keys_out,
+                           const uint32_t* vals_in, uint32_t* vals_out, int64_t n, int end_bit, hipStream_t stream);
+// out[i] = in[0] + ... + in[i - 1], i < n.
+size_t ExclusiveSumU32TempBytes(int n);
+hipError_t ExclusiveSumU32(void* temp, size_t temp_bytes, const uint32_t* in, uint32_t* out, int n,
+                           hipStream_t stream);
+
+// One list of a call: `words` int32 per entry, *count entries (device memory), or `fixed` of them when count is
+// null.  limit: the most entries the list may have: the smaller of the caller's capacity and the slots of `from`.
+struct CopyList {
+  const int32_t* from;
+  int32_t* to;
+  uint32_t words;
+  const uint32_t* count;
+  uint32_t fixed, limit;
+};
+// The lists of a call, unused ones zero.  flags: null, or a word of device memory that has to be 0.
+struct CopyLists {
+  CopyList list[4];
+  const uint32_t* flags;
+};
+// Copies every list to its `to` (device memory), or nothing at all when a list is longer than its limit or a
+// flag is up.  No launch when every limit is 0.
+void LaunchCopyLists(const CopyLists& lists, hipStream_t stream);
 
 // ---- level regions (level.hip): runs, regions and moments from the filled id plane ------------------
 
@@ -91,14 +129,6 @@ struct LevelStatus {
 // in no particular order, status->runs of them.  Slots at or beyond `capacity` are not written.
 void LaunchLevelRuns(const int32_t* plane, int pitch, int width, int height, uint32_t capacity,
                      unsigned long long* keys, uint32_t* rights, LevelStatus* status, hipStream_t stream);
-// Work space of LevelSort and LevelRank (the larger of the two).
-size_t LevelTempBytes(int64_t n, int end_bit);
-// The library radix sort on bits [0, end_bit) of the keys.
-hipError_t LevelSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                     const uint32_t* rights_in, uint32_t* rights_out, int64_t n, int end_bit, hipStream_t stream);
-// rank[i] = number of distinct ids among sorted runs [0, i].
-hipError_t LevelRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, uint32_t* rank, int64_t n,
-                     hipStream_t stream);
 // n sorted runs -> n intervals, and id and first_interval of every region; status->regions.
 // `regions` has room for capacity_regions entries of kLevelRegionWords words.
 void LaunchLevelTable(const unsigned long long* keys_sorted, const uint32_t* rights_sorted, const uint32_t* rank,
@@ -107,10 +137,6 @@ void LaunchLevelTable(const unsigned long long* keys_sorted, const uint32_t* rig
 // The remaining fields of every region; status->largest.
 void LaunchLevelMoments(const Interval* intervals, uint32_t n, uint32_t capacity_regions, int32_t* regions,
                         LevelStatus* status, hipStream_t stream);
-// Copies status->regions regions and n intervals, or nothing when there are more regions than
-// capacity_regions.
-void LaunchLevelCopy(const int32_t* regions, const Interval* intervals, uint32_t n, uint32_t capacity_regions,
-                     int32_t* regions_out, int32_t* intervals_out, const LevelStatus* status, hipStream_t stream);
 
 // ---- level components (components.hip): the connected components of every region of a level ---------
 
@@ -129,24 +155,16 @@ struct CompStatus {
   uint32_t flags, pad;
 };
 
-// Union-find over the n sorted runs of LevelSort (keys, right ends): runs of one id in adjacent rows
+// Union-find over the n sorted runs of the level (keys, right ends): runs of one id in adjacent rows
 // are united when left_a <= right_b + slack and left_b <= right_a + slack (slack 0: N4, 1: N8).
 // Leaves label[i] = the smallest run index of i's component and index[i] = i.  parent, label and index
 // have n entries each.
 void LaunchCompLink(const unsigned long long* keys_sorted, const uint32_t* rights_sorted, uint32_t n, int width,
                     int slack, uint32_t* parent, uint32_t* label, uint32_t* index, CompStatus* status,
                     hipStream_t stream);
-// Work space of CompSort and CompRank (the larger of the two).
-size_t CompTempBytes(int64_t n, int end_bit);
-// The library radix sort (stable) of the (label, index) pairs on bits [0, end_bit) of the label.
-hipError_t CompSort(void* temp, size_t temp_bytes, const uint32_t* label, uint32_t* label_sorted,
-                    const uint32_t* index, uint32_t* order, int64_t n, int end_bit, hipStream_t stream);
-// comp_rank[k] = number of distinct labels among ordered runs [0, k].
-hipError_t CompRank(void* temp, size_t temp_bytes, const uint32_t* label_sorted, uint32_t* comp_rank, int64_t n,
-                    hipStream_t stream);
 // n ordered runs -> the ordered interval list, the same list with the component's index as its value
 // (`fill`, may be null), and id, component, region_components and first_interval of every component;
-// status->components.  region_rank and intervals are LevelRank's and LaunchLevelTable's, level_status
+// status->components.  region_rank and intervals are the scan of HeadFlag and LaunchLevelTable's, level_status
 // holds the number of regions.  `components` has room for capacity_components entries of
 // kLevelComponentWords words, region_first for capacity_regions words.
 void LaunchCompTable(const uint32_t* label_sorted, const uint32_t* order, const uint32_t* comp_rank,
@@ -184,21 +202,12 @@ struct BoundStatus {
 // raises BOUND_FLAG_OVERFLOW.
 void LaunchBoundClassify(const int32_t* plane, int width, int height, bool outer, bool emit, uint32_t capacity,
                          unsigned long long* keys, BoundStatus* status, hipStream_t stream);
-// Work space of BoundSort and of LevelRank on the sorted keys (the larger of the two).
-size_t BoundTempBytes(int64_t n, int end_bit);
-// The library radix sort on bits [0, end_bit) of the keys.
-hipError_t BoundSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                     int64_t n, int end_bit, hipStream_t stream);
-// n sorted keys with LevelRank's ranks -> n points {x, y} and the records {id, component, first_point,
+// n sorted keys with their ranks (the scan of HeadFlag) -> n points {x, y} and the records {id, component, first_point,
 // num_points}; status->boundaries and status->largest.  comp_table: null (id = group, component = -1),
 // or the table of LaunchCompTable the groups index.  `records` has room for capacity_records entries.
 void LaunchBoundTable(const unsigned long long* keys_sorted, const uint32_t* rank, uint32_t n, int width, int height,
                       uint32_t max_group, uint32_t capacity_records, const int32_t* comp_table, int32_t* points,
                       int32_t* records, BoundStatus* status, hipStream_t stream);
-// Copies status->boundaries records and n points, or nothing when there are more records than
-// capacity_records or a flag is up.
-void LaunchBoundCopy(const int32_t* records, const int32_t* points, uint32_t n, uint32_t capacity_records,
-                     int32_t* records_out, int32_t* points_out, const BoundStatus* status, hipStream_t stream);
 
 // ---- level adjacency (adjacency.hip): the region adjacency graph of an int32 plane -------------------
 
@@ -229,26 +238,13 @@ struct AdjStatus {
 // at or beyond `capacity` is not written and raises ADJ_FLAG_OVERFLOW.
 void LaunchAdjClassify(const int32_t* plane, int width, int height, int group_bits, bool diagonal, bool emit,
                        uint32_t capacity, unsigned long long* keys, AdjStatus* status, hipStream_t stream);
-// Work space of AdjSort and AdjRank (the larger of the two).
-size_t AdjTempBytes(int64_t n, int end_bit);
-// The library radix sort on bits [0, end_bit) of the keys; all of a key is below 2 * group_bits + 2.
-hipError_t AdjSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                   int64_t n, int end_bit, hipStream_t stream);
-// heads[i] = (distinct groups) << 32 | (distinct (group, other) with other a group) among sorted keys
-// [0, i]: LevelRank's scan with two counters in one sum.
-hipError_t AdjRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted, int group_bits,
-                   unsigned long long* heads, int64_t n, hipStream_t stream);
-// n sorted keys with AdjRank's heads -> the nodes and the edges; status->nodes, ->edges and ->largest.
+// n sorted keys with the scan of AdjHeads -> the nodes and the edges; status->nodes, ->edges and ->largest.
 // `nodes` (capacity_nodes entries) and `edges` (capacity_edges entries) have to be cleared to zero
 // before.  comp_table: null (id = group, component = -1, neighbour = the rank of the neighbour's id), or
 // the table of LaunchCompTable the groups index (neighbour = the group across).
 void LaunchAdjTable(const unsigned long long* keys_sorted, const unsigned long long* heads, uint32_t n, int group_bits,
                     uint32_t max_group, uint32_t capacity_nodes, uint32_t capacity_edges, const int32_t* comp_table,
                     int32_t* nodes, int32_t* edges, AdjStatus* status, hipStream_t stream);
-// Copies status->nodes nodes and status->edges edges, or nothing when either list is longer than its
-// capacity or a flag is up.
-void LaunchAdjCopy(const int32_t* nodes, const int32_t* edges, uint32_t capacity_nodes, uint32_t capacity_edges,
-                   int32_t* nodes_out, int32_t* edges_out, const AdjStatus* status, hipStream_t stream);
 
 // ---- level overlap (overlap.hip): the contingency table of an int32 plane and a plane of labels ------
 
@@ -288,14 +284,7 @@ struct OvlStatus {
 void LaunchOverlapRuns(const int32_t* plane, const int32_t* other, size_t other_pitch, int width, int height,
                        int group_bits, int label_bits, bool emit, uint32_t capacity, unsigned long long* keys,
                        uint32_t* lengths, uint32_t* row_totals, OvlStatus* status, hipStream_t stream);
-// Work space of OverlapRank and OverlapColRank (the larger); the sorts are LevelSort, see LevelTempBytes.
-size_t OverlapScanTempBytes(int64_t n);
-// Two scans over the n sorted runs: row_heads[i] = (distinct groups) << 32 | (distinct (group, label), both
-// real) and key_heads[i] = (distinct keys) << 32 | (sum of the lengths), each over [0, i].
-hipError_t OverlapRank(void* temp, size_t temp_bytes, const unsigned long long* keys_sorted,
-                       const uint32_t* lengths_sorted, int group_bits, int label_bits, unsigned long long* row_heads,
-                       unsigned long long* key_heads, int64_t n, hipStream_t stream);
-// n sorted runs with OverlapRank's scans -> the list of distinct keys (key, start and rank: m, m + 1 and m
+// n sorted runs with the scans of OvlRowHeads and OvlKeyHeads -> the list of distinct keys (key, start and rank: m, m + 1 and m
 // entries; m bounds their number), the rows (capacity_rows entries, cleared to zero before) and the pairs
 // (m entries) but for `col`, and the m (column key, index of the distinct key) operands of the column sort;
 // status->distinct, ->rows, ->pairs and ->largest.  comp_table: null (id = group, component = -1), or the
@@ -306,20 +295,12 @@ void LaunchOverlapTable(const unsigned long long* keys_sorted, const uint32_t* l
                         const int32_t* comp_table, unsigned long long* key, uint32_t* start, unsigned long long* rank,
                         int32_t* rows, int32_t* pairs, unsigned long long* ckeys, uint32_t* cvals, OvlStatus* status,
                         hipStream_t stream);
-// rank[j] = number of distinct labels among sorted column keys [0, j].
-hipError_t OverlapColRank(void* temp, size_t temp_bytes, const unsigned long long* ckeys_sorted, int group_bits,
-                          int label_bits, uint32_t* rank, int64_t m, hipStream_t stream);
 // m sorted column operands with their ranks -> the columns (m entries) and `col` of every pair;
 // status->cols.  `first` has m + 1 entries; start and rank are those of LaunchOverlapTable.
 void LaunchOverlapCols(const unsigned long long* ckeys_sorted, const uint32_t* cvals_sorted, const uint32_t* col_rank,
                        const uint32_t* start, const unsigned long long* rank, uint32_t m, int group_bits,
                        int label_bits, uint32_t* first, int32_t* cols, int32_t* pairs, OvlStatus* status,
                        hipStream_t stream);
-// Copies status->rows rows, status->cols columns and status->pairs pairs, or nothing when a list is longer
-// than its capacity or a flag is up.
-void LaunchOverlapCopy(const int32_t* rows, const int32_t* cols, const int32_t* pairs, uint32_t capacity_rows,
-                       uint32_t capacity_cols, uint32_t capacity_pairs, int32_t* rows_out, int32_t* cols_out,
-                       int32_t* pairs_out, const OvlStatus* status, hipStream_t stream);
 
 // ---- boundary persistence (persistence.hip): all hierarchy levels' edges from the level-0 plane --------
 
@@ -379,8 +360,8 @@ struct ColorStatus {
 // read.  Dword loads when bgr and stride are multiples of 4.
 void LaunchColorRuns(const Interval* intervals, uint32_t n, int width, int height, const uint8_t* bgr, size_t stride,
                      uint32_t* partials, hipStream_t stream);
-// The partials summed per record, then the records.  rank[i] - 1 is the record of interval i (LevelRank's
-// or CompRank's scan; records are contiguous in the list).  acc: capacity_acc entries of kColorAccBytes,
+// The partials summed per record, then the records.  rank[i] - 1 is the record of interval i (the scan of
+// HeadFlag or LabelHead; records are contiguous in the list).  acc: capacity_acc entries of kColorAccBytes,
 // cleared to zero before.  table: table_words words per record, word 0 its id, word 1 (has_component) its
 // component.  *count records exist (device memory); they are written to `records` unless there are more
 // than `capacity`.  status->covered and ->largest are added to.
@@ -481,9 +462,8 @@ struct ContourStatus {
   uint32_t flags, pad;
 };
 
-// Work space of the scans, the sort and LevelRank of a call (the largest of them): `pixels` mask bytes,
-// `contours` contour slots.
-size_t ContourTempBytes(uint32_t pixels, int64_t contours, int end_bit);
+// Work space of ContourClassify's scan over `pixels` mask bytes.
+size_t ContourClassifyTempBytes(uint32_t pixels);
 // The count pass over the H x W plane (row pitch W; negative and everything outside the frame: no group):
 // mask[p] = bit s set when side s (0 top, 1 right, 2 bottom, 3 left) of pixel p is a crack, offset[p] = the
 // cracks of the pixels before p, status->cracks += their number.
@@ -510,9 +490,6 @@ const uint2* LaunchContourSums(uint2* in, uint2* out, uint32_t n, int rounds, hi
 // entries, set to ~0 before so that unused slots sort last.
 void LaunchContourLeaders(const uint32_t* leader, const uint32_t* key, const int32_t* plane, uint32_t n,
                           uint32_t capacity, unsigned long long* ckeys, ContourStatus* status, hipStream_t stream);
-// The library radix sort on bits [0, end_bit) of all `capacity` slots.
-hipError_t ContourSort(void* temp, size_t temp_bytes, const unsigned long long* ckeys, unsigned long long* ckeys_sorted,
-                       int64_t capacity, int end_bit, hipStream_t stream);
 // count[j] and first[j] of sorted contour j (capacity entries each, 0 beyond the contours), place[leader] = j
 // (n entries), then every turn crack's start corner at vertices[first + rank] and owner[that slot] = j
 // (n slots each).  Three launches.
@@ -520,18 +497,13 @@ hipError_t ContourVertices(void* temp, size_t temp_bytes, const unsigned long lo
                            const uint32_t* succ, const uint32_t* leader, const uint2* ranked, uint32_t n,
                            uint32_t capacity, int width, uint32_t* place, uint32_t* count, uint32_t* first,
                            int32_t* vertices, uint32_t* owner, ContourStatus* status, hipStream_t stream);
-// The records (capacity entries); status->vertices, ->holes and ->largest.  rank: LevelRank of the sorted
+// The records (capacity entries); status->vertices, ->holes and ->largest.  rank: the scan of HeadFlag over the sorted
 // keys.  comp_table: null (id = group, component = -1, group = rank - 1), or the table of LaunchCompTable
 // the groups index.  Three launches.
 void LaunchContourTable(const unsigned long long* ckeys_sorted, const uint32_t* rank, const uint32_t* count,
                         const uint32_t* first, const int32_t* vertices, const uint32_t* owner, uint32_t n,
                         uint32_t capacity, uint32_t max_group, const int32_t* comp_table, int32_t* records,
                         ContourStatus* status, hipStream_t stream);
-// Copies status->contours records and status->vertices vertices, or nothing when either list is longer than
-// its capacity or a flag is up.
-void LaunchContourCopy(const int32_t* records, const int32_t* vertices, uint32_t capacity, uint32_t n,
-                       uint32_t capacity_records, uint32_t capacity_vertices, int32_t* records_out,
-                       int32_t* vertices_out, const ContourStatus* status, hipStream_t stream);
 
 // ---- level mesh (mesh.hip): the contours cut at the junctions into shared segments -----------------------
 
@@ -599,8 +571,6 @@ struct MeshSegmentSpace {
   int32_t* refs;
 };
 
-// Work space of the sort of `items` keys and of a scan over as many.
-size_t MeshTempBytes(int64_t items, int end_bit);
 // Junction bits, the third doubling (rounds / 2 launches), the halves of every crack, head and last crack of
 // every half, the unsorted owner keys; status->junctions, ->segments, ->refs.  ckeys_sorted: the contours'.
 // 7 + rounds / 2 launches, the scan counted as one.
@@ -612,11 +582,6 @@ hipError_t MeshSplit(void* temp, size_t temp_bytes, const MeshInput& in, const u
 hipError_t MeshTables(void* temp, size_t temp_bytes, const MeshInput& in, const MeshCrackSpace& w,
                       const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_halves, int end_bit,
                       MeshStatus* status, hipStream_t stream);
-// Copies the four lists, or nothing when the vertices do not fit or a flag is up (the other three lengths
-// are the host's to check).
-void LaunchMeshCopy(const MeshSegmentSpace& t, uint32_t n_segments, uint32_t n_loops, uint32_t n_refs,
-                    uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
-                    int32_t* refs_out, const MeshStatus* status, hipStream_t stream);
 
 // ---- mesh simplification (simplify.hip): Douglas-Peucker on the segments of the level mesh ----------------
 
@@ -658,8 +623,6 @@ struct SimplifyView {
   uint32_t* long_list;
 };
 
-// Work space of the scan over `segments` counts.
-size_t SimplifyTempBytes(int64_t segments);
 // The collapse rule, the sweeps and the rounds of every segment; kept, kseg, kcount, rounds, sflag.  3 launches:
 // the clear of kseg, the wavefronts, the workgroups of the long segments.  status: cleared by the caller.
 hipError_t SimplifyDp(const SimplifyView& m, SimplifyStatus* status, hipStream_t stream);
@@ -669,11 +632,6 @@ hipError_t SimplifyClean(const SimplifyView& m, uint32_t* ncount, hipStream_t st
 // the counts of status.  3 launches, the scan counted as one.
 hipError_t SimplifyTables(void* temp, size_t temp_bytes, const SimplifyView& m, const uint32_t* ncount, uint32_t* nfirst,
                           int32_t* segments_out, int32_t* vertices_out, SimplifyStatus* status, hipStream_t stream);
-// Copies the four lists, or nothing when the vertices do not fit or a flag is up.
-void LaunchSimplifyCopy(const int32_t* segments, const int32_t* vertices, const int32_t* loops, const int32_t* refs,
-                        uint32_t n_segments, uint32_t n_loops, uint32_t n_refs, uint32_t slots,
-                        uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
-                        int32_t* refs_out, const SimplifyStatus* status, hipStream_t stream);
 
 // ---- boundary distance (distance.hip): the squared distance to an edge set, the boundary benchmark ------
 

@@ -6,6 +6,8 @@
 // entry points share that thread-local only inside one translation unit: the parts below are included here, in
 // dependency order, and are not compiled on their own.
 //
+//   render_scan.h          the scans over segment heads the entry points call, with their head functors: the one
+//                          place where this unit instantiates device code (the library's scan kernels)
 //   render_desc.h          the proto reader, the hierarchy lookup, the polygon lines of a vector-only desc;
 //                          host only, no HIP call
 //   render_handle.h        struct vsg_render, the families' state, the stage enums, the helpers the families share
@@ -34,6 +36,7 @@
 
 #include "../../include/vsg_render.h"
 #include "render.h"
+#include "render_scan.h"
 #include "persistence_table.h"
 #include "../common/capi_support.h"
 

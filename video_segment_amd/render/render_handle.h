@@ -220,6 +220,15 @@ int BitsFor(uint64_t value, int limit) {
   return bits;
 }
 
+// The work space that serves every library sort and scan of a call: the largest of their sizes, 16 at the least.
+size_t MaxBytes(std::initializer_list<size_t> sizes) { return std::max<size_t>(std::max(sizes), 16); }
+
+// The sort of a level's runs (64-bit key, 32-bit value) and the scan of their regions' ranks.
+size_t LevelTempBytes(int64_t n, int end_bit) {
+  using namespace vsg_render_impl;
+  return MaxBytes({SortPairsU64U32TempBytes(n, end_bit), HeadScanTempBytes<HeadFlag>(n)});
+}
+
 }  // namespace
 
 struct vsg_render {
@@ -303,7 +312,7 @@ struct vsg_render {
     const size_t lines_bytes = lines.size() * sizeof(VecLine);
     const size_t values_bytes = region_value.size() * sizeof(uint32_t);
     const int end_bit = kVecRowBits + BitsFor(region_value.size(), 31);
-    const size_t temp_bytes = std::max<size_t>(VecSortTempBytes(n_cross, end_bit), 16);
+    const size_t temp_bytes = MaxBytes({SortPairsU64U64TempBytes(n_cross, end_bit)});
     h_intervals.Reserve(lines_bytes + values_bytes, &allocations);
     vec.in.Reserve(lines_bytes + values_bytes, &allocations);
     vec.cross.Reserve(4 * n * sizeof(unsigned long long), &allocations);
@@ -327,7 +336,7 @@ struct vsg_render {
     vec.clock.Begin(stream);
     LaunchVecWalk(d_lines, (int)lines.size(), keys, vals, status, stream);
     vec.clock.Mark(VEC_WALK);
-    VSG_HIP(VecSort(d_sort_temp.p, temp_bytes, keys, keys_sorted, vals, vals_sorted, n_cross, end_bit, stream));
+    VSG_HIP(SortPairsU64U64(d_sort_temp.p, temp_bytes, keys, keys_sorted, vals, vals_sorted, n_cross, end_bit, stream));
     vec.clock.Mark(VEC_SORT);
     LaunchVecPairs(keys_sorted, vals_sorted, d_lines, (uint32_t)lines.size(), d_values,
                    (uint32_t)region_value.size(), n_cross, W, H, static_cast<Interval*>(d_intervals.p), status, stream);

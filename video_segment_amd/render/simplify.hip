@@ -19,7 +19,7 @@
 //   scan                 first_vertex of the new lists
 //   k_simplify_compact   one thread per kept slot: the vertex to its place
 //   k_simplify_records   one thread per segment: the record, the counts of the stats
-//   k_simplify_copy      the four lists to the caller's device memory, if the vertices fit
+//   k_copy_lists         of lists.hip: the four lists to the caller's device memory, if the vertices fit
 //
 // The number of rounds is bounded by the number of vertices, whatever the data.  A handle is at most 32768
 // wide and high, so every cross product and every squared distance here is an integer below 2^32, exact in a
@@ -27,10 +27,9 @@
 // operation for operation, with contraction off.  Every index read from memory is checked against its array
 // before it is used.
 #include "render.h"
+#include "render_device.h"
 
 #include <algorithm>
-
-#include <hipcub/hipcub.hpp>
 
 #pragma clang fp contract(off)
 
@@ -118,7 +117,7 @@ __device__ void DpSegment(const SimplifyView& m, uint32_t s, const SegmentOf& g,
         const double dist = dx * dx + dy * dy;
         if (dist > 0) mine = max(mine, (u64)dist << 32 | (u64)(kNone - j));
       }
-      for (int d = 32; d > 0; d >>= 1) mine = max(mine, (u64)__shfl_xor((long long)mine, d));
+      mine = WaveMax(mine);
       if (lane == 0 && mine) atomicMax(&sh->sweep, mine);
       __syncthreads();
       const u64 key = sh->sweep;
@@ -430,11 +429,9 @@ __global__ __launch_bounds__(kTableBlock) void k_simplify_records(SimplifyView m
     if (s == m.n_segments - 1u) status->vertices_out = f + c;
   }
   const uint32_t n_collapsed = (uint32_t)__popcll(__ballot(collapsed)), n_single = (uint32_t)__popcll(__ballot(single));
-  for (int d = 32; d > 0; d >>= 1) {
-    kept += (uint32_t)__shfl_xor(kept, d);
-    rounds = max(rounds, (uint32_t)__shfl_xor(rounds, d));
-    longest = max(longest, (uint32_t)__shfl_xor(longest, d));
-  }
+  kept = WaveSum(kept);
+  rounds = WaveMax(rounds);
+  longest = WaveMax(longest);
   if ((threadIdx.x & 63) == 0) {
     if (n_collapsed) atomicAdd(&status->collapsed, n_collapsed);
     if (n_single) atomicAdd(&status->single_closed, n_single);
@@ -444,36 +441,9 @@ __global__ __launch_bounds__(kTableBlock) void k_simplify_records(SimplifyView m
   }
 }
 
-__global__ __launch_bounds__(256) void k_simplify_copy(const int32_t* __restrict__ segments, const int32_t* __restrict__ vertices,
-                                                       const int32_t* __restrict__ loops, const int32_t* __restrict__ refs,
-                                                       uint32_t n_segments, uint32_t n_loops, uint32_t n_refs,
-                                                       uint32_t slots, uint32_t capacity_vertices,
-                                                       int32_t* __restrict__ segments_out, int32_t* __restrict__ vertices_out,
-                                                       int32_t* __restrict__ loops_out, int32_t* __restrict__ refs_out,
-                                                       const SimplifyStatus* __restrict__ status) {
-  const uint32_t n_vertices = status->vertices_out;
-  if (n_vertices > capacity_vertices || n_vertices > slots || status->flags) return;
-  const size_t a = (size_t)n_segments * kMeshSegmentWords, b = a + (size_t)n_vertices * 2;
-  const size_t c = b + (size_t)n_loops * kMeshLoopWords, d = c + n_refs;
-  const size_t step = (size_t)gridDim.x * 256;
-  for (size_t k = (size_t)blockIdx.x * 256 + threadIdx.x; k < d; k += step) {
-    if (k < a) segments_out[k] = segments[k];
-    else if (k < b) vertices_out[k - a] = vertices[k - a];
-    else if (k < c) loops_out[k - b] = loops[k - b];
-    else refs_out[k - c] = refs[k - c];
-  }
-}
-
 inline dim3 GridOf(uint32_t n) { return dim3((std::max(n, 1u) + kTableBlock - 1) / kTableBlock); }
 
 }  // namespace
-
-size_t SimplifyTempBytes(int64_t segments) {
-  size_t scan = 0;
-  (void)hipcub::DeviceScan::ExclusiveSum(nullptr, scan, (const uint32_t*)nullptr, (uint32_t*)nullptr, (int)segments,
-                                         (hipStream_t) nullptr);
-  return scan;
-}
 
 hipError_t SimplifyDp(const SimplifyView& m, SimplifyStatus* status, hipStream_t stream) {
   const hipError_t e = hipMemsetAsync(m.kseg, 0xff, (size_t)m.slots * sizeof(uint32_t), stream);
@@ -490,25 +460,13 @@ hipError_t SimplifyClean(const SimplifyView& m, uint32_t* ncount, hipStream_t st
 
 hipError_t SimplifyTables(void* temp, size_t temp_bytes, const SimplifyView& m, const uint32_t* ncount, uint32_t* nfirst,
                           int32_t* segments_out, int32_t* vertices_out, SimplifyStatus* status, hipStream_t stream) {
-  const hipError_t e = hipcub::DeviceScan::ExclusiveSum(temp, temp_bytes, ncount, nfirst, (int)m.n_segments, stream);
+  const hipError_t e = ExclusiveSumU32(temp, temp_bytes, ncount, nfirst, (int)m.n_segments, stream);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_simplify_compact, GridOf(m.slots), dim3(kTableBlock), 0, stream, m, ncount, nfirst,
                      reinterpret_cast<int2*>(vertices_out));
   hipLaunchKernelGGL(k_simplify_records, GridOf(m.n_segments), dim3(kTableBlock), 0, stream, m, ncount, nfirst,
                      segments_out, status);
   return hipGetLastError();
-}
-
-void LaunchSimplifyCopy(const int32_t* segments, const int32_t* vertices, const int32_t* loops, const int32_t* refs,
-                        uint32_t n_segments, uint32_t n_loops, uint32_t n_refs, uint32_t slots,
-                        uint32_t capacity_vertices, int32_t* segments_out, int32_t* vertices_out, int32_t* loops_out,
-                        int32_t* refs_out, const SimplifyStatus* status, hipStream_t stream) {
-  const size_t words = (size_t)n_segments * kMeshSegmentWords + (size_t)slots * 2 + (size_t)n_loops * kMeshLoopWords +
-                       n_refs;
-  const size_t groups = std::max<size_t>((words + 255) / 256, 1);
-  hipLaunchKernelGGL(k_simplify_copy, dim3((unsigned)(groups < 2048 ? groups : 2048)), dim3(256), 0, stream, segments,
-                     vertices, loops, refs, n_segments, n_loops, n_refs, slots, capacity_vertices, segments_out,
-                     vertices_out, loops_out, refs_out, status);
 }
 
 }  // namespace vsg_render_impl

@@ -11,8 +11,7 @@
 // comparator uses eps = 1e-3f, the interval ends are ceil(x - 1e-6f) and floor(x) with the
 // exclusive-right rule.  The file is compiled with -ffp-contract=off.
 #include "render.h"
-
-#include <hipcub/hipcub.hpp>
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -162,10 +161,7 @@ __global__ __launch_bounds__(kVecBlock) void k_vec_pairs(const unsigned long lon
   // statistics and the flag: one atomic of each kind per wavefront
   const unsigned long long heads = __ballot(head);
   long long largest = head ? (long long)size : 0;
-  for (int s = 32; s > 0; s >>= 1) {
-    const long long o = __shfl_xor(largest, s);
-    largest = o > largest ? o : largest;
-  }
+  largest = WaveMax(largest);
   const bool any_bad = __ballot(bad) != 0, any_broken = __ballot(broken) != 0;
   if ((threadIdx.x & 63) == 0) {
     if (heads) atomicAdd(&status->groups, (unsigned long long)__popcll(heads));
@@ -182,21 +178,6 @@ void LaunchVecWalk(const VecLine* lines, int n_lines, unsigned long long* keys, 
   if (n_lines <= 0) return;
   hipLaunchKernelGGL(k_vec_walk, dim3((n_lines + kVecBlock - 1) / kVecBlock), dim3(kVecBlock), 0, stream, lines,
                      n_lines, keys, vals, status);
-}
-
-size_t VecSortTempBytes(int64_t n, int end_bit) {
-  size_t bytes = 0;
-  (void)hipcub::DeviceRadixSort::SortPairs(nullptr, bytes, (const unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, (const unsigned long long*)nullptr,
-                                           (unsigned long long*)nullptr, n, 0, end_bit, (hipStream_t) nullptr);
-  return bytes;
-}
-
-hipError_t VecSort(void* temp, size_t temp_bytes, const unsigned long long* keys_in, unsigned long long* keys_out,
-                   const unsigned long long* vals_in, unsigned long long* vals_out, int64_t n, int end_bit,
-                   hipStream_t stream) {
-  return hipcub::DeviceRadixSort::SortPairs(temp, temp_bytes, keys_in, keys_out, vals_in, vals_out, n, 0, end_bit,
-                                            stream);
 }
 
 void LaunchVecPairs(const unsigned long long* keys, const unsigned long long* vals, const VecLine* lines,

@@ -1,7 +1,7 @@
 // volume.hip -- a level's regions accumulated over frames: the supervoxel table of a volume session (gfx950).
 //
 // Input is what the level, colour and overlap pipelines leave on the device for one frame: the interval list
-// {y, left_x, right_x, id} grouped by region with every interval's 1-based record (LevelRank's scan), the
+// {y, left_x, right_x, id} grouped by region with every interval's 1-based record (the scan of HeadFlag), the
 // region table, the colour records, the overlap rows, columns and pairs.  The session keeps three tables, each
 // a sorted array of 64-bit keys with one record per key: rows (key = id), columns (key = label) and pairs
 // (key = id << 32 | label).  The records are the caller's records: vsg_render_volume_row, _col and _pair.
@@ -23,6 +23,7 @@
 //
 // Everything is integer arithmetic; no result depends on the order of execution.
 #include "render.h"
+#include "render_device.h"
 
 namespace vsg_render_impl {
 
@@ -229,8 +230,7 @@ __global__ __launch_bounds__(kVolumeBlock) void k_volume_merge_rows(
       rows[at] = r;
     }
   }
-#pragma unroll
-  for (int s = 32; s > 0; s >>= 1) covered += __shfl_xor(covered, s);
+  covered = WaveSum(covered);
   if ((threadIdx.x & 63) == 0 && covered) atomicAdd(&status->covered, covered);
 }
 
