@@ -1201,6 +1201,92 @@ typedef struct vsg_render_distance_stats {
 } vsg_render_distance_stats;                /* 56 bytes */
 int vsg_render_last_distance_stats(vsg_render* h, vsg_render_distance_stats* s);
 
+/* ---- Tree cut: the best non-horizontal cut of the hierarchy ----
+ *
+ * Every other call looks at the hierarchy one horizontal level at a time.  This one chooses, region by
+ * region, the level at which to stop: a coarse node where a gain says so, fine nodes elsewhere.
+ *
+ * Hierarchy, height L, ancestors A_l(r).  Exactly those of the persistence calls: the desc's own hierarchy
+ * replaces the kept one; L = max(1, levels); L > 65535 is VSG_ERR_INVALID; the lookups and refusals are those
+ * of vsg_render_id_image at level L - 1; a negative region id is refused; only regions that paint are looked
+ * up.
+ * Nodes.  A node is a pair (l, id) with id = A_l(r) for a region r of the level-0 id image.  Its pixels are
+ * those whose level-0 region r has A_l(r) = id, its leaves those regions, its children the distinct nodes
+ * (l - 1, A_{l-1}(r)) of its leaves; a node of level 0 has none.  A node with one child has that child's
+ * pixels.
+ * Gain g(n), int64.  Exactly one of two sources is given; both, or neither, is VSG_ERR_INVALID.
+ *   Labels (labels != NULL).  B is a label plane as in vsg_render_level_overlap: any int32, negative means no
+ *   label, host or device memory, labels_pitch 0 means W.  best(n) is the largest number of pixels n shares
+ *   with one label >= 0, ties go to the smallest label; without a labelled pixel best_label is -1 and
+ *   best_count 0.  g(n) = best(n) - penalty, 0 <= penalty <= 2^32; any other penalty is refused before the
+ *   handle is dereferenced, with either source.
+ *   Gain table (gains != NULL; num_gains may be 0).  vsg_render_cut_gain entries in host or device memory,
+ *   strictly ascending by (level, id), |gain| <= 2^32.  A table out of order, a duplicate or a gain out of
+ *   range is VSG_ERR_INVALID; the check runs on the device, and no output is touched.  Entries that name no
+ *   node of this frame are ignored; nodes not listed have gain 0.  best_label is -1 and best_count 0 in every
+ *   record.
+ * The cut.  Bottom-up: opt(n) = g(n) at level 0.  Above, S(n) is the sum of opt(c) over the children,
+ * keep(n) <=> g(n) >= S(n) -- a tie keeps the coarser node -- and opt(n) = max(g(n), S(n)).  Leaves always
+ * keep.  The selected node of a region r is (l*, A_{l*}(r)) with l* = max { l : keep(A_l(r)) }: the first kept
+ * node met when descending from the top.  The selected nodes partition the covered pixels, and the cut
+ * maximises the sum of g over all partitions into nodes.  total is that sum; it equals the sum of opt over the
+ * top-level nodes.  Everything fits in int64.
+ * Consequences.  With labels and penalty 0 the sum of best_count over the cut equals that of the level-0 rows
+ * of vsg_render_level_overlap, and the cut is the coarsest partition that reaches it.  With a penalty above
+ * every best(n) the cut is the top level.  As the penalty grows the number of nodes never increases and no
+ * region's l* decreases: the cuts are nested.
+ *
+ * nodes: one record per selected node, ascending by (level, id).  area: its pixels; leaves, children: as
+ * defined above; split_value = S(n), 0 where children == 0; reserved is 0.  plane (optional): W * H int32,
+ * rows W apart; each pixel holds the index of the record that covers it, -1 where the level-0 id image is
+ * -1; NULL means not wanted and not painted.  nodes and plane are in mem_out memory.
+ * *num_nodes and *total are set on VSG_OK and when the capacity is too small; in that case the call fails
+ * with VSG_ERR_INVALID and nothing is touched.  nodes == NULL and plane == NULL with capacity 0 asks for the
+ * count and the total only.  Vector-only descs are scan converted first.  The call returns after its stream
+ * work has finished.
+ * Size.  With R the regions of the level-0 image and P its (region, label) pairs (0 with a gain table),
+ * L * R + L * P > 2^27 is VSG_ERR_INVALID; the message names L, R and P.  The refusal comes once the counts
+ * are known, with nothing written.
+ * With labels the level-0 table is made by vsg_render_level_overlap's pipeline (vsg_render_last_overlap_stats
+ * then describes it), with a gain table by vsg_render_level_regions' (vsg_render_last_level_stats).
+ * A null handle, a null count or total pointer, an unknown memory kind, a pitch below W, both or neither
+ * source, or a penalty out of range is VSG_ERR_INVALID. */
+typedef struct vsg_render_cut_gain {   /* 16 bytes, no padding */
+  int32_t level, id;
+  int64_t gain;
+} vsg_render_cut_gain;
+
+typedef struct vsg_render_cut_node {   /* 48 bytes, no padding */
+  int32_t level, id, area, leaves, children, best_label, best_count, reserved;
+  int64_t gain, split_value;
+} vsg_render_cut_node;
+
+int vsg_render_tree_cut(vsg_render* h, const uint8_t* seg, size_t seg_len,
+                        const int32_t* labels, size_t labels_pitch, int mem_labels, int64_t penalty,
+                        const vsg_render_cut_gain* gains, size_t num_gains, int mem_gains,
+                        vsg_render_cut_node* nodes, size_t capacity_nodes, size_t* num_nodes,
+                        int32_t* plane, int64_t* total, int mem_out);
+
+/* Two DP paths.  With tree_nodes <= block_nodes one workgroup walks all levels in one launch; above it the
+ * levels are launched one by one.  0: always per level.  INT64_MAX: always one workgroup.  -1: the default
+ * (32768).  Any other negative value is VSG_ERR_INVALID.  The bytes of both paths are the same. */
+int vsg_render_tree_cut_tuning(vsg_render* h, int64_t block_nodes);
+
+/* What the last vsg_render_tree_cut of the handle did.  levels: L.  leaves: R.  tree_nodes: nodes of all
+ * levels.  pairs: P.  entries: the keys the two sorts saw, L * R + L * P.  cut_nodes, covered (pixels of the
+ * selected nodes), total.  block_nodes: the threshold in force.  Device times are HIP events around the
+ * stages: plane_us, the level-0 plane; table_us, the level-0 table of the sibling call; lift_us, the node
+ * keys, their sort, the node table and the gains; dp_us, the dynamic programme; paint_us, k_cut_select, the
+ * scan, k_cut_records and k_cut_paint.  dp_path: 0 not run (no node), 1 one workgroup, 2 per level.
+ * dp_launches: 1 on the one-workgroup path, L on the per-level path.  launches: everything the call enqueued;
+ * on the one-workgroup path it does not depend on L, on the per-level path it is that number + L - 1. */
+typedef struct vsg_render_cut_stats {
+  int64_t levels, leaves, tree_nodes, pairs, entries, cut_nodes, covered, total, block_nodes;
+  float plane_us, table_us, lift_us, dp_us, paint_us;
+  int dp_path, dp_launches, launches;
+} vsg_render_cut_stats;
+int vsg_render_last_cut_stats(vsg_render* h, vsg_render_cut_stats* s);
+
 /* srand(region_id); c[k] = rand() % 255 (segmentation_render.cpp:66-69) with glibc's generator
  * restated, so that process-global state stays untouched.  Host only; needs no device. */
 void vsg_render_color(int region_id, uint8_t c[3]);

@@ -44,6 +44,12 @@
 // persistence_levels=<L of the last frame> persistence_edge_pixels=<sum> persistence_edges=<sum>
 // persistence_fnv1a32=<hash of every frame's plane, then persistence, then level_sides bytes>.
 //
+//   --tree_cut <penalty>
+// asks vsg_render_tree_cut, for every frame after the first, for the best cut of the frame's hierarchy against
+// the previous frame's level-0 id image (fetched with vsg_render_id_image into host memory) with that penalty
+// and prints a line
+// tree_cut_nodes=<sum> tree_cut_total=<sum> tree_cut_fnv1a32=<hash of every compared frame's records, then plane>.
+//
 //   --level_pool <level> [--pool_components [--components_n8]]
 // asks vsg_render_level_pool for the sums, sums of squares, minima and maxima of five planar f32 channels (the
 // frame's B, G, R, then x and y) over that level's regions, or their connected components, in every frame, and
@@ -841,6 +847,76 @@ class LevelOverlapSinkUnit : public VideoUnit {
   uint32_t hash_ = 2166136261u;
 };
 
+// --tree_cut: the best non-horizontal cut of every frame's hierarchy after the first against the previous
+// frame's level-0 id image (vsg_render_tree_cut with labels): the records, then the plane.
+class TreeCutSinkUnit : public VideoUnit {
+ public:
+  TreeCutSinkUnit(int64_t penalty, int device) : penalty_(penalty), device_(device) {}
+  ~TreeCutSinkUnit() override { vsg_render_destroy(render_); }
+  bool OpenStreams(StreamSet* set) override {
+    seg_idx_ = FindStreamIdx("SegmentationStream", set);
+    if (seg_idx_ < 0) return false;
+    const SegmentationStream& s = set->at(seg_idx_)->As<SegmentationStream>();
+    vsg_render_options o;
+    vsg_render_default_options(&o);
+    o.has_video = 0;
+    o.device = device_;
+    if (vsg_render_create(&o, s.frame_width(), s.frame_height(), &render_) != VSG_OK) {
+      render_ = nullptr;
+      std::fprintf(stderr, "ERROR: could not create the HIP renderer: %s\n", vsg_render_last_error());
+      return false;
+    }
+    previous_.resize((size_t)s.frame_width() * s.frame_height());
+    plane_.resize(previous_.size());
+    return true;
+  }
+  void ProcessFrame(FrameSetPtr input, std::list<FrameSetPtr>* output) override {
+    const SegmentationDesc& desc = input->at(seg_idx_)->As<PointerFrame<SegmentationDesc>>().Ref();
+    const uint8_t* seg = reinterpret_cast<const uint8_t*>(desc.wire.data());
+    if (have_previous_) {
+      size_t n = 0;
+      int64_t total = 0;
+      VF_CHECK(vsg_render_tree_cut(render_, seg, desc.wire.size(), previous_.data(), 0, VSG_MEM_HOST, penalty_,
+                                   nullptr, 0, VSG_MEM_HOST, nullptr, 0, &n, nullptr, &total, VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+      nodes_buf_.resize(std::max<size_t>(n, 1));
+      VF_CHECK(vsg_render_tree_cut(render_, seg, desc.wire.size(), previous_.data(), 0, VSG_MEM_HOST, penalty_,
+                                   nullptr, 0, VSG_MEM_HOST, nodes_buf_.data(), n, &n, plane_.data(), &total,
+                                   VSG_MEM_HOST) == VSG_OK,
+               vsg_render_last_error());
+      Hash(nodes_buf_.data(), n * sizeof(vsg_render_cut_node));
+      Hash(plane_.data(), plane_.size() * sizeof(int32_t));
+      nodes_ += (long)n;
+      total_ += (long long)total;
+    }
+    VF_CHECK(vsg_render_id_image(render_, seg, desc.wire.size(), 0, previous_.data(), VSG_MEM_HOST) == VSG_OK,
+             vsg_render_last_error());
+    have_previous_ = true;
+    output->push_back(input);
+  }
+  uint32_t hash() const { return hash_; }
+  long nodes() const { return nodes_; }
+  long long total() const { return total_; }
+
+ private:
+  void Hash(const void* p, size_t n) {
+    const uint8_t* b = static_cast<const uint8_t*>(p);
+    for (size_t k = 0; k < n; ++k) {
+      hash_ ^= b[k];
+      hash_ *= 16777619u;
+    }
+  }
+  int64_t penalty_;
+  int device_, seg_idx_ = -1;
+  vsg_render* render_ = nullptr;
+  bool have_previous_ = false;
+  std::vector<int32_t> previous_, plane_;
+  std::vector<vsg_render_cut_node> nodes_buf_;
+  long nodes_ = 0;
+  long long total_ = 0;
+  uint32_t hash_ = 2166136261u;
+};
+
 // --boundary_distance and --boundary_benchmark: the squared distance to a level's edges of every frame
 // (vsg_render_boundary_distance), and the boundary records of all levels of every frame after the first
 // against the previous frame's level-0 id image (vsg_render_boundary_benchmark).  level < 0 or
@@ -1215,6 +1291,9 @@ struct Flags {
   // vsg_render_persistence_image and vsg_render_persistence_graph for every frame; the graph's
   // neighbourhood is --adjacency_n8's
   bool persistence = false;
+  // vsg_render_tree_cut with this penalty for every frame after the first, against the previous frame's
+  // level-0 id image; < 0: off
+  long long tree_cut = -1;
   // vsg_render_level_colors and vsg_render_mean_frame at this level for every frame; < 0: off.  Of the
   // regions, or of the components (N4, or N8 with --components_n8) with --colors_components
   int level_colors = -1;
@@ -1336,6 +1415,7 @@ bool ParseFlags(int argc, char** argv, Flags* f) {
     else if (a == "level_overlap") f->level_overlap = atoi(v.c_str());
     else if (a == "overlap_components") f->overlap_components = bv;
     else if (a == "persistence") f->persistence = bv;
+    else if (a == "tree_cut") f->tree_cut = atoll(v.c_str());
     else if (a == "level_colors") f->level_colors = atoi(v.c_str());
     else if (a == "colors_components") f->colors_components = bv;
     else if (a == "level_pool") f->level_pool = atoi(v.c_str());
@@ -1611,6 +1691,12 @@ int main(int argc, char** argv) {
     overlap_sink->AttachTo(input);
     input = overlap_sink.get();
   }
+  std::unique_ptr<TreeCutSinkUnit> tree_cut_sink;
+  if (FLAGS.tree_cut >= 0) {
+    tree_cut_sink.reset(new TreeCutSinkUnit(FLAGS.tree_cut, FLAGS.device));
+    tree_cut_sink->AttachTo(input);
+    input = tree_cut_sink.get();
+  }
   std::unique_ptr<PersistenceSinkUnit> persistence_sink;
   if (FLAGS.persistence) {
     persistence_sink.reset(new PersistenceSinkUnit(FLAGS.adjacency_n8, FLAGS.device));
@@ -1752,6 +1838,10 @@ int main(int argc, char** argv) {
   if (overlap_sink) {
     std::printf("level_overlap_rows=%ld overlap_cols=%ld overlap_pairs=%ld overlap_fnv1a32=%08x\n",
                 overlap_sink->rows(), overlap_sink->cols(), overlap_sink->pairs(), overlap_sink->hash());
+  }
+  if (tree_cut_sink) {
+    std::printf("tree_cut_nodes=%ld tree_cut_total=%lld tree_cut_fnv1a32=%08x\n", tree_cut_sink->nodes(),
+                tree_cut_sink->total(), tree_cut_sink->hash());
   }
   if (persistence_sink) {
     std::printf("persistence_levels=%d persistence_edge_pixels=%ld persistence_edges=%ld persistence_fnv1a32=%08x\n",

@@ -101,6 +101,17 @@ class VsgRenderPersistenceStats(_capi.Structure):
     ]
 
 
+class VsgRenderCutStats(_capi.Structure):
+    _fields_ = [
+        ("levels", C.c_int64), ("leaves", C.c_int64), ("tree_nodes", C.c_int64), ("pairs", C.c_int64),
+        ("entries", C.c_int64), ("cut_nodes", C.c_int64), ("covered", C.c_int64), ("total", C.c_int64),
+        ("block_nodes", C.c_int64),
+        ("plane_us", C.c_float), ("table_us", C.c_float), ("lift_us", C.c_float), ("dp_us", C.c_float),
+        ("paint_us", C.c_float),
+        ("dp_path", C.c_int), ("dp_launches", C.c_int), ("launches", C.c_int),
+    ]
+
+
 class VsgRenderColorStats(_capi.Structure):
     _fields_ = [
         ("groups", C.c_int64), ("intervals", C.c_int64), ("covered", C.c_int64),
@@ -323,6 +334,19 @@ BOUNDARY_SCORE_DTYPE = np.dtype([
 assert BOUNDARY_SCORE_DTYPE.itemsize == 32
 BOUNDARY_SCORE_WORDS = 4
 
+# vsg_render_cut_node (48 bytes) and vsg_render_cut_gain (16 bytes); as int32 words in torch tensors
+CUT_NODE_DTYPE = np.dtype([
+    ("level", np.int32), ("id", np.int32), ("area", np.int32), ("leaves", np.int32), ("children", np.int32),
+    ("best_label", np.int32), ("best_count", np.int32), ("reserved", np.int32),
+    ("gain", np.int64), ("split_value", np.int64)])
+assert CUT_NODE_DTYPE.itemsize == 48
+CUT_NODE_WORDS = 12
+CUT_GAIN_DTYPE = np.dtype([("level", np.int32), ("id", np.int32), ("gain", np.int64)])
+assert CUT_GAIN_DTYPE.itemsize == 16
+CUT_GAIN_WORDS = 4
+CUT_MAX_PENALTY = 1 << 32
+CUT_BLOCK_ALWAYS = (1 << 63) - 1   # tree_cut_tuning: always one workgroup
+
 # VSG_RENDER_DISTANCE_NONE, VSG_RENDER_MAX_TOLERANCE_SQ
 DISTANCE_NONE = 0x7fffffff
 MAX_TOLERANCE_SQ = 4096
@@ -344,6 +368,7 @@ EXPORTED_SYMBOLS = [
     "vsg_render_level_overlap", "vsg_render_last_overlap_stats",
     "vsg_render_persistence_image", "vsg_render_persistence_frame", "vsg_render_persistence_graph",
     "vsg_render_last_persistence_stats",
+    "vsg_render_tree_cut", "vsg_render_tree_cut_tuning", "vsg_render_last_cut_stats",
     "vsg_render_level_colors", "vsg_render_mean_frame", "vsg_render_last_color_stats",
     "vsg_render_volume_begin", "vsg_render_volume_add", "vsg_render_volume_table", "vsg_render_last_volume_stats",
     "vsg_render_level_pool", "vsg_render_level_unpool", "vsg_render_last_pool_stats",
@@ -444,6 +469,11 @@ def lib():
     L.vsg_render_boundary_benchmark.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, vp,
                                                 C.c_size_t, C.POINTER(C.c_size_t), C.c_int]
     L.vsg_render_last_distance_stats.argtypes = [vp, C.POINTER(VsgRenderDistanceStats)]
+    L.vsg_render_tree_cut.argtypes = [vp, C.c_char_p, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int64, vp, C.c_size_t,
+                                      C.c_int, vp, C.c_size_t, C.POINTER(C.c_size_t), vp, C.POINTER(C.c_int64),
+                                      C.c_int]
+    L.vsg_render_tree_cut_tuning.argtypes = [vp, C.c_int64]
+    L.vsg_render_last_cut_stats.argtypes = [vp, C.POINTER(VsgRenderCutStats)]
     _handle = L
     return L
 
@@ -1389,6 +1419,76 @@ class SegmentationRenderer(_capi.Handle):
         check(lib().vsg_render_last_distance_stats(self.h, C.byref(s)))
         return s.as_dict()
 
+    def tree_cut(self, seg_bytes, labels=None, penalty=0, gains=None, plane=True, nodes_out=None, plane_out=None):
+        """The best non-horizontal cut of the desc's hierarchy: (nodes, plane, total).  Exactly one source of
+        gains: labels, an H x W int32 plane as level_overlap's `other` (a node gains the pixels it shares with
+        its best label, minus penalty), or gains, a CUT_GAIN_DTYPE array (or a torch CUDA (n, 4) int32 tensor
+        of the same bytes) strictly ascending by (level, id).  nodes: a CUT_NODE_DTYPE array, one record per
+        selected node by ascending (level, id); plane: H x W int32, the index of the record that covers each
+        pixel, -1 where no region is, or None with plane=False; total: the sum of the selected nodes' gains.
+        Without outputs the count is asked for first and the arrays are allocated exactly.  nodes_out (and
+        plane_out when a plane is wanted): buffers to fill instead, both numpy or both torch CUDA tensors
+        ((capacity, 12) int32 and H x W int32); the filled part of nodes_out is returned."""
+        seg_bytes = bytes(seg_bytes)
+        p_labels, pitch, mem_labels = None, 0, VSG_MEM_HOST
+        if labels is not None:
+            p_labels, pitch, mem_labels = self._other_ptr(labels)
+        p_gains, n_gains, mem_gains = None, 0, VSG_MEM_HOST
+        keep = None
+        if gains is not None:
+            if _capi.is_torch(gains):
+                if gains.dim() != 2 or gains.shape[1] != CUT_GAIN_WORDS or str(gains.dtype) != "torch.int32":
+                    raise ValueError("gains has to be (n, %d) int32" % CUT_GAIN_WORDS)
+            elif gains.dtype != CUT_GAIN_DTYPE or gains.ndim != 1:
+                raise ValueError("gains has to be a one-dimensional CUT_GAIN_DTYPE array")
+            n_gains = int(gains.shape[0])
+            if n_gains == 0:
+                keep = np.zeros(1, CUT_GAIN_DTYPE)    # an empty table still says "a gain table"
+                p_gains, mem_gains = _capi.contiguous_ptr(keep)
+            else:
+                p_gains, mem_gains = _capi.contiguous_ptr(gains)
+        args = (self.h, seg_bytes, len(seg_bytes), p_labels, pitch, mem_labels, int(penalty), p_gains, n_gains,
+                mem_gains)
+        n, total = C.c_size_t(), C.c_int64()
+        if nodes_out is None:
+            if plane_out is not None:
+                raise ValueError("pass nodes_out with plane_out")
+            check(lib().vsg_render_tree_cut(*args, None, 0, C.byref(n), None, C.byref(total), VSG_MEM_HOST))
+            nodes_out = np.empty(n.value, CUT_NODE_DTYPE)
+            if plane:
+                plane_out = np.empty((self.H, self.W), np.int32)
+        elif plane and plane_out is None:
+            raise ValueError("pass plane_out with nodes_out, or plane=False")
+        if _capi.is_torch(nodes_out):
+            if nodes_out.dim() != 2 or nodes_out.shape[1] != CUT_NODE_WORDS or str(nodes_out.dtype) != "torch.int32":
+                raise ValueError("nodes_out has to be (capacity, %d) int32" % CUT_NODE_WORDS)
+        elif nodes_out.dtype != CUT_NODE_DTYPE or nodes_out.ndim != 1:
+            raise ValueError("nodes_out has to be a one-dimensional CUT_NODE_DTYPE array")
+        p_nodes, mem_out = _capi.contiguous_ptr(nodes_out)
+        p_plane = None
+        if plane:
+            if tuple(plane_out.shape) != (self.H, self.W) or str(plane_out.dtype).replace("torch.", "") != "int32":
+                raise ValueError("plane_out has to be %d x %d int32" % (self.H, self.W))
+            p_plane, mem_plane = _capi.contiguous_ptr(plane_out)
+            if mem_plane != mem_out:
+                raise ValueError("all outputs have to be in the same kind of memory")
+        else:
+            plane_out = None
+        check(lib().vsg_render_tree_cut(*args, p_nodes, nodes_out.shape[0], C.byref(n), p_plane, C.byref(total),
+                                        mem_out))
+        return nodes_out[:n.value], plane_out, total.value
+
+    def tree_cut_tuning(self, block_nodes=-1):
+        """The threshold between tree_cut's two DP paths: one workgroup up to block_nodes tree nodes, a launch
+        per level above.  0: always per level; CUT_BLOCK_ALWAYS: always one workgroup; -1: the default."""
+        check(lib().vsg_render_tree_cut_tuning(self.h, int(block_nodes)))
+
+    def last_cut_stats(self):
+        """vsg_render_last_cut_stats of the last tree_cut call, as a dict."""
+        s = VsgRenderCutStats()
+        check(lib().vsg_render_last_cut_stats(self.h, C.byref(s)))
+        return s.as_dict()
+
     def last_vector_stats(self):
         """vsg_render_last_vector_stats of the last call, as a dict."""
         s = VsgRenderVectorStats()
@@ -1417,6 +1517,36 @@ def overlap_scores(rows, pairs):
     ue_sum = int(np.minimum(count, inside - count).sum())
     return {"n": n, "asa_sum": asa_sum, "ue_sum": ue_sum,
             "asa": asa_sum / n if n else None, "ue": ue_sum / n if n else None}
+
+
+def cut_scores(nodes):
+    """What a cut amounts to: {"nodes", "best_sum" (the sum of best_count: the numerator of the achievable
+    segmentation accuracy of the cut), "per_level" (level -> number of selected nodes)}."""
+    nodes = np.asarray(nodes)
+    levels, counts = np.unique(nodes["level"], return_counts=True)
+    return {"nodes": int(len(nodes)), "best_sum": int(nodes["best_count"].astype(np.int64).sum()),
+            "per_level": {int(l): int(c) for l, c in zip(levels, counts)}}
+
+
+def tree_cut_for_count(renderer, seg_bytes, labels, max_nodes):
+    """The smallest penalty whose cut of `labels` has at most max_nodes nodes: (penalty, nodes, plane, total).
+    The cuts are nested (the node count never rises with the penalty), so the penalty is found by bisection
+    over [0, 2^32].  When even the top level has more nodes, that cut (penalty 2^32) is returned."""
+    def count(penalty):
+        nodes, _, _ = renderer.tree_cut(seg_bytes, labels=labels, penalty=penalty, plane=False)
+        return len(nodes)
+    lo, hi = 0, CUT_MAX_PENALTY
+    if count(lo) > max_nodes:
+        while hi - lo > 1:        # count(lo) > max_nodes; count(hi) <= max_nodes, or hi is the end
+            mid = (lo + hi) // 2
+            if count(mid) > max_nodes:
+                lo = mid
+            else:
+                hi = mid
+    else:
+        hi = 0
+    nodes, plane, total = renderer.tree_cut(seg_bytes, labels=labels, penalty=hi)
+    return hi, nodes, plane, total
 
 
 def volume_scores(rows, cols, pairs):

@@ -63,6 +63,7 @@ int vsg_render_create(const vsg_render_options* o, int width, int height, vsg_re
     h->mesh.Init();
     h->simp.Init();
     h->vol.Init();
+    h->cut.Init();
     h->d_plane.Reserve((size_t)h->pitch * height * sizeof(uint32_t), &h->allocations);
     *out = h.release();
   });

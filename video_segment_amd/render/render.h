@@ -744,6 +744,80 @@ void LaunchVolumeGather(const void* src, void* dst, const uint32_t* perm, uint32
 int LaunchVolumeReadout(const VolumeTables& tables, void* rows, void* cols, void* pairs, VolumeStatus* status,
                         hipStream_t stream);
 
+// ---- tree cut (tree_cut.hip): the best non-horizontal cut of the hierarchy ---------------------------------
+
+constexpr int kCutNodeWords = 12;   // vsg_render_cut_node as int32 words
+
+enum CutFlag {
+  CUT_FLAG_RANGE = 1,        // a leaf, a key, a node or a record was out of range
+  CUT_FLAG_GAIN_ORDER = 2,   // the gain table is not strictly ascending by (level, id)
+  CUT_FLAG_GAIN_RANGE = 4,   // a gain of the table is beyond +-2^32
+};
+
+// Written by the cut kernels; read by the host after the lift and after the records.
+struct CutStatus {
+  uint32_t flags;
+  uint32_t tree_nodes;          // nodes of all levels
+  uint32_t cut_nodes, pad;      // selected nodes
+  long long total;              // sum of their gains
+  unsigned long long covered;   // sum of their areas
+};
+
+// vsg_render_cut_gain.
+struct CutGain {
+  int32_t level, id;
+  long long gain;
+};
+static_assert(sizeof(CutGain) == 16, "read as is");
+
+// The node table, one array per field, T entries each.  area, leaves, children, sum have to be zero before
+// LaunchCutNodeTable.
+struct CutNodes {
+  int32_t *level, *id, *parent, *best_label, *best_count;
+  uint32_t *area, *leaves, *children, *keep;
+  long long *gain, *split;
+  unsigned long long* sum;   // what the children have added so far
+};
+
+// list: R entries of `words` int32 by ascending id, word 0 the id, word area_word the area.  ids: the n_ids
+// ascending ids the ancestor table has columns for.
+void LaunchCutLeaves(const int32_t* list, uint32_t words, uint32_t area_word, uint32_t R, const int32_t* ids,
+                     uint32_t n_ids, int32_t* leaf_id, uint32_t* leaf_area, uint32_t* leaf_col, CutStatus* status,
+                     hipStream_t stream);
+// keys[l * R + j] = l << 32 | A_l(leaf j), vals[i] = i; table as in persistence.hip, n_ids values a row.
+void LaunchCutNodeKeys(const int32_t* leaf_id, const uint32_t* leaf_col, uint32_t R, const int32_t* table,
+                       uint32_t n_ids, uint32_t L, unsigned long long* keys, uint32_t* vals, hipStream_t stream);
+// map[l * R + j] = node; level_first[0 .. L]; status->tree_nodes.  vals, rank: of the L * R sorted keys.
+void LaunchCutNodeMap(const uint32_t* vals, const uint32_t* rank, uint32_t R, uint32_t L, uint32_t* map,
+                      uint32_t* level_first, CutStatus* status, hipStream_t stream);
+void LaunchCutNodeTable(const unsigned long long* keys, const uint32_t* vals, const uint32_t* rank,
+                        const uint32_t* map, const uint32_t* leaf_area, uint32_t R, uint32_t L, uint32_t T,
+                        const CutNodes& nodes, hipStream_t stream);
+// pairs: P vsg_render_overlap_pair of level 0.  keys[l * P + e] = node << label_bits | label, counts likewise.
+void LaunchCutPairKeys(const int32_t* pairs, uint32_t P, const uint32_t* map, uint32_t R, uint32_t L, int label_bits,
+                       unsigned long long* keys, uint32_t* counts, hipStream_t stream);
+// Sorted keys with their counts and ranks -> best[node] = count << 31 | (2^31 - 1 - label) of the best label.
+// sums (n) and best (T) have to be zero before.  Two launches.
+void LaunchCutBest(const unsigned long long* keys, const uint32_t* counts, const uint32_t* rank, uint32_t n,
+                   int label_bits, uint32_t T, uint32_t* sums, unsigned long long* best, CutStatus* status,
+                   hipStream_t stream);
+void LaunchCutGainLabels(const unsigned long long* best, uint32_t T, int64_t penalty, const CutNodes& nodes,
+                         hipStream_t stream);
+void LaunchCutGainCheck(const CutGain* gains, size_t n, CutStatus* status, hipStream_t stream);
+void LaunchCutGainLookup(const CutGain* gains, size_t n, uint32_t T, const CutNodes& nodes, hipStream_t stream);
+// The dynamic programme: all levels in one workgroup, or the nodes [first, end) of one level.
+void LaunchCutDpBlock(const uint32_t* level_first, uint32_t L, const CutNodes& nodes, hipStream_t stream);
+void LaunchCutDpLevel(uint32_t first, uint32_t end, const CutNodes& nodes, hipStream_t stream);
+// leaf_node[j]: the selected node of leaf j; selected[node] = 1 for those (zero before).
+void LaunchCutSelect(const uint32_t* map, uint32_t R, uint32_t L, uint32_t T, const uint32_t* keep,
+                     uint32_t* leaf_node, uint32_t* selected, CutStatus* status, hipStream_t stream);
+// place: the inclusive scan of selected.  records: room for `capacity`; status->cut_nodes, total, covered.
+void LaunchCutRecords(const uint32_t* selected, const uint32_t* place, uint32_t T, uint32_t capacity,
+                      const CutNodes& nodes, int32_t* records, CutStatus* status, hipStream_t stream);
+// ids, out: W * H int32, rows W apart.
+void LaunchCutPaint(const int32_t* ids, int W, int H, const int32_t* leaf_id, uint32_t R, const uint32_t* leaf_node,
+                    const uint32_t* place, int32_t* out, CutStatus* status, hipStream_t stream);
+
 }  // namespace vsg_render_impl
 
 #endif  // VSG_RENDER_RENDER_H_

@@ -18,6 +18,7 @@
 //   capi_adjacency.inc     vsg_render_level_adjacency
 //   capi_overlap.inc       vsg_render_level_overlap
 //   capi_persistence.inc   vsg_render_persistence_image, _frame, _graph
+//   capi_tree_cut.inc      vsg_render_tree_cut, _tuning
 //   capi_colors.inc        vsg_render_level_colors, vsg_render_mean_frame
 //   capi_pool.inc          vsg_render_level_pool, vsg_render_level_unpool
 //   capi_volume.inc        vsg_render_volume_begin, _add, _table
@@ -48,6 +49,7 @@
 #include "capi_adjacency.inc"
 #include "capi_overlap.inc"
 #include "capi_persistence.inc"
+#include "capi_tree_cut.inc"
 #include "capi_colors.inc"
 #include "capi_pool.inc"
 #include "capi_volume.inc"

@@ -11,6 +11,7 @@ using vsg_render_impl::BoundStatus;
 using vsg_render_impl::ColorStatus;
 using vsg_render_impl::CompStatus;
 using vsg_render_impl::ContourStatus;
+using vsg_render_impl::CutStatus;
 using vsg_render_impl::DistStatus;
 using vsg_render_impl::Interval;
 using vsg_render_impl::LevelStatus;
@@ -41,6 +42,8 @@ enum SimplifyStage { SMP_DP = 0, SMP_CLEAN, SMP_TABLE, SMP_STAGES };
 // DST_PLANE: the upload of a host label plane
 enum DistStage { DST_PLANE = 0, DST_CLASSIFY, DST_COLUMNS, DST_ROWS, DST_MATCH, DST_STAGES };
 enum VolumeStage { VOL_GEOMETRY = 0, VOL_MERGE, VOL_SORT, VOL_TABLE, VOL_STAGES };
+// CUT_WAIT: the stream idles while the host reads the number of nodes, then of records; reported with no stage
+enum CutStage { CUT_LIFT = 0, CUT_DP, CUT_PAINT, CUT_WAIT, CUT_STAGES };
 
 double NowMs() {
   return std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now().time_since_epoch())
@@ -213,6 +216,25 @@ struct VolumeState {
   void Init() { InitFamily(this, VOL_STAGES); }
 };
 
+// tree cut: the threshold between the two DP paths; what there is per leaf (id, area, ancestor column, selected
+// node); per (level, leaf) (unsorted and sorted keys and values, ranks, the map to nodes); per node (the table's
+// fields, the best labels' words, marks and places); per (level, pair) (unsorted and sorted keys and counts,
+// ranks, sums); the first node of every level and the pinned block it comes back through; a host gain table on
+// the device; the records; the plane of a host output; the status words and the pinned block they and host
+// outputs come back through
+struct CutState {
+  StageClock clock;
+  int64_t block_nodes = 32768;
+  Block leaves, lift, nodes, pairs, levels, levels_seen, gains, records, plane, status, seen;
+  vsg_render_cut_stats stats;
+  void Init() {
+    levels_seen.pinned = true;
+    seen.pinned = true;
+    clock.Create(12);   // Begin, and the marks of the longest call
+    std::memset(&stats, 0, sizeof(stats));
+  }
+};
+
 // The number of bits of a sort key's field that holds values up to `value`: at least 1, at most `limit`.
 int BitsFor(uint64_t value, int limit) {
   int bits = 1;
@@ -264,6 +286,7 @@ struct vsg_render {
   MeshState mesh;
   SimplifyState simp;
   VolumeState vol;
+  CutState cut;
 
   ~vsg_render() {
     if (!stream) return;

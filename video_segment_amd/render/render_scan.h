@@ -141,6 +141,19 @@ struct OvlColHeads {
   }
 };
 
+// ---- tree_cut.hip: whole keys, and marks ---------------------------------------------------------------------
+
+// Sorted key i -> 1 if it differs from the key before: the sums are the (1-based) ranks of the distinct keys.
+struct CutKeyHead {
+  const unsigned long long* keys;
+  __host__ __device__ uint32_t operator()(uint32_t i) const { return (i == 0 || keys[i] != keys[i - 1]) ? 1u : 0u; }
+};
+// Node i -> its mark (0 or 1): the sums are the (1-based) places of the marked nodes.
+struct CutMark {
+  const uint32_t* marks;
+  __host__ __device__ uint32_t operator()(uint32_t i) const { return marks[i]; }
+};
+
 }  // namespace vsg_render_impl
 
 #endif  // VSG_RENDER_RENDER_SCAN_H_
